@@ -2,7 +2,15 @@
 """DS2 training throughput on MI355X: audio-seconds/sec, 5xBiGRU-800, 32 x 10 s per GPU.
 
 python bench.py [--gpus N --steps K --warmup W]          (N=1: plain process)
+python bench.py --full ...                               (adds the CPU baseline leg)
+python bench.py --dump-outputs DIR ...                   (what the last timed step computed)
 python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the line (``cpu_baseline`` null).
+``--full`` adds the legs that take runs of their own: today the oracle's CPU training and
+forward steps (``cpu_baseline``, a few minutes).  ``--dump-outputs DIR`` writes what a caller
+of the timed path holds after its last step as DIR/<name>.npy (``dump_outputs``); the inputs
+and the initial weights are seeded, so two builds can be compared array for array.
 
 One step = the reference's train_batch (train.py:555-632) on the HIP path:
 forward (conv/BN/5 BiGRU/FC/softmax), greedy decode + per-batch CER/WER, CTC (+grad), backward,
@@ -297,12 +305,51 @@ def cpu_baseline(train_steps: int = 3, fwd_steps: int = 2, budget_s: float = 150
                       f"(train mode, no grad): 1 warm-up + {fwd_steps} timed (median {fw:.1f} s)"}
 
 
+DUMP_SAMPLE = 4 << 20      # elements kept of each flat array larger than this (16 MB of fp32)
+DUMP_SEED = 20240607
+
+
+def dump_outputs(path: str, tr, loss) -> None:
+    """What a caller of Trainer.train_batch holds after the last timed step, as
+    <path>/<name>.npy: the returned loss (float32 [1]), the running (WER, CER, words, chars)
+    sums over every step of the run (float64 [4]), and the parameters and their gradients
+    (float32, model.named_parameters() order, flattened and concatenated).  Arrays above
+    DUMP_SAMPLE elements are sampled at fixed positions, the same in every run of the same
+    model: the sorted draws of torch.randint(0, n, (DUMP_SAMPLE,)) from a CPU generator seeded
+    with DUMP_SEED.  32 MB in all at the bench's shape."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    if loss.is_cuda:
+        torch.cuda.synchronize()
+    named = [p for _, p in tr.model.named_parameters() if p.requires_grad]
+    params = torch.cat([p.detach().reshape(-1) for p in named])
+    grads = torch.cat([p.grad.detach().reshape(-1) for p in named])
+    n = params.numel()
+    if n > DUMP_SAMPLE:
+        g = torch.Generator().manual_seed(DUMP_SEED)
+        idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=g).sort().values.to(params.device)
+        params, grads = params[idx], grads[idx]
+    np.save(os.path.join(path, "loss.npy"),
+            loss.detach().reshape(1).float().cpu().numpy())
+    np.save(os.path.join(path, "score.npy"),
+            np.array([tr.train_wer, tr.train_cer, tr.num_words, tr.num_chars], dtype=np.float64))
+    np.save(os.path.join(path, "params.npy"), params.float().cpu().numpy())
+    np.save(os.path.join(path, "grads.npy"), grads.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own (the CPU baseline); "
+                         "a plain run only sets up, warms up, times the steps and prints")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed (loss, "
+                         "scores, parameters, gradients) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-steps", type=int, default=3,
                     help="timed oracle training steps of the CPU baseline (after 1 warm-up)")
     ap.add_argument("--probe", default="ds2_sgemm_ws,ds2_sgemm_amax_ws",
@@ -312,6 +359,8 @@ def main():
                          "pcm: raw 16 kHz PCM resident in HBM, the device STFT + max_frame "
                          "normalisation inside every timed step (SURVEY 8d secondary variant)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -393,6 +442,8 @@ def main():
         dt = float(tt.item())
     final_loss = float(loss.item())
     pk, fk, bk, ak = (p_.summary() for p_ in probes)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tr, loss)
 
     if rank == 0:
         audio = world * BATCH * SECONDS * args.steps
@@ -452,7 +503,7 @@ def main():
         # the roofline object is the dominant kernel family of the step (most ms per step)
         roof = max(kernels.values(), key=lambda e: e["ms_per_step"]) if kernels else None
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cpu = cpu_baseline(args.cpu_steps)
         out = {
             "metric": "audio-seconds/sec training, DS2 5x BiGRU-800 bs32, at 1/2/4/8 MI355X",

@@ -1065,7 +1065,8 @@ def test_lookahead(dev, t, n, h, context, fused):
 # ---------------------------------------------------------------------------- CTC
 @pytest.mark.parametrize("t,act,lab", [
     (60, [60, 55, 40, 12, 30, 5], [20, 1, 0, 5, 14, 2]),
-    # several 32-step log-prob chunks of the scan; lengths on and next to chunk edges
+    # one 256-frame log-prob stage of the scan, rows rescaled every 8th step; lengths on and
+    # next to multiples of 32 (tests/test_gpu_ctc.py has the stage and rescale edges)
     (160, [160, 128, 97, 64, 33, 32], [70, 40, 30, 20, 10, 31])])
 def test_ctc_vs_torch(dev, t, act, lab):
     g = torch.Generator().manual_seed(9)

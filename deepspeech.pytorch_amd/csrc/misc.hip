@@ -1,5 +1,5 @@
 // Status strings, small elementwise/reduction kernels, softmax and the
-// clip + SGD-Nesterov optimizer tail.  All HBM-bound: float4 where the layout
+// clip + SGD-Nesterov / Adam optimizer tail.  All HBM-bound: float4 where the layout
 // allows, grid-stride loops capped at ~2048 blocks (256 CUs x 8).
 #include "common.h"
 
@@ -248,6 +248,136 @@ __global__ void clip_sgd_nesterov_kernel(float* __restrict__ p, const float* __r
   }
 }
 
+// The same update on g' = g*coef + wd*p (torch.optim.SGD adds the decay in step(), after
+// clip_grad_norm_ has scaled .grad).  g*coef is rounded on its own, as the clipped .grad is.
+__device__ __forceinline__ float decayed_grad(float g, float coef, float wd, float p) {
+#pragma clang fp contract(off)
+  const float gc = g * coef;
+  return fmaf(wd, p, gc);
+}
+
+__global__ void clip_sgd_nesterov_wd_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                            float* __restrict__ buf, int64_t numel, float lr,
+                                            float mom, float wd, float max_norm,
+                                            const float* __restrict__ norm,
+                                            const int* __restrict__ skip) {
+  if (skip != nullptr && *skip != 0) return;
+  float coef = 1.0f;
+  if (norm != nullptr && max_norm > 0.0f) {
+    coef = max_norm / (*norm + 1e-6f);
+    coef = fminf(coef, 1.0f);
+  }
+  const int64_t n4 = numel >> 2;
+  float4* p4 = reinterpret_cast<float4*>(p);
+  const float4* g4 = reinterpret_cast<const float4*>(g);
+  float4* b4 = reinterpret_cast<float4*>(buf);
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    float4 gv = g4[i], bv = b4[i], pv = p4[i];
+    gv.x = decayed_grad(gv.x, coef, wd, pv.x); gv.y = decayed_grad(gv.y, coef, wd, pv.y);
+    gv.z = decayed_grad(gv.z, coef, wd, pv.z); gv.w = decayed_grad(gv.w, coef, wd, pv.w);
+    bv.x = mom * bv.x + gv.x; bv.y = mom * bv.y + gv.y;
+    bv.z = mom * bv.z + gv.z; bv.w = mom * bv.w + gv.w;
+    pv.x -= lr * (gv.x + mom * bv.x); pv.y -= lr * (gv.y + mom * bv.y);
+    pv.z -= lr * (gv.z + mom * bv.z); pv.w -= lr * (gv.w + mom * bv.w);
+    b4[i] = bv;
+    p4[i] = pv;
+  }
+  for (int64_t i = (n4 << 2) + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < numel;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    float pv = p[i];
+    float gv = decayed_grad(g[i], coef, wd, pv);
+    float bv = mom * buf[i] + gv;
+    buf[i] = bv;
+    p[i] = pv - lr * (gv + mom * bv);
+  }
+}
+
+// torch.optim.Adam (single-tensor path; amsgrad, maximize, decoupled decay off) after
+// clip_grad_norm_.  The scalars every element shares: torch forms 1 - beta, the two bias
+// corrections and lr / (1 - beta1^t) in Python floats (double) and rounds each to float once.
+struct AdamScalars {
+  float coef, wd, w1, beta2, w2, neg_step, bc2_sqrt, eps;
+  bool decay;
+};
+
+__device__ __forceinline__ AdamScalars adam_scalars(double lr, double beta1, double beta2,
+                                                    double eps, double wd, float max_norm,
+                                                    const float* __restrict__ norm, int t) {
+  AdamScalars s;
+  s.coef = 1.0f;
+  if (norm != nullptr && max_norm > 0.0f) {
+    s.coef = max_norm / (*norm + 1e-6f);
+    s.coef = fminf(s.coef, 1.0f);
+  }
+  s.wd = static_cast<float>(wd);
+  s.decay = wd != 0.0;
+  s.w1 = static_cast<float>(1.0 - beta1);
+  s.beta2 = static_cast<float>(beta2);
+  s.w2 = static_cast<float>(1.0 - beta2);
+  const double bc1 = 1.0 - pow(beta1, static_cast<double>(t));
+  const double bc2 = 1.0 - pow(beta2, static_cast<double>(t));
+  s.neg_step = static_cast<float>(-(lr / bc1));
+  s.bc2_sqrt = static_cast<float>(sqrt(bc2));
+  s.eps = static_cast<float>(eps);
+  return s;
+}
+
+// One element, in ATen's operation order (lerp_, mul_ + addcmul_, sqrt / div / add_,
+// addcdiv_), each product-sum fused where ATen's kernels fuse it:
+//   m += (1-b1) (g'-m);  v = fma((1-b2) g', g', b2 v);  p += (-step m) / (sqrt(v)/bc2 + eps)
+__device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v,
+                                            const AdamScalars& s) {
+#pragma clang fp contract(off)
+  float gp = g * s.coef;
+  if (s.decay) gp = fmaf(s.wd, p, gp);
+  m = fmaf(s.w1, gp - m, m);
+  v = fmaf(s.w2 * gp, gp, v * s.beta2);
+  const float denom = sqrtf(v) / s.bc2_sqrt + s.eps;
+  p = p + (s.neg_step * m) / denom;
+}
+
+// step: the count of steps taken so far, on the device (read here by every workgroup,
+// advanced by adam_advance_kernel behind this kernel on the same stream).
+__global__ void clip_adam_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                 float* __restrict__ m, float* __restrict__ v, int64_t numel,
+                                 double lr, double beta1, double beta2, double eps, double wd,
+                                 float max_norm, const float* __restrict__ norm,
+                                 const int* __restrict__ step, const int* __restrict__ skip) {
+  if (skip != nullptr && *skip != 0) return;
+  const AdamScalars s = adam_scalars(lr, beta1, beta2, eps, wd, max_norm, norm, *step + 1);
+  const int64_t n4 = numel >> 2;
+  float4* p4 = reinterpret_cast<float4*>(p);
+  const float4* g4 = reinterpret_cast<const float4*>(g);
+  float4* m4 = reinterpret_cast<float4*>(m);
+  float4* v4 = reinterpret_cast<float4*>(v);
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    float4 gv = g4[i], mv = m4[i], vv = v4[i], pv = p4[i];
+    adam_update(pv.x, gv.x, mv.x, vv.x, s);
+    adam_update(pv.y, gv.y, mv.y, vv.y, s);
+    adam_update(pv.z, gv.z, mv.z, vv.z, s);
+    adam_update(pv.w, gv.w, mv.w, vv.w, s);
+    m4[i] = mv;
+    v4[i] = vv;
+    p4[i] = pv;
+  }
+  for (int64_t i = (n4 << 2) + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < numel;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    float pv = p[i], mv = m[i], vv = v[i];
+    adam_update(pv, g[i], mv, vv, s);
+    m[i] = mv;
+    v[i] = vv;
+    p[i] = pv;
+  }
+}
+
+// One thread, launched behind clip_adam_kernel on its stream: a skipped step is not counted.
+__global__ void adam_advance_kernel(int* step, const int* skip) {
+  if (skip != nullptr && *skip != 0) return;
+  *step += 1;
+}
+
 __global__ void nan_guard_kernel(float* __restrict__ x, int64_t numel, int zero_nans,
                                  int* __restrict__ flag, unsigned char* __restrict__ mask) {
   int found = 0;
@@ -391,6 +521,41 @@ ds2_status_t ds2_clip_sgd_nesterov(float* params, const float* grads, float* mom
                      0, as_stream(stream), params, grads, momentum_buf, numel, lr, momentum,
                      max_norm, norm, skip_flag);
   return launch_status("ds2_clip_sgd_nesterov");
+}
+
+ds2_status_t ds2_clip_sgd_nesterov_wd(float* params, const float* grads, float* momentum_buf,
+                                      int64_t numel, float lr, float momentum,
+                                      float weight_decay, float max_norm, const float* norm,
+                                      const int* skip_flag, ds2_stream_t stream) {
+  if (numel < 0) return DS2_INVALID_VALUE;
+  if (((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grads) |
+        reinterpret_cast<uintptr_t>(momentum_buf)) & 15) != 0)
+    return DS2_INVALID_VALUE;
+  if (!(lr >= 0.0f) || !(weight_decay >= 0.0f)) return DS2_INVALID_VALUE;
+  if (numel == 0) return DS2_OK;
+  hipLaunchKernelGGL(clip_sgd_nesterov_wd_kernel, dim3(grid_for((numel >> 2) + 1, 256)),
+                     dim3(256), 0, as_stream(stream), params, grads, momentum_buf, numel, lr,
+                     momentum, weight_decay, max_norm, norm, skip_flag);
+  return launch_status("ds2_clip_sgd_nesterov_wd");
+}
+
+ds2_status_t ds2_clip_adam(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                           int64_t numel, double lr, double beta1, double beta2, double eps,
+                           double weight_decay, float max_norm, const float* norm, int* step,
+                           const int* skip_flag, ds2_stream_t stream) {
+  if (numel < 0 || step == nullptr) return DS2_INVALID_VALUE;
+  if (((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grads) |
+        reinterpret_cast<uintptr_t>(exp_avg) | reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15) != 0)
+    return DS2_INVALID_VALUE;
+  if (!(lr >= 0.0) || !(eps >= 0.0) || !(weight_decay >= 0.0)) return DS2_INVALID_VALUE;
+  if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return DS2_INVALID_VALUE;
+  if (numel == 0) return DS2_OK;
+  hipLaunchKernelGGL(clip_adam_kernel, dim3(grid_for((numel >> 2) + 1, 256)), dim3(256), 0,
+                     as_stream(stream), params, grads, exp_avg, exp_avg_sq, numel, lr, beta1,
+                     beta2, eps, weight_decay, max_norm, norm, step, skip_flag);
+  hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, as_stream(stream), step,
+                     skip_flag);
+  return launch_status("ds2_clip_adam");
 }
 
 ds2_status_t ds2_nan_guard(float* x, int64_t numel, int zero_nans, int* flag,

@@ -145,6 +145,10 @@ _PROTOS = {
     "ds2_optim_workspace_size": (_sz, [_c_i64]),
     "ds2_grad_norm": (_c_int, [_vp, _c_i64, _vp, _vp, _sz, _vp]),
     "ds2_clip_sgd_nesterov": (_c_int, [_vp, _vp, _vp, _c_i64, _c_f, _c_f, _c_f, _vp, _vp, _vp]),
+    "ds2_clip_sgd_nesterov_wd": (_c_int, [_vp, _vp, _vp, _c_i64, _c_f, _c_f, _c_f, _c_f, _vp, _vp,
+                                          _vp]),
+    "ds2_clip_adam": (_c_int, [_vp, _vp, _vp, _vp, _c_i64] + [ctypes.c_double] * 5
+                      + [_c_f, _vp, _vp, _vp, _vp]),
     "ds2_nan_guard": (_c_int, [_vp, _c_i64, _c_int, _vp, _vp, _vp]),
     "ds2_zero_masked": (_c_int, [_vp, _vp, _c_i64, _vp, _vp]),
     "ds2_scale_by_device_scalar": (_c_int, [_vp, _c_i64, _vp, _vp]),

@@ -1,7 +1,8 @@
-"""Training-step tail: flat parameter/gradient buffers, fused clip + SGD-Nesterov,
+"""Training-step tail: flat parameter/gradient buffers, fused clip + SGD-Nesterov or Adam,
 and the data-parallel gradient exchange.
 
-ref train.py:139-152 (SGD, momentum 0.9, nesterov=True, weight_decay 0),
+ref train.py:139-152 (build_optimizer: SGD with momentum, nesterov=True and --weight-decay,
+or Adam(lr); FusedSGD, FusedAdam and build_optimizer below),
 train.py:619-632 (zero_grad, backward, clip_grad_norm_(max_norm), NaN-skip, step),
 train.py:947-951 (DistributedDataParallel) and data/utils.py:40-44 (reduce_tensor).
 
@@ -109,16 +110,21 @@ class FlatParams:
 
 
 class FusedSGD:
-    """torch.optim.SGD(lr, momentum, nesterov=True) + clip_grad_norm_ on flat buffers."""
+    """torch.optim.SGD(lr, momentum, nesterov=True, weight_decay) + clip_grad_norm_ on flat
+    buffers.  weight_decay == 0 (the default) runs ds2_clip_sgd_nesterov, anything else
+    ds2_clip_sgd_nesterov_wd."""
 
     def __init__(self, flat: FlatParams, lr: float, momentum: float = 0.9,
-                 max_norm: float = 0.0, nesterov: bool = True):
+                 max_norm: float = 0.0, nesterov: bool = True, weight_decay: float = 0.0):
         if not nesterov:
             raise ValueError("FusedSGD implements the reference's nesterov=True update")
+        if weight_decay < 0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
         self.flat = flat
         self.lr = lr
         self.momentum = momentum
         self.max_norm = max_norm
+        self.weight_decay = weight_decay
         dev = flat.flat.device
         self.buf = torch.zeros_like(flat.flat)
         self.norm = torch.zeros(1, dtype=torch.float32, device=dev)
@@ -143,9 +149,16 @@ class FusedSGD:
         if self.max_norm > 0:
             self.grad_norm()
             norm_ptr = self.norm.data_ptr()
-        _lib.call("ds2_clip_sgd_nesterov", self.flat.flat.data_ptr(), self.flat.grad.data_ptr(),
-                  self.buf.data_ptr(), self.flat.numel, float(self.lr), float(self.momentum),
-                  float(self.max_norm), norm_ptr, _p(skip_flag), _stream())
+        if self.weight_decay == 0:
+            _lib.call("ds2_clip_sgd_nesterov", self.flat.flat.data_ptr(),
+                      self.flat.grad.data_ptr(), self.buf.data_ptr(), self.flat.numel,
+                      float(self.lr), float(self.momentum), float(self.max_norm), norm_ptr,
+                      _p(skip_flag), _stream())
+        else:
+            _lib.call("ds2_clip_sgd_nesterov_wd", self.flat.flat.data_ptr(),
+                      self.flat.grad.data_ptr(), self.buf.data_ptr(), self.flat.numel,
+                      float(self.lr), float(self.momentum), float(self.weight_decay),
+                      float(self.max_norm), norm_ptr, _p(skip_flag), _stream())
         self.steps += 1
 
     # ---- torch.optim.SGD's state_dict format (model.py:446 optim_dict; train.py:843) ----
@@ -158,13 +171,15 @@ class FusedSGD:
         # the installed torch's own SGD param_group keys, so the dict loads into
         # torch.optim.SGD of this torch version unchanged
         probe = torch.optim.SGD([torch.zeros(1, requires_grad=True)], lr=self.lr,
-                                momentum=self.momentum, nesterov=True)
+                                momentum=self.momentum, nesterov=True,
+                                weight_decay=self.weight_decay)
         g = dict(probe.param_groups[0])
         g.pop('params')
         return g
 
     def state_dict(self):
-        """torch.optim.SGD(model.parameters(), lr, momentum, nesterov=True).state_dict():
+        """torch.optim.SGD(model.parameters(), lr, momentum, nesterov=True,
+        weight_decay).state_dict():
         per-parameter ``momentum_buffer`` (after the first step) in model.parameters()
         order and one param_group.  ``max_norm`` is train.py's --max-norm argument, not
         optimizer state, so it is not stored (as in the reference)."""
@@ -193,13 +208,15 @@ class FusedSGD:
             raise ValueError(f"param_group holds {len(g['params'])} parameters, the model has "
                              f"{len(order)}")
         if not g.get('nesterov', False) or g.get('dampening', 0) != 0 or \
-                g.get('weight_decay', 0) != 0 or g.get('maximize', False):
+                g.get('maximize', False) or not g.get('weight_decay', 0) >= 0:
             raise ValueError("FusedSGD implements SGD(momentum, nesterov=True, dampening=0, "
-                             "weight_decay=0) (train.py:146-149); the state_dict has "
+                             "weight_decay >= 0) (train.py:146-149); the state_dict has "
                              f"nesterov={g.get('nesterov')}, dampening={g.get('dampening')}, "
+                             f"maximize={g.get('maximize')}, "
                              f"weight_decay={g.get('weight_decay')}")
         self.lr = float(g['lr'])
         self.momentum = float(g['momentum'])
+        self.weight_decay = float(g.get('weight_decay', 0))
         self.buf.zero_()
         state = sd['state']
         for slot, idx in enumerate(g['params']):
@@ -218,6 +235,179 @@ class FusedSGD:
                                  f"{tuple(p.shape)}")
             self.buf[o:o + p.numel()].copy_(mb.reshape(-1).to(self.buf.device, torch.float32))
         self.steps = max(self.steps, 1 if state else 0)
+
+
+class FusedAdam:
+    """torch.optim.Adam(lr, betas, eps, weight_decay) + clip_grad_norm_ on flat buffers
+    (ds2_clip_adam; amsgrad, maximize and decoupled decay are not implemented).  The step
+    count lives on the device (``step_count``): a step skipped through ``skip_flag`` is not
+    counted, and nothing here reads it back except state_dict()."""
+
+    _STATE_KEYS = {'step', 'exp_avg', 'exp_avg_sq'}
+
+    def __init__(self, flat: FlatParams, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0.0, max_norm: float = 0.0):
+        self.flat = flat
+        self.lr = lr
+        self.betas = (float(betas[0]), float(betas[1]))
+        self.eps = eps
+        self.weight_decay = weight_decay
+        self.max_norm = max_norm
+        self._check_hyper()
+        dev = flat.flat.device
+        self.exp_avg = torch.zeros_like(flat.flat)
+        self.exp_avg_sq = torch.zeros_like(flat.flat)
+        self.step_count = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.norm = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.ws = torch.empty(max(16, _lib.size("ds2_optim_workspace_size", flat.numel)),
+                              dtype=torch.uint8, device=dev)
+
+    def _check_hyper(self):
+        # torch.optim.Adam's own checks
+        if not self.lr >= 0:
+            raise ValueError(f"Invalid learning rate: {self.lr}")
+        if not self.eps >= 0:
+            raise ValueError(f"Invalid epsilon value: {self.eps}")
+        for i, b in enumerate(self.betas):
+            if not 0.0 <= b < 1.0:
+                raise ValueError(f"Invalid beta parameter at index {i}: {b}")
+        if not self.weight_decay >= 0:
+            raise ValueError(f"Invalid weight_decay value: {self.weight_decay}")
+
+    def zero_grad(self):
+        self.flat.zero_grad()
+
+    def grad_norm(self) -> torch.Tensor:
+        """Global L2 norm of the gradients, on the device (no host sync)."""
+        self.flat.finalize_grads()
+        _lib.call("ds2_grad_norm", self.flat.grad.data_ptr(), self.flat.numel, self.norm.data_ptr(),
+                  self.ws.data_ptr(), self.ws.numel(), _stream())
+        return self.norm
+
+    def step(self, skip_flag: Optional[torch.Tensor] = None):
+        self.flat.finalize_grads()
+        norm_ptr = None
+        if self.max_norm > 0:
+            self.grad_norm()
+            norm_ptr = self.norm.data_ptr()
+        _lib.call("ds2_clip_adam", self.flat.flat.data_ptr(), self.flat.grad.data_ptr(),
+                  self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.flat.numel,
+                  float(self.lr), self.betas[0], self.betas[1], float(self.eps),
+                  float(self.weight_decay), float(self.max_norm), norm_ptr,
+                  self.step_count.data_ptr(), _p(skip_flag), _stream())
+
+    # ---- torch.optim.Adam's state_dict format (model.py:446 optim_dict; train.py:843) ----
+    def _model_order(self):
+        return [(p, self.flat.offset_of[id(p)]) for p in self.flat.model_params]
+
+    def _group_defaults(self):
+        # the installed torch's own Adam param_group keys, so the dict loads into
+        # torch.optim.Adam of this torch version unchanged
+        probe = torch.optim.Adam([torch.zeros(1, requires_grad=True)], lr=self.lr,
+                                 betas=self.betas, eps=self.eps, weight_decay=self.weight_decay)
+        g = dict(probe.param_groups[0])
+        g.pop('params')
+        return g
+
+    def state_dict(self):
+        """torch.optim.Adam(model.parameters(), lr, betas, eps, weight_decay).state_dict():
+        per parameter, in model.parameters() order, ``step`` (a float32 scalar tensor, the
+        same for all), ``exp_avg`` and ``exp_avg_sq``; empty before the first counted step.
+        Reads the device step count (a host sync: checkpoints and set_lr only)."""
+        order = self._model_order()
+        t = int(self.step_count.item())
+        state = {}
+        if t > 0:
+            for i, (p, o) in enumerate(order):
+                n = p.numel()
+                state[i] = {'step': torch.tensor(float(t), dtype=torch.float32),
+                            'exp_avg': self.exp_avg[o:o + n].detach().view_as(p).cpu().clone(),
+                            'exp_avg_sq': self.exp_avg_sq[o:o + n].detach().view_as(p).cpu()
+                            .clone()}
+        group = self._group_defaults()
+        group['params'] = list(range(len(order)))
+        return {'state': state, 'param_groups': [group]}
+
+    def load_state_dict(self, sd):
+        """Accepts torch.optim.Adam's format (a reference ``package['optim_dict']`` of an
+        ``--optimizer adam`` run).  Raises on anything else instead of guessing; nothing of
+        this optimizer changes unless the whole dict is accepted."""
+        if not isinstance(sd, dict) or set(sd) != {'state', 'param_groups'}:
+            raise ValueError("FusedAdam.load_state_dict expects a torch.optim.Adam state_dict "
+                             f"({{'state', 'param_groups'}}), got keys {sorted(sd) if isinstance(sd, dict) else type(sd)}")
+        groups = sd['param_groups']
+        order = self._model_order()
+        if len(groups) != 1:
+            raise ValueError(f"expected one param_group (model.parameters()), got {len(groups)}")
+        g = groups[0]
+        if 'betas' not in g or 'eps' not in g:
+            raise ValueError("not a torch.optim.Adam state_dict: the param_group has no "
+                             f"betas / eps (keys {sorted(g)})")
+        if len(g['params']) != len(order):
+            raise ValueError(f"param_group holds {len(g['params'])} parameters, the model has "
+                             f"{len(order)}")
+        if g.get('amsgrad', False) or g.get('maximize', False) or \
+                g.get('decoupled_weight_decay', False):
+            raise ValueError("FusedAdam implements Adam(amsgrad=False, maximize=False, "
+                             "decoupled_weight_decay=False) (train.py:150-152); the state_dict "
+                             f"has amsgrad={g.get('amsgrad')}, maximize={g.get('maximize')}, "
+                             f"decoupled_weight_decay={g.get('decoupled_weight_decay')}")
+        state = sd['state']
+        have = [idx for idx in g['params'] if state.get(idx)]
+        if have and len(have) != len(order):
+            raise ValueError(f"state for {len(have)} of {len(order)} parameters: Adam keeps "
+                             "either none (no step taken) or all")
+        steps, moments = set(), []
+        for slot, idx in enumerate(g['params']):
+            st = state.get(idx)
+            if not st:
+                continue
+            if set(st) != self._STATE_KEYS:
+                raise ValueError(f"param {idx}: Adam state keys {sorted(self._STATE_KEYS)} "
+                                 f"expected, got {sorted(st)}")
+            p, o = order[slot]
+            for key in ('exp_avg', 'exp_avg_sq'):
+                if tuple(st[key].shape) != tuple(p.shape):
+                    raise ValueError(f"{key} {idx}: shape {tuple(st[key].shape)} != parameter "
+                                     f"{tuple(p.shape)}")
+            t = float(st['step'])
+            if t != int(t) or t < 0:
+                raise ValueError(f"param {idx}: step {t} is not a step count")
+            steps.add(int(t))
+            moments.append((o, p.numel(), st['exp_avg'], st['exp_avg_sq']))
+        if len(steps) > 1:
+            raise ValueError(f"per-parameter step counts differ ({sorted(steps)}): one fused "
+                             "update keeps one count")
+        old = (self.lr, self.betas, self.eps, self.weight_decay)
+        self.lr = float(g['lr'])
+        self.betas = (float(g['betas'][0]), float(g['betas'][1]))
+        self.eps = float(g['eps'])
+        self.weight_decay = float(g.get('weight_decay', 0))
+        try:
+            self._check_hyper()
+        except ValueError:
+            self.lr, self.betas, self.eps, self.weight_decay = old
+            raise
+        self.exp_avg.zero_()
+        self.exp_avg_sq.zero_()
+        for o, n, m, v in moments:
+            self.exp_avg[o:o + n].copy_(m.reshape(-1).to(self.exp_avg.device, torch.float32))
+            self.exp_avg_sq[o:o + n].copy_(v.reshape(-1).to(self.exp_avg.device, torch.float32))
+        self.step_count.fill_(steps.pop() if steps else 0)
+
+
+def build_optimizer(args, flat: FlatParams, max_norm: float = 0.0):
+    """train.py:139-152 on flat buffers: ``args.optimizer`` 'sgd' -> SGD(lr, momentum,
+    nesterov=True, weight_decay), 'adam' -> Adam(lr) with torch's defaults for the rest (the
+    reference passes it nothing else).  ``max_norm`` is train.py's --max-norm, which the fused
+    step applies.  Any other name raises (the reference returns None and fails later)."""
+    name = getattr(args, 'optimizer', 'sgd')
+    if name == 'sgd':
+        return FusedSGD(flat, lr=args.lr, momentum=args.momentum, max_norm=max_norm,
+                        weight_decay=getattr(args, 'weight_decay', 0.0))
+    if name == 'adam':
+        return FusedAdam(flat, lr=args.lr, max_norm=max_norm)
+    raise ValueError(f"unknown optimizer {name!r}: 'sgd' or 'adam' (train.py:145-152)")
 
 
 class ParamBroadcaster:

@@ -7,7 +7,8 @@ per-batch CER/WER of train.py:575-587 on the device), the NaN work-around of
 train.py:595-598 (NaN logits zeroed in place, their gradient zero, the step always
 taken -- the reference's skip check at :625 can never fire after :598), CTC / N,
 zero_grad, backward with the bucketed gradient all-reduce overlapped,
-clip_grad_norm_(max_norm) and SGD-Nesterov as one device-resident pass.
+clip_grad_norm_(max_norm) and the update of build_optimizer's choice (train.py:139-152:
+SGD-Nesterov with optional weight decay, or Adam) as one device-resident pass.
 
 No host synchronisation per step: the reference's two warnings (NaN logits, inf loss)
 and the persistent recurrences' hand-off status (ds2hip.h err_out) travel to the host
@@ -28,7 +29,8 @@ from . import _lib, ops
 from .ctc import CTCLoss
 from .decoder import GreedyDecoder
 from .ops import _stream
-from .optim import FlatParams, FusedSGD, GradAllReducer, ParamBroadcaster, RcclComm
+from .optim import (FlatParams, FusedAdam, FusedSGD, GradAllReducer, ParamBroadcaster, RcclComm,
+                    build_optimizer)  # noqa: F401  (build_optimizer: train.py:139-152)
 
 
 def reduce_tensor(tensor, world_size):
@@ -98,7 +100,10 @@ class Trainer:
 
     def __init__(self, model, labels, lr=3e-4, momentum=0.9, max_norm=100.0, device=None,
                  bucket_mb=40.0, decode=True, score=False, group=None, broadcast_buffers=True,
-                 verbose=True):
+                 verbose=True, optimizer='sgd', weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8):
+        """optimizer: 'sgd' (SGD-Nesterov with ``momentum`` and ``weight_decay``, train.py's
+        default) or 'adam' (``betas``, ``eps``, ``weight_decay``; the reference's
+        ``--optimizer adam`` is Adam(lr) with these defaults)."""
         self.device = torch.device(device) if device is not None else torch.device('cuda')
         self.model = model.to(self.device)
         self.model.train()
@@ -110,7 +115,14 @@ class Trainer:
         # bucket (GradAllReducer.set_status_packer) instead of two collectives of their own
         self.flat = FlatParams(list(self.model.parameters()), self.device, adjacent=pairs,
                                tail=2 if dist.is_initialized() else 0)
-        self.optimizer = FusedSGD(self.flat, lr=lr, momentum=momentum, max_norm=max_norm)
+        if optimizer == 'sgd':
+            self.optimizer = FusedSGD(self.flat, lr=lr, momentum=momentum, max_norm=max_norm,
+                                      weight_decay=weight_decay)
+        elif optimizer == 'adam':
+            self.optimizer = FusedAdam(self.flat, lr=lr, betas=betas, eps=eps,
+                                       weight_decay=weight_decay, max_norm=max_norm)
+        else:
+            raise ValueError(f"unknown optimizer {optimizer!r}: 'sgd' or 'adam'")
         # DS2_ALLREDUCE=ds2: the buckets go through the library's own RCCL communicator
         # (ds2_comm_init / ds2_allreduce_bucket) instead of torch.distributed's
         comm = None
@@ -277,10 +289,11 @@ class Trainer:
         self._step_loss = loss.detach().reshape(1)
         loss.backward()
         self.reducer.finish()
-        # clip + SGD; always taken for NaN data (see module docstring).  Skipped on the device
+        # clip + update; always taken for NaN data (see module docstring).  Skipped on the device
         # when a persistent recurrence reported a hand-off failure this step: its outputs are
         # NaN and the update would write NaN into every parameter and momentum slot before the
-        # host sees the error (the word is 0 in a normal step; no host sync).  With a process
+        # host sees the error (the word is 0 in a normal step; no host sync; Adam's device step
+        # count does not advance either).  With a process
         # group the decision is global: the status word rode in the last gradient bucket's
         # tail, summed over the ranks (the failing rank's NaN gradients are already in every
         # rank's buckets, so all ranks skip and all raise), and so did the loss (reduce_tensor,

@@ -513,6 +513,25 @@ ds2_status_t ds2_clip_sgd_nesterov(float* params, const float* grads, float* mom
                                    int64_t numel, float lr, float momentum, float max_norm,
                                    const float* norm, const int* skip_flag,
                                    ds2_stream_t stream);
+/* The same with torch.optim.SGD's weight_decay: the update runs on
+ * g' = g*coef + weight_decay*p (clipping scales .grad before step() adds the decay). */
+ds2_status_t ds2_clip_sgd_nesterov_wd(float* params, const float* grads, float* momentum_buf,
+                                      int64_t numel, float lr, float momentum,
+                                      float weight_decay, float max_norm, const float* norm,
+                                      const int* skip_flag, ds2_stream_t stream);
+/* clip_grad_norm_(max_norm) then torch.optim.Adam (amsgrad, maximize and decoupled decay
+ * off; ref train.py:150-152) in one pass over flat fp32 buffers.  With t = *step + 1:
+ *   g' = g*coef (+ weight_decay*p);  m += (1-beta1)(g'-m);  v = beta2 v + (1-beta2) g'^2;
+ *   p -= lr/(1-beta1^t) * m / (sqrt(v)/sqrt(1-beta2^t) + eps)
+ * The hyper-parameters are doubles, as torch holds them: 1-beta, the bias corrections and
+ * lr/(1-beta1^t) are formed in double and rounded to float once.  step is a device word,
+ * the count of steps taken: read by the update and advanced by a one-thread kernel behind
+ * it on the same stream (no host sync, no race).  A skipped step (skip_flag as above)
+ * leaves params, both moments and *step unchanged.                                  */
+ds2_status_t ds2_clip_adam(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
+                           int64_t numel, double lr, double beta1, double beta2, double eps,
+                           double weight_decay, float max_norm, const float* norm, int* step,
+                           const int* skip_flag, ds2_stream_t stream);
 /* *flag = 1 if any x is NaN (flag must be zeroed by the caller first);
  * if zero_nans, NaNs are replaced by 0 in place (train.py:595-598); mask
  * (nullable, one byte per element) records where the NaNs were.              */

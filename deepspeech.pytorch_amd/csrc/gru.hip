@@ -21,6 +21,7 @@
 #include "rnn_common.h"
 
 #include <algorithm>
+#include <mutex>
 
 namespace ds2 {
 
@@ -1079,13 +1080,18 @@ size_t gru_xl_ctr_words();
 bool launch_gru_fwd_xl(int t_max, int n, int h, int num_dirs, const float* xproj,
                        const float* w_hh_f, const float* w_hh_r, const float* b_hh_f,
                        const float* b_hh_r, const int* lens, float* h_all, float* gates,
-                       float* ring, unsigned* xl, unsigned* err, unsigned long long* stamps,
-                       size_t lds_pad, hipStream_t st);
+                       float* ring, unsigned* ctrs, size_t ctr_bytes, unsigned* xl, unsigned* err,
+                       unsigned* err_out, unsigned long long* stamps, size_t lds_pad,
+                       hipStream_t st);
 bool launch_gru_bwd_xl(int t_max, int n, int h, int num_dirs, const float* dy, int dy_dirs,
                        const float* w_hh_f, const float* w_hh_r, const float* h_all,
                        const float* gates, const int* lens, float* dgates_x, float* dgates_h,
-                       float* ring, unsigned* xl, unsigned* err, unsigned long long* stamps,
-                       double* dbp, size_t lds_pad, hipStream_t st, unsigned* camax);
+                       float* ring, unsigned* ctrs, size_t ctr_bytes, unsigned* xl, unsigned* err,
+                       unsigned* err_out, unsigned long long* stamps, double* dbp, size_t lds_pad,
+                       hipStream_t st, unsigned* camax, float* rowp);
+size_t gru_xl_rowp_bytes(int t_max, int n, int h, int num_dirs);
+void launch_gru_xl_row_amax(int t_max, int n, int h, int num_dirs, const float* rowp,
+                            unsigned* out, hipStream_t st);
 }  // namespace ds2
 
 using namespace ds2;
@@ -1199,21 +1205,22 @@ ds2_status_t ds2_gru_fwd(int t_max, int n, int h, int num_dirs, const float* xpr
       static_cast<char*>(ws) + align256((size_t)num_dirs * UB * KS * 3 * 64 * sizeof(float)));
   unsigned* err = ctrs + num_dirs * BT;
   if (persistent && (h % GU) == 0 && UB <= 8 * GW) {
-    if (hipMemsetAsync(ctrs, 0, counter_bytes(n, num_dirs), st) != hipSuccess)
-      return launch_status("ds2_gru counters");
     int T_ = t_max, N_ = n, H_ = h, D_ = num_dirs, UB_ = UB, BT_ = BT;
     unsigned long long* stamps = stamp_mode() == 2 ? stamp_slots(ctrs, n, num_dirs) : nullptr;
     float* ring = reinterpret_cast<float*>(reinterpret_cast<char*>(ctrs) +
                                            align256(counter_bytes(n, num_dirs)));
     void* args[] = {&T_, &N_, &H_, &D_, &UB_, &BT_, &xproj, &w_hh_f, &w_hh_r, &b_hh_f,
                     &b_hh_r, &lens, &h_all, &gates, &ring, &ctrs, &err, &stamps};
-    if (ring_reset(ring, n, h, num_dirs, st) != hipSuccess) return launch_status("ds2_gru ring");
+    // the XCD-local launch prepares the counters and its part of the ring itself and reports
+    // into err_out from the kernel: no fills and no fold launch around it
     if (launch_gru_fwd_xl(t_max, n, h, num_dirs, xproj, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lens,
-                          h_all, gates, ring, err + 1, err, stamps, kDopPadLds, st)) {
-      fold_err(err, err_out, st);
+                          h_all, gates, ring, ctrs, counter_bytes(n, num_dirs), err + 1, err,
+                          err_out, stamps, kDopPadLds, st))
       return launch_status("ds2_gru_fwd");
-    }
     (void)hipGetLastError();
+    if (hipMemsetAsync(ctrs, 0, counter_bytes(n, num_dirs), st) != hipSuccess)
+      return launch_status("ds2_gru counters");
+    if (ring_reset(ring, n, h, num_dirs, st) != hipSuccess) return launch_status("ds2_gru ring");
     if (launch_gru_fwd_x6(t_max, n, h, num_dirs, xproj, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lens,
                           h_all, gates, ring, ctrs, err, stamps, kDopPadLds, st)) {
       fold_err(err, err_out, st);
@@ -1290,6 +1297,48 @@ size_t ds2_gru_bwd_workspace_size(int n, int h, int num_dirs) {
   return gru_bwd_ws_base(n, h, num_dirs) + gru_db_bytes(n, h, num_dirs);
 }
 
+size_t ds2_gru_row_amax_workspace_size(int t_max, int n, int h, int num_dirs) {
+  if (t_max < 0 || n < 0 || h < 1 || (num_dirs != 1 && num_dirs != 2)) return 0;
+  return ds2_gru_bwd_workspace_size(n, h, num_dirs) +
+         align256(gru_xl_rowp_bytes(t_max, n, h, num_dirs));
+}
+
+// Which workspace holds valid row-maximum partials, and of which call: set when the XCD-local
+// backward ran with them, cleared by every other backward on that workspace.  One record: a
+// second thread's call in between only sends ds2_gru_row_amax to its fall-back status.
+struct RowRec {
+  const void* ws;
+  int t, n, h, d;
+};
+static std::mutex g_row_mu;
+static RowRec g_row_rec = {nullptr, 0, 0, 0, 0};
+static void row_rec_clear(const void* ws) {
+  std::lock_guard<std::mutex> lk(g_row_mu);
+  if (g_row_rec.ws == ws) g_row_rec.ws = nullptr;
+}
+static void row_rec_set(const void* ws, int t, int n, int h, int d) {
+  std::lock_guard<std::mutex> lk(g_row_mu);
+  g_row_rec = RowRec{ws, t, n, h, d};
+}
+
+ds2_status_t ds2_gru_row_amax(int t_max, int n, int h, int num_dirs, const void* ws,
+                                  size_t ws_bytes, unsigned* row_amax, ds2_stream_t stream) {
+  if (t_max < 0 || n < 0 || h < 1 || (num_dirs != 1 && num_dirs != 2)) return DS2_INVALID_VALUE;
+  if (t_max == 0 || n == 0) return DS2_OK;
+  if (ws == nullptr || row_amax == nullptr) return DS2_INVALID_VALUE;
+  {
+    std::lock_guard<std::mutex> lk(g_row_mu);
+    const RowRec r = g_row_rec;
+    if (r.ws != ws || r.t != t_max || r.n != n || r.h != h || r.d != num_dirs ||
+        ws_bytes < ds2_gru_row_amax_workspace_size(t_max, n, h, num_dirs))
+      return DS2_UNSUPPORTED_SHAPE;
+  }
+  const float* rowp = reinterpret_cast<const float*>(static_cast<const char*>(ws) +
+                                                     ds2_gru_bwd_workspace_size(n, h, num_dirs));
+  launch_gru_xl_row_amax(t_max, n, h, num_dirs, rowp, row_amax, as_stream(stream));
+  return launch_status("ds2_gru_row_amax");
+}
+
 #define DS2_BWD_CASE(K)                                                                     \
   case K:                                                                                   \
     hipLaunchKernelGGL(gru_bwd_step_kernel<K>, dim3(grid), dim3(GT), 0, st, s, t_max, n, h,  \
@@ -1332,7 +1381,7 @@ static ds2_status_t gru_bwd_run(int t_max, int n, int h, int num_dirs, const flo
                                 const float* gates, const int* lens, float* dgates_x,
                                 float* dgates_h, unsigned* err_out, void* ws, hipStream_t st,
                                 double* dbp, bool& summed, unsigned* camax, bool& camax_done,
-                                int& db_tiles);
+                                int& db_tiles, float* rowp, bool& rowp_done);
 
 static ds2_status_t gru_bwd_bias_impl(int t_max, int n, int h, int num_dirs, const float* dy,
                                       int dy_dirs, const float* w_hh_f, const float* w_hh_r,
@@ -1384,9 +1433,10 @@ static ds2_status_t gru_bwd_bias_impl(int t_max, int n, int h, int num_dirs, con
   hipStream_t st = as_stream(stream);
   double* dbp = reinterpret_cast<double*>(static_cast<char*>(ws) + gru_bwd_ws_base(n, h, num_dirs));
   const size_t camax_bytes = (size_t)2 * num_dirs * 3 * h * sizeof(unsigned);
-  if (camax != nullptr && hipMemsetAsync(camax, 0, camax_bytes, st) != hipSuccess)
-    return launch_status("ds2_gru_bwd_bias_amax");
+  row_rec_clear(ws);
   if (t_max == 0 || n == 0) {
+    if (camax != nullptr && hipMemsetAsync(camax, 0, camax_bytes, st) != hipSuccess)
+      return launch_status("ds2_gru_bwd_bias_amax");
     if (!want_db) return DS2_OK;
     // no rows: zero bias gradients
     if (hipMemsetAsync(dbp, 0, gru_db_bytes(n > 0 ? n : 1, h, num_dirs), st) != hipSuccess)
@@ -1395,12 +1445,20 @@ static ds2_status_t gru_bwd_bias_impl(int t_max, int n, int h, int num_dirs, con
                        dbp, 1, num_dirs, h, db_ih_f, db_hh_f, db_ih_r, db_hh_r);
     return launch_status("ds2_gru_bwd_bias");
   }
-  bool summed = false, camax_done = false;
+  bool summed = false, camax_done = false, rowp_done = false;
   int db_tiles = (n + GB - 1) / GB;
+  // the row-maximum partials of dgates_x (ds2_gru_row_amax): behind the plain workspace,
+  // kept only when the caller sized it with ds2_gru_row_amax_workspace_size
+  float* rowp = nullptr;
+  if (camax != nullptr && ws_bytes >= ds2_gru_row_amax_workspace_size(t_max, n, h, num_dirs))
+    rowp = reinterpret_cast<float*>(static_cast<char*>(ws) +
+                                    ds2_gru_bwd_workspace_size(n, h, num_dirs));
   const ds2_status_t rc = gru_bwd_run(t_max, n, h, num_dirs, dy, dy_dirs, w_hh_f, w_hh_r, h_all,
                                       gates, lens, dgates_x, dgates_h, err_out, ws, st,
-                                      want_db ? dbp : nullptr, summed, camax, camax_done, db_tiles);
+                                      want_db ? dbp : nullptr, summed, camax, camax_done, db_tiles,
+                                      rowp, rowp_done);
   if (rc != DS2_OK) return rc;
+  if (rowp_done) row_rec_set(ws, t_max, n, h, num_dirs);
   if (camax != nullptr && !camax_done) {
     // a kernel without the fused maxima ran: one column pass over each of dgx, dgh
     const ds2_status_t ra = ds2_amax(dgates_x, t_max * n, num_dirs * 3 * h, num_dirs * 3 * h,
@@ -1427,7 +1485,7 @@ static ds2_status_t gru_bwd_run(int t_max, int n, int h, int num_dirs, const flo
                                 const float* gates, const int* lens, float* dgates_x,
                                 float* dgates_h, unsigned* err_out, void* ws, hipStream_t st,
                                 double* dbp, bool& summed, unsigned* camax, bool& camax_done,
-                                int& db_tiles) {
+                                int& db_tiles, float* rowp, bool& rowp_done) {
   if (num_dirs == 1) w_hh_r = w_hh_f;
   apply_spin_limit_env();
   apply_rnn_tune_env();
@@ -1446,7 +1504,28 @@ static ds2_status_t gru_bwd_run(int t_max, int n, int h, int num_dirs, const flo
   unsigned* ctrs = reinterpret_cast<unsigned*>(
       reinterpret_cast<char*>(dhs) + align256((size_t)2 * n * num_dirs * h * sizeof(float)));
   unsigned* err = ctrs + num_dirs * BT;
-  if (persistent && (h % GU) == 0 && UB <= 8 * GW) {
+  const size_t camax_bytes = (size_t)2 * num_dirs * 3 * h * sizeof(unsigned);
+  const bool dop = persistent && (h % GU) == 0 && UB <= 8 * GW;
+  if (dop) {
+    // the XCD-local launch zeroes the counters and camax itself and reports into err_out from
+    // the kernel: no fills and no fold launch around it
+    unsigned long long* stamps = stamp_mode() == 2 ? stamp_slots(ctrs, n, num_dirs) : nullptr;
+    float* ring = reinterpret_cast<float*>(reinterpret_cast<char*>(ctrs) +
+                                           align256(counter_bytes(n, num_dirs)));
+    if (launch_gru_bwd_xl(t_max, n, h, num_dirs, dy, dy_dirs, w_hh_f, w_hh_r, h_all, gates,
+                          lens, dgates_x, dgates_h, ring, ctrs, counter_bytes(n, num_dirs),
+                          err + 1, err, err_out, stamps, dbp, kDopPadLds, st, camax, rowp)) {
+      summed = dbp != nullptr;
+      camax_done = camax != nullptr;
+      rowp_done = rowp != nullptr;
+      db_tiles = (n + 7) / 8;
+      return launch_status("ds2_gru_bwd");
+    }
+    (void)hipGetLastError();
+  }
+  if (camax != nullptr && hipMemsetAsync(camax, 0, camax_bytes, st) != hipSuccess)
+    return launch_status("ds2_gru_bwd_bias_amax");
+  if (dop) {
     if (hipMemsetAsync(ctrs, 0, counter_bytes(n, num_dirs), st) != hipSuccess)
       return launch_status("ds2_gru counters");
     int T_ = t_max, N_ = n, H_ = h, D_ = num_dirs, UB_ = UB, BT_ = BT, DYD_ = dy_dirs;
@@ -1455,16 +1534,6 @@ static ds2_status_t gru_bwd_run(int t_max, int n, int h, int num_dirs, const flo
                                            align256(counter_bytes(n, num_dirs)));
     void* args[] = {&T_, &N_, &H_, &D_, &UB_, &BT_, &dy, &DYD_, &w_hh_f, &w_hh_r, &h_all,
                     &gates, &lens, &dgates_x, &dgates_h, &ring, &ctrs, &err, &stamps, &dbp};
-    if (launch_gru_bwd_xl(t_max, n, h, num_dirs, dy, dy_dirs, w_hh_f, w_hh_r, h_all, gates,
-                          lens, dgates_x, dgates_h, ring, err + 1, err, stamps, dbp, kDopPadLds,
-                          st, camax)) {
-      fold_err(err, err_out, st);
-      summed = dbp != nullptr;
-      camax_done = camax != nullptr;
-      db_tiles = (n + 7) / 8;
-      return launch_status("ds2_gru_bwd");
-    }
-    (void)hipGetLastError();
     if (launch_gru_bwd_x6(t_max, n, h, num_dirs, dy, dy_dirs, w_hh_f, w_hh_r, h_all, gates,
                           lens, dgates_x, dgates_h, ring, ctrs, err, stamps, dbp, kDopPadLds, st,
                           camax, &camax_done)) {

@@ -33,8 +33,11 @@
 // Forward hand-off: the sentinel ring of gru_fwd_x6_kernel (4 slots, the data is the flag),
 // tiles consumed in a fixed producer order (a wave multiplies tile p only after tile p - 1:
 // deterministic sums).  Backward: per-producer flags (the record after a drain, then the
-// flag), records multiplied in a fixed order, two in flight per wave.
+// flag), each wave waiting for the flags of its own producers only; records multiplied in a
+// fixed order, three in flight per wave beside the one multiplied.
 #include "rnn_common.h"
+
+#include <algorithm>
 
 namespace ds2 {
 
@@ -70,7 +73,8 @@ __device__ __forceinline__ bool xl_map(int G, int UBX, int& g, int& ub) {
 // the same table).  A timeout sets the error word and answers false.  `mode` (diagnostic, read
 // by scripts/trace_gru.py): OR of 1 (a member ran LOCAL) / 2 (GLOBAL) per group.
 __device__ __forceinline__ bool xl_group_local(unsigned* xtab, int ub, int UBX, unsigned* err,
-                                               int* lds_word, unsigned* mode, int force_global) {
+                                               unsigned* err_out, int* lds_word, unsigned* mode,
+                                               int force_global) {
   const unsigned mine = xcc_id() + 1u;
   if (threadIdx.x == 0) __hip_atomic_store(xtab + ub, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if ((threadIdx.x >> 6) == 0) {
@@ -82,7 +86,7 @@ __device__ __forceinline__ bool xl_group_local(unsigned* xtab, int ub, int UBX, 
                      : mine;
       if (__ballot(v == 0u) == 0ull) break;
       if (spins > g_spin_limit) {
-        if (lane == 0) __hip_atomic_fetch_or(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (lane == 0) raise_err(err, err_out);
         ok = false;
         break;
       }
@@ -105,6 +109,51 @@ __device__ __forceinline__ void xl_store(u32x4 v, __amdgpu_buffer_rsrc_t rs, int
     __builtin_amdgcn_raw_buffer_store_b128(v, rs, off, 0, kSc1);
 }
 
+// max of v over the lane's half of the wave (lanes 0-31 / 32-63: one sample's 32 units), in
+// every lane: four DPP steps inside each row of 16 (quad swaps, half-row and row mirrors),
+// then the two rows of a half joined through readlane -- no LDS-crossbar shuffles (five
+// dependent ds_bpermute, ~0.15 us, where this is ~40 cycles).  A maximum: the order is free.
+#define DS2_DPP_MAX(v, ctrl)                                                               \
+  v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(                      \
+                   0, __builtin_bit_cast(int, v), ctrl, 0xf, 0xf, true)))
+__device__ __forceinline__ float half_wave_max(float v) {
+  DS2_DPP_MAX(v, 0xB1);    // quad_perm [1, 0, 3, 2]
+  DS2_DPP_MAX(v, 0x4E);    // quad_perm [2, 3, 0, 1]
+  DS2_DPP_MAX(v, 0x141);   // row_half_mirror
+  DS2_DPP_MAX(v, 0x140);   // row_mirror
+  const int b = __builtin_bit_cast(int, v);
+  const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 0));
+  const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 16));
+  const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32));
+  const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48));
+  return (threadIdx.x & 32) ? fmaxf(r2, r3) : fmaxf(r0, r1);
+}
+#undef DS2_DPP_MAX
+
+// The backward's per-wave flag wait: lane l polls the flag of the wave's producer l (`flags` =
+// the group's flag line at the wave's first producer) until all `count` have reached `target`.
+// The wave then loads those producers' records itself (MI355X_MICROARCH "Valid forms" row 1:
+// the wave that polled loads after its own poll matched), without waiting for the group's
+// other producers or for a workgroup barrier.  False, and the error words set, past the spin
+// bound (DS2_RNN_SPIN_LIMIT=0: at once).
+__device__ __forceinline__ bool xl_wave_flags_wait(const unsigned* flags, int count,
+                                                   unsigned target, unsigned* err,
+                                                   unsigned* err_out) {
+  const int lane = threadIdx.x & 63;
+  if (count == 0) return true;
+  for (unsigned spins = 0;; ++spins) {
+    if (spins > g_spin_limit || g_spin_limit == 0) {
+      if (lane == 0) raise_err(err, err_out);
+      return false;
+    }
+    const unsigned v = lane < count ? __hip_atomic_load(flags + lane, __ATOMIC_RELAXED,
+                                                        __HIP_MEMORY_SCOPE_AGENT)
+                                    : target;
+    if (__ballot(v < target) == 0ull) return true;
+    sleep_units(g_rnn_tune[3]);
+  }
+}
+
 // the stacked fp16 (hi; lo) A-fragment slots of value (row m < 8, k) in a 1-KB fragment:
 // lane (k >> 3) * 16 + m (hi) / + m + 8 (lo), slot k & 7
 __device__ __forceinline__ int xl_frag_hi(int m, int k) { return (((k >> 3) << 4) + m) * 8 + (k & 7); }
@@ -120,7 +169,8 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     const float* __restrict__ w_f, const float* __restrict__ w_r, const float* __restrict__ b_f,
     const float* __restrict__ b_r, const int* __restrict__ lens, float* __restrict__ h_all,
     float* __restrict__ gates, float* __restrict__ ring, unsigned* __restrict__ xl,
-    unsigned* __restrict__ err, unsigned long long* __restrict__ stamps, int force_global) {
+    unsigned* __restrict__ err, unsigned* __restrict__ err_out,
+    unsigned long long* __restrict__ stamps, int force_global) {
   constexpr int NCT = 6;
   constexpr int RC = 3 * LU + 1;   // reduction row pitch
   __shared__ float red[LW * 16 * RC];
@@ -145,7 +195,8 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
   const int p0 = wave * (UBX / LW) + min(wave, UBX % LW);
   const int np = UBX / LW + (wave < UBX % LW ? 1 : 0);   // host guarantees np <= NPW + 1
   if (threadIdx.x == 0) failed = 0;
-  const bool local = xl_group_local(xl + g * 32, ub, UBX, err, &sh_local, xl + 512 + g, force_global);
+  const bool local =
+      xl_group_local(xl + g * 32, ub, UBX, err, err_out, &sh_local, xl + 512 + g, force_global);
   const int slot_floats = G * UBX * 256;
   const __amdgpu_buffer_rsrc_t x_rs =
       __builtin_amdgcn_make_buffer_rsrc(ring, (short)0, LSLOTS * slot_floats * 4, 0x00020000);
@@ -344,7 +395,7 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
                !kAblWait && (!wave_ready(__builtin_bit_cast(f32x4, hv[p])) || g_spin_limit == 0);
                ++spins) {
             if (spins > g_spin_limit || g_spin_limit == 0) {
-              if (lane == 0) __hip_atomic_fetch_or(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              if (lane == 0) raise_err(err, err_out);
               failed = 1;
               bad = true;
               break;
@@ -444,15 +495,17 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 // added to the wave's partial in producer order.
 // Per-producer flags: the records as their own flags (the forward's sentinel ring over 3.1-KB
 // records, no drain and no flag) measured 5.3-5.5 vs 3.8 us per step and was removed.
-template <int NPW>
+// ROWS: the instantiation that also keeps the row maxima of dgx (rowp)
+template <int NPW, bool ROWS>
 __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void gru_bwd_xl_kernel(
     int T, int N, int H, int D, int UBX, int BTX, const float* __restrict__ dy, int dyd,
     const float* __restrict__ w_f, const float* __restrict__ w_r,
     const float* __restrict__ h_all, const float* __restrict__ gates,
     const int* __restrict__ lens, float* __restrict__ dgx, float* __restrict__ dgh,
     float* __restrict__ ring, unsigned* __restrict__ xl, unsigned* __restrict__ err,
-    unsigned long long* __restrict__ stamps, double* __restrict__ dbp,
-    unsigned* __restrict__ camax, int force_global) {
+    unsigned* __restrict__ err_out, unsigned long long* __restrict__ stamps,
+    double* __restrict__ dbp, unsigned* __restrict__ camax, float* __restrict__ rowp,
+    int force_global) {
   constexpr int RC = LU + 1;
   constexpr int LWP = 3;     // records in flight per wave beside the one multiplied
   __shared__ __attribute__((aligned(8))) float red[LW * 16 * RC > 4 * LB * LU * 2 ? LW * 16 * RC : 4 * LB * LU * 2];
@@ -464,6 +517,7 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
   __shared__ int slen[LB];
   __shared__ int sh_local;
   __shared__ int flag;
+  __shared__ float rowmx[2 * LB];   // dgx row maxima of the last two steps (rowp)
   // W_hh^T fragments of a wave's last producer when it has NPW + 1 (as the forward's)
   __shared__ u32x4 wx[LW * 6 * 2 * 64];
   const int G = D * BTX;
@@ -477,11 +531,13 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
   const int p0 = wave * (UBX / LW) + min(wave, UBX % LW);
   const int np = UBX / LW + (wave < UBX % LW ? 1 : 0);   // host guarantees np <= NPW + 1
   const int H3 = 3 * H;
+  if (threadIdx.x == 0) flag = 1;
   const int slot_floats = G * UBX * LRB;
   const __amdgpu_buffer_rsrc_t x_rs =
       __builtin_amdgcn_make_buffer_rsrc(ring, (short)0, 2 * slot_floats * 4, 0x00020000);
   const int grp_off = g * UBX * LRB;
-  const bool local = xl_group_local(xl + g * 32, ub, UBX, err, &sh_local, xl + 512 + g, force_global);
+  const bool local =
+      xl_group_local(xl + g * 32, ub, UBX, err, err_out, &sh_local, xl + 512 + g, force_global);
   unsigned* flags = xl + 256 + g * 32;
   const __amdgpu_buffer_rsrc_t f_rs =
       __builtin_amdgcn_make_buffer_rsrc(xl + 256, (short)0, 8 * 32 * 4, 0x00020000);
@@ -583,8 +639,9 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
   const int len = slen[m];
   const int shi = xl_frag_hi(m, u), slo = shi + 64;
   // The step's HBM traffic through LDS, issued by waves 1-3 only (as in the forward): wave 0
-  // polls the flags and publishes, and neither its poll nor its drain may queue behind HBM
-  // loads or stores (vmcnt counts in order).  Inputs one step ahead, loaded after the wave's
+  // publishes, and its drain may not queue behind HBM loads or stores (vmcnt counts in order).
+  // Every wave polls the flags of its own producers; an io wave's poll comes after it staged
+  // the inputs it loaded a step earlier, so nothing of its own is in flight in front of it.  Inputs one step ahead, loaded after the wave's
   // record loop; the gradients of step s stored during step s + 1.  io float4 idx = q + 192 k:
   // sample idx / 48, field (idx % 48) / 8, units 4 (idx % 8).
   // Addresses set up once (as the forward's): a fixed row pointer per io float4, advanced by
@@ -649,6 +706,20 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     store_one(tt, sl0);
     store_one(tt, sl1);
   };
+  // rowp [T N][D][UBX]: the workgroup's max |dgx| per sample row of every step (the dX GEMM's
+  // row scales without a pass over dgx).  Reduced and parked in rowmx after the publish, in
+  // the slack before the next step's wait; stored two steps later by the first 8 lanes of
+  // wave 1 beside store_out (the reduction barrier of the step in between orders the two).
+  // (32-bit element offsets, as the other outputs: rowp is smaller than dgx)
+  const int rpo = ROWS && wave == 1 && lane < LB && bt * LB + lane < N
+                      ? ((bt * LB + lane) * D + d) * UBX + ub
+                      : -1;
+  const int rpstr = N * D * UBX;
+  auto store_rmx = [&](int st) __attribute__((always_inline)) {
+    if (!ROWS || wave != 1) return;
+    const int tt = d == 0 ? T - 1 - st : st;
+    if (rpo >= 0) rowp[rpo + tt * rpstr] = rowmx[(st & 1) * LB + lane];
+  };
   // one step ahead (as the forward's)
   f32x4 xin0 = io ? load_in(0, sl0) : z4v, xin1 = io ? load_in(0, sl1) : z4v;
   float dh_prev = 0.f, z_prev = 0.f;
@@ -665,21 +736,22 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
       xin1 = load_in(st + 1, sl1);
     }
     if (!kAblStores && st > 0) store_out(st - 1);
+    if (!kAblStores && st > 1) store_rmx(st - 2);
   };
   for (int s = 0; s < T; ++s) {
     const int t = d == 0 ? T - 1 - s : s;
     f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
     trace_at(s, 0);
-    if (io) {   // the step's inputs (loaded during the last step; waited for beside the poll)
+    if (io) {   // the step's inputs (loaded during the last step), before the wave's poll
       stage_in(xin0, sl0, s);
       stage_in(xin1, sl1, s);
     }
     if (s == 0) io_issue(0);
     if (s > 0) {
-      if (!kAblWait && !flags_wait(flags, UBX, (unsigned)s, err, &flag)) {
-        poison_rest(dgx, s, T, d == 0, N, D, n, d, H, j, H3, 3, owner);
-        return;
-      }
+      // a wave whose wait timed out clears `flag`; the workgroup leaves at the reduction barrier
+      if (!kAblWait && !xl_wave_flags_wait(flags + p0, np, (unsigned)s, err, err_out) && lane == 0)
+        flag = 0;
+      asm volatile("" ::: "memory");
       trace_at(s, 1);
       const int rb = (((s - 1) & 1) * slot_floats + grp_off + p0 * LRB) * 4;
       u32x4 r0[NPW + 1], r1[NPW + 1], r2[NPW + 1];
@@ -728,6 +800,10 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
       for (int i = 0; i < 4; ++i)
         red[(wave * 16 + (lane >> 4) * 4 + i) * RC + 16 * c + (lane & 15)] = acc[c][i];
     __syncthreads();
+    if (flag == 0) {
+      poison_rest(dgx, s, T, d == 0, N, D, n, d, H, j, H3, 3, owner);
+      return;
+    }
     const float dyv = pin[m * LU + u], g_r = pin[256 + m * LU + u], g_z = pin[512 + m * LU + u];
     const float g_n = pin[768 + m * LU + u], g_hn = pin[1024 + m * LU + u];
     const float hp = pin[1280 + m * LU + u];
@@ -765,9 +841,7 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     pout[768 + m * LU + u] = dghn;
     {
       // the row's scale: max over the sample's 32 units x 3 gates (32 consecutive lanes)
-      float mx = fmaxf(fmaxf(fabsf(dar), fabsf(daz)), fabsf(dghn));
-#pragma unroll
-      for (int o = 1; o < 32; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+      const float mx = half_wave_max(fmaxf(fmaxf(fabsf(dar), fabsf(daz)), fabsf(dghn)));
       const int e = h3_row_exp(mx);
       const float sc = __builtin_ldexpf(1.f, e);
       const float vr = dar * sc, vz = daz * sc, vn = dghn * sc;
@@ -798,9 +872,18 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
       }
     }
     trace_at(s, 5);
+    if (ROWS) {
+      // max over the sample's 32 units x 3 gates of dgx (32 consecutive lanes); 0 where t >= len
+      const float rm = half_wave_max(fmaxf(fmaxf(fabsf(dar), fabsf(daz)), fabsf(dan)));
+      if (u == 0) rowmx[(s & 1) * LB + m] = rm;
+    }
   }
   __syncthreads();
   if (io && !kAblStores) store_out(T - 1);
+  if (!kAblStores) {
+    if (T > 1) store_rmx(T - 2);
+    store_rmx(T - 1);
+  }
   if (camax != nullptr) {
     // column maxima of dgx [T N][D 3H] into camax[0, D 3H) and dgh into [D 3H, 2 D 3H): the 8
     // samples' running maxima per unit, one unsigned atomic max per (gate, unit)
@@ -848,6 +931,35 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 }
 
 // ---------------------------------------------------------------------------------------
+// One preparation launch per recurrence call instead of two fills: zeroes `za` / `zb` (the
+// counter area; the backward's column maxima) and sets every word of `ff` (the part of the
+// forward's sentinel ring these kernels use) to the sentinel.  ff is 16-B aligned, ff16 its
+// length in 16-B units.
+__global__ __launch_bounds__(256) void gru_xl_prep_kernel(unsigned* __restrict__ za, size_t na,
+                                                          unsigned* __restrict__ zb, size_t nb,
+                                                          u32x4* __restrict__ ff, size_t ff16) {
+  const size_t i0 = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  const size_t step = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = i0; i < na; i += step) za[i] = 0u;
+  for (size_t i = i0; i < nb; i += step) zb[i] = 0u;
+  for (size_t i = i0; i < ff16; i += step) ff[i] = u32x4{kSentinel, kSentinel, kSentinel, kSentinel};
+}
+
+// out[row] = max over the row's D x UBX partials the backward stored in rowp (float bits; all
+// are >= 0, so the float max is the maximum of the bits): 8 lanes per row
+__global__ __launch_bounds__(256) void gru_xl_row_amax_kernel(const float* __restrict__ rowp,
+                                                              int rows, int parts,
+                                                              unsigned* __restrict__ out) {
+  const int r = (blockIdx.x * 256 + (int)threadIdx.x) >> 3, k = threadIdx.x & 7;
+  float m = 0.f;
+  if (r < rows)
+    for (int i = k; i < parts; i += 8) m = fmaxf(m, rowp[(int64_t)r * parts + i]);
+#pragma unroll
+  for (int o = 1; o < 8; o <<= 1) m = fmaxf(m, __shfl_xor(m, o));
+  if (r < rows && k == 0) out[r] = __float_as_uint(m);
+}
+
+// ---------------------------------------------------------------------------------------
 // host side (called by ds2_gru_fwd / ds2_gru_bwd in gru.hip with their workspace carve-up)
 
 static inline bool env_off(const char* name) {
@@ -892,10 +1004,12 @@ static const void* fwd_xl_fn(int UBX) {
   return nullptr;
 }
 
-static const void* bwd_xl_fn(int UBX) {
+static const void* bwd_xl_fn(int UBX, bool rows) {
   const int need = (UBX + LW - 1) / LW;
-#define DS2_BXL(K) \
-  if (need <= K + 1) return reinterpret_cast<const void*>(gru_bwd_xl_kernel<K>);
+#define DS2_BXL(K)                                                                    \
+  if (need <= K + 1)                                                                  \
+    return rows ? reinterpret_cast<const void*>(gru_bwd_xl_kernel<K, true>)           \
+                : reinterpret_cast<const void*>(gru_bwd_xl_kernel<K, false>);
   DS2_BXL(1) DS2_BXL(3) DS2_BXL(6)
 #undef DS2_BXL
   return nullptr;
@@ -908,41 +1022,77 @@ size_t gru_xl_ring_bytes(int n, int h, int num_dirs, bool bwd) {
   return bwd ? 2 * G * UBX * LRB * sizeof(float) : LSLOTS * G * UBX * 256 * sizeof(float);
 }
 
+// The one preparation launch (gru_xl_prep_kernel): zeroes the counter area [ctrs, + ctr_bytes)
+// and `zb` (nb words, nullable), fills ff_bytes of the ring with the sentinel.
+static bool xl_prepare(unsigned* ctrs, size_t ctr_bytes, unsigned* zb, size_t nb, float* ring,
+                       size_t ff_bytes, hipStream_t st) {
+  const size_t na = ctr_bytes / sizeof(unsigned), ff16 = ff_bytes / 16;
+  const size_t most = std::max(std::max(na, nb), ff16);
+  const unsigned grid = (unsigned)std::min<size_t>(1024, std::max<size_t>(1, (most + 255) / 256));
+  hipLaunchKernelGGL(gru_xl_prep_kernel, dim3(grid), dim3(256), 0, st, ctrs, na, zb, nb,
+                     reinterpret_cast<u32x4*>(ring), ff16);
+  return hipGetLastError() == hipSuccess;
+}
+
+// ctrs: the counter area ([ctrs, + ctr_bytes), `xl` and `err` inside it): these launches zero
+// it and set the ring's sentinels themselves, so the caller fills nothing when they answer
+// true; on false the caller prepares the area for the kernel it falls back to.  err_out
+// (nullable): the caller's status word, OR-ed by the kernel itself (no fold launch).
 bool launch_gru_fwd_xl(int t_max, int n, int h, int num_dirs, const float* xproj,
                        const float* w_hh_f, const float* w_hh_r, const float* b_hh_f,
                        const float* b_hh_r, const int* lens, float* h_all, float* gates,
-                       float* ring, unsigned* xl, unsigned* err, unsigned long long* stamps,
-                       size_t lds_pad, hipStream_t st) {
+                       float* ring, unsigned* ctrs, size_t ctr_bytes, unsigned* xl, unsigned* err,
+                       unsigned* err_out, unsigned long long* stamps, size_t lds_pad,
+                       hipStream_t st) {
   if (gru_xl_groups(n, h, num_dirs) == 0 || env_off("DS2_GRU_H3")) return false;
   apply_spin_limit_env();
   apply_rnn_tune_env();
   const int UBX = h / LU, BTX = (n + LB - 1) / LB;
   const void* fn = fwd_xl_fn(UBX);
   if (fn == nullptr) return false;
+  if (!xl_prepare(ctrs, ctr_bytes, nullptr, 0, ring, gru_xl_ring_bytes(n, h, num_dirs, false), st))
+    return false;
   int T_ = t_max, N_ = n, H_ = h, D_ = num_dirs, UB_ = UBX, BT_ = BTX, FG_ = xl_force_global();
   void* args[] = {&T_, &N_, &H_, &D_, &UB_, &BT_, &xproj, &w_hh_f, &w_hh_r, &b_hh_f,
-                  &b_hh_r, &lens, &h_all, &gates, &ring, &xl, &err, &stamps, &FG_};
+                  &b_hh_r, &lens, &h_all, &gates, &ring, &xl, &err, &err_out, &stamps, &FG_};
   return rnn_launch(fn, dim3(8 * UBX), dim3(LT), args, lds_pad, st) == hipSuccess;
 }
 
-// dbp: [ceil(n / 8)][D][4][H] partials (nullable); camax as launch_gru_bwd_x6's
+// dbp: [ceil(n / 8)][D][4][H] partials (nullable); camax as launch_gru_bwd_x6's (zeroed by the
+// preparation launch); rowp: [T N][D][h / 32] row-maximum partials of dgates_x (nullable)
 bool launch_gru_bwd_xl(int t_max, int n, int h, int num_dirs, const float* dy, int dy_dirs,
                        const float* w_hh_f, const float* w_hh_r, const float* h_all,
                        const float* gates, const int* lens, float* dgates_x, float* dgates_h,
-                       float* ring, unsigned* xl, unsigned* err, unsigned long long* stamps,
-                       double* dbp, size_t lds_pad, hipStream_t st, unsigned* camax) {
+                       float* ring, unsigned* ctrs, size_t ctr_bytes, unsigned* xl, unsigned* err,
+                       unsigned* err_out, unsigned long long* stamps, double* dbp, size_t lds_pad,
+                       hipStream_t st, unsigned* camax, float* rowp) {
   if (gru_xl_groups(n, h, num_dirs) == 0 || env_off("DS2_GRU_H3_BWD")) return false;
   apply_spin_limit_env();
   apply_rnn_tune_env();
   const int UBX = h / LU, BTX = (n + LB - 1) / LB;
-  const void* fn = bwd_xl_fn(UBX);
+  const void* fn = bwd_xl_fn(UBX, rowp != nullptr);
   if (fn == nullptr) return false;
+  if (!xl_prepare(ctrs, ctr_bytes, camax, camax != nullptr ? (size_t)2 * num_dirs * 3 * h : 0,
+                  nullptr, 0, st))
+    return false;
   int T_ = t_max, N_ = n, H_ = h, D_ = num_dirs, UB_ = UBX, BT_ = BTX, DYD_ = dy_dirs;
   int FG_ = xl_force_global();
   void* args[] = {&T_, &N_, &H_, &D_, &UB_, &BT_, &dy, &DYD_, &w_hh_f, &w_hh_r, &h_all,
-                  &gates, &lens, &dgates_x, &dgates_h, &ring, &xl, &err, &stamps, &dbp, &camax,
-                  &FG_};
+                  &gates, &lens, &dgates_x, &dgates_h, &ring, &xl, &err, &err_out, &stamps, &dbp,
+                  &camax, &rowp, &FG_};
   return rnn_launch(fn, dim3(8 * UBX), dim3(LT), args, lds_pad, st) == hipSuccess;
+}
+
+// the row-maximum partials of launch_gru_bwd_xl: bytes, and their reduction to out[t_max n]
+size_t gru_xl_rowp_bytes(int t_max, int n, int h, int num_dirs) {
+  return (size_t)t_max * n * num_dirs * (h / LU) * sizeof(float);
+}
+
+void launch_gru_xl_row_amax(int t_max, int n, int h, int num_dirs, const float* rowp,
+                            unsigned* out, hipStream_t st) {
+  const int rows = t_max * n;
+  hipLaunchKernelGGL(gru_xl_row_amax_kernel, dim3((rows * 8 + 255) / 256), dim3(256), 0, st, rowp,
+                     rows, num_dirs * (h / LU), out);
 }
 
 }  // namespace ds2

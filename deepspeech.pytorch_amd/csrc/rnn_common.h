@@ -219,6 +219,14 @@ static inline void fold_err(const unsigned* err, unsigned* err_out, hipStream_t 
   if (err_out != nullptr) hipLaunchKernelGGL(err_fold_kernel, dim3(1), dim3(64), 0, st, err, err_out);
 }
 
+// The XCD-local kernels (gru_xl.hip) take err_out themselves and need no fold launch: one lane
+// ORs a failure into the launch's error word and, when the caller gave one, into err_out.
+__device__ __forceinline__ void raise_err(unsigned* err, unsigned* err_out) {
+  __hip_atomic_fetch_or(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (err_out != nullptr)
+    __hip_atomic_fetch_or(err_out, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 __device__ __forceinline__ void st_sc1(float* p, float v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }

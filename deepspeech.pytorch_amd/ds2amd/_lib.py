@@ -102,6 +102,8 @@ _PROTOS = {
     "ds2_gru_bwd_bias_amax": (_c_int, [_c_int, _c_int, _c_int, _c_int, _vp, _c_int, _vp, _vp,
                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                        _sz, _vp]),
+    "ds2_gru_row_amax_workspace_size": (_sz, [_c_int, _c_int, _c_int, _c_int]),
+    "ds2_gru_row_amax": (_c_int, [_c_int, _c_int, _c_int, _c_int, _vp, _sz, _vp, _vp]),
     "ds2_lstm_fwd_workspace_size": (_sz, [_c_int, _c_int, _c_int]),
     "ds2_lstm_fwd": (_c_int, [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                               _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -197,6 +199,19 @@ def check(status: int, what: str) -> None:
 def call(name: str, *args) -> None:
     lib = load()
     check(getattr(lib, name)(*args), name)
+
+
+UNSUPPORTED_SHAPE = 2   # DS2_UNSUPPORTED_SHAPE
+
+
+def call_or_unsupported(name: str, *args) -> bool:
+    """call(), but False (nothing raised) where the entry point answers
+    DS2_UNSUPPORTED_SHAPE: the documented "take the other kernel" status."""
+    status = getattr(load(), name)(*args)
+    if status == UNSUPPORTED_SHAPE:
+        return False
+    check(status, name)
+    return True
 
 
 def size(name: str, *args) -> int:

@@ -908,7 +908,7 @@ def _rnn_param_grads_bf16(x2d, h_all, dgx, dgh, weights, nd, g, t, n, inp, h, ne
 
 
 def _rnn_param_grads(x, h_all, dgx, dgh, weights, nd, g, need_dx, bf16=False, pre=None,
-                     dbias=None, shared_bf16=True, col_amax=None):
+                     dbias=None, shared_bf16=True, col_amax=None, row_amax=None):
     """Weight/bias/input gradients of one recurrent layer from the gate gradients.
 
     dgx = d/d(x W_ih^T + b_ih), dgh = d/d(h W_hh^T + b_hh), both [T, N, D, g]
@@ -916,8 +916,9 @@ def _rnn_param_grads(x, h_all, dgx, dgh, weights, nd, g, need_dx, bf16=False, pr
     direction already summed (the GRU backward kernel's own sums) skips the column sums.
     shared_bf16=False keeps bf16 mode on the per-GEMM conversions (the cross-check of
     _rnn_param_grads_bf16's shared copies, tests/test_gpu_ops.py).  col_amax: the column
-    maxima of dgx and dgh ([2 D g] float bits) when the recurrence kept them.  pre: the column
-    maxima of x and of the stacked W_ih the forward's input projection took (_rnn_input_proj).
+    maxima of dgx and dgh ([2 D g] float bits) when the recurrence kept them; row_amax: the row
+    maxima of dgx ([T N] float bits) when it kept those too (else one ds2_amax pass).  pre: the
+    column maxima of x and of the stacked W_ih the forward's input projection took (_rnn_input_proj).
     """
     t, n, inp = x.shape
     h = h_all.shape[-1]
@@ -944,7 +945,8 @@ def _rnn_param_grads(x, h_all, dgx, dgh, weights, nd, g, need_dx, bf16=False, pr
             am["dgx_c"] = col_amax[:ld]
             am["dgh_c"] = col_amax[ld:] if col_amax.numel() == 2 * ld else am["dgx_c"]
             if need_dx:
-                am["dgx_r"] = amax(dgx, tn, ld, ld, want_cols=False)[0]
+                am["dgx_r"] = (row_amax if row_amax is not None
+                               else amax(dgx, tn, ld, ld, want_cols=False)[0])
         else:
             am["dgx_r"], am["dgx_c"] = amax(dgx, tn, ld, ld, want_rows=need_dx)
             am["dgh_c"] = am["dgx_c"] if dgh is dgx else amax(dgh, tn, ld, ld, want_rows=False)[1]
@@ -1083,7 +1085,11 @@ class GRULayerFn(torch.autograd.Function):
         dgh = torch.empty(t, n, nd, h3, device=dev, dtype=_F32)
         w_hh_f = weights[1]
         w_hh_r = weights[5] if nd == 2 else None
-        ws = _ws(_lib.size("ds2_gru_bwd_workspace_size", n, h, nd), dev)
+        h3_scales = h3_enabled() and not bf16
+        want_rows = h3_scales and ctx.needs_input_grad[0]
+        # with the dX GEMM's row scales wanted, room for the recurrence's row-maximum partials
+        ws = _ws(_lib.size("ds2_gru_row_amax_workspace_size", t, n, h, nd) if want_rows
+                 else _lib.size("ds2_gru_bwd_workspace_size", n, h, nd), dev)
         _guard_cooperative("gru", n, h, nd)
         # bias gradients straight into their slots, summed by the recurrence kernel; with the
         # fp16x3 GEMMs the kernel also keeps the column maxima of dgx / dgh they scale by
@@ -1092,17 +1098,25 @@ class GRULayerFn(torch.autograd.Function):
                   h_all.data_ptr(), gates.data_ptr(), lens.data_ptr(), dgx.data_ptr(),
                   dgh.data_ptr(), dbias[0].data_ptr(), dbias[1].data_ptr(),
                   _p(dbias[2] if nd == 2 else None), _p(dbias[3] if nd == 2 else None))
-        col_amax = None
-        if h3_enabled() and not bf16:
+        col_amax = row_amax = None
+        if h3_scales:
             col_amax = torch.empty(2 * nd * h3, dtype=_I32, device=dev)
             _lib.call("ds2_gru_bwd_bias_amax", *common, col_amax.data_ptr(),
                       rnn_status_word(dev).data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+            if want_rows and t * n > 0:
+                # the XCD-local kernel's partials reduced to dgx's row maxima; a kernel without
+                # them ran: None, and _rnn_param_grads takes its ds2_amax pass over dgx
+                row_amax = torch.empty(t * n, dtype=_I32, device=dev)
+                if not _lib.call_or_unsupported("ds2_gru_row_amax", t, n, h, nd,
+                                                ws.data_ptr(), ws.numel(), row_amax.data_ptr(),
+                                                _stream()):
+                    row_amax = None
         else:
             _lib.call("ds2_gru_bwd_bias", *common, rnn_status_word(dev).data_ptr(),
                       ws.data_ptr(), ws.numel(), _stream())
         dx, grads = _rnn_param_grads(x, h_all, dgx, dgh, weights, nd, h3,
                                      ctx.needs_input_grad[0], bf16, ctx.pre, dbias=dbias,
-                                     col_amax=col_amax)
+                                     col_amax=col_amax, row_amax=row_amax)
         return (dx, None, None, None, *grads)
 
 

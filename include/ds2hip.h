@@ -296,6 +296,17 @@ ds2_status_t ds2_gru_bwd_bias_amax(int t_max, int n, int h, int num_dirs, const 
                                    float* db_hh_f, float* db_ih_r, float* db_hh_r,
                                    unsigned* col_amax, unsigned* err_out, void* ws,
                                    size_t ws_bytes, ds2_stream_t stream);
+/* The row maxima of dgates_x ([T N] float bits, ds2_amax's row format: the dX GEMM's row
+ * scales) without a pass over dgates_x.  When ds2_gru_bwd_bias_amax is given a workspace of
+ * ds2_gru_row_amax_workspace_size(T, N, H, D) bytes (>= ds2_gru_bwd_workspace_size), the
+ * XCD-local fp16x3 recurrence leaves per-workgroup partial maxima behind in it, and
+ * ds2_gru_row_amax -- called next on the same stream with the same shape and workspace --
+ * reduces them; rows with t >= len are 0.  DS2_UNSUPPORTED_SHAPE when that workspace holds no
+ * partials of such a call (another recurrence kernel ran, or the workspace was the smaller
+ * one): the caller then takes ds2_amax over dgates_x, which gives the same bits.          */
+size_t ds2_gru_row_amax_workspace_size(int t_max, int n, int h, int num_dirs);
+ds2_status_t ds2_gru_row_amax(int t_max, int n, int h, int num_dirs, const void* ws,
+                                  size_t ws_bytes, unsigned* row_amax, ds2_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* (Bi)directional LSTM recurrence (torch gate order i, f, g, o), same packed-

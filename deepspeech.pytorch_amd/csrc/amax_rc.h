@@ -1,8 +1,9 @@
 // Row AND column maxima of |v| over a [rows][c] fp32 matrix (c <= 2048), one wave per row:
 // the fp16x3 GEMM scales (float bits, ds2_amax's format).  APPLY: v = the BatchNorm affine of
-// x, written to y (ds2_bn_apply_amax: the same expression as bn.hip's apply_rows_kernel), else
-// v = x (ds2_amax of a narrow matrix).  Lane l holds the float4 columns l + 64 j (j < CPL) --
-// with APPLY their gamma / mean / invstd / beta -- in registers; two rows per pass; a block
+// x, written to y (ds2_bn_apply_amax: the same expression as bn.hip's apply_rows_kernel; with
+// RELU followed by max(v, 0): ds2_bn_relu_apply_amax), else v = x (ds2_amax of a narrow
+// matrix).  Lane l holds the float4 columns l + 64 j (j < CPL) -- with APPLY their gamma /
+// mean / invstd / beta -- in registers; two rows per pass; a block
 // covers `rpb` rows with 4 waves, writes each row's maximum (a wave reduction, no atomics),
 // folds the waves' column maxima through LDS and leaves them with one unsigned atomic max per
 // column (cmax zeroed first).
@@ -11,7 +12,7 @@
 
 namespace ds2 {
 
-template <int CPL, bool APPLY>
+template <int CPL, bool APPLY, bool RELU = false>
 __global__ __launch_bounds__(256) void rows_amax_kernel(
     const float* __restrict__ x, int R, int C, int64_t ld, const float* __restrict__ mean,
     const float* __restrict__ invstd, const float* __restrict__ gamma,
@@ -39,6 +40,12 @@ __global__ __launch_bounds__(256) void rows_amax_kernel(
       v.y = ga[j].y * ((v.y - me[j].y) * is[j].y) + be[j].y;
       v.z = ga[j].z * ((v.z - me[j].z) * is[j].z) + be[j].z;
       v.w = ga[j].w * ((v.w - me[j].w) * is[j].w) + be[j].w;
+      if (RELU) {
+        v.x = fmaxf(v.x, 0.f);
+        v.y = fmaxf(v.y, 0.f);
+        v.z = fmaxf(v.z, 0.f);
+        v.w = fmaxf(v.w, 0.f);
+      }
     }
     return v;
   };
@@ -107,7 +114,7 @@ __global__ __launch_bounds__(256) void rows_amax_kernel(
 }
 
 // rows_amax_kernel's launch for c <= 2048 (the columns-per-lane instantiation by width)
-template <bool APPLY>
+template <bool APPLY, bool RELU = false>
 inline void launch_rows_amax(const float* x, int rows, int c, int64_t ld, const float* mean,
                              const float* invstd, const float* gamma, const float* beta, float* y,
                              unsigned* rmax, unsigned* cmax, hipStream_t st) {
@@ -115,8 +122,8 @@ inline void launch_rows_amax(const float* x, int rows, int c, int64_t ld, const 
   const dim3 grid((rows + rpb - 1) / rpb);
   const int c4 = c / 4;
 #define DS2_RA(CPL_)                                                                          \
-  hipLaunchKernelGGL((rows_amax_kernel<CPL_, APPLY>), grid, dim3(256), 0, st, x, rows, c, ld, \
-                     mean, invstd, gamma, beta, y, rpb, rmax, cmax)
+  hipLaunchKernelGGL((rows_amax_kernel<CPL_, APPLY, RELU>), grid, dim3(256), 0, st, x, rows, c, \
+                     ld, mean, invstd, gamma, beta, y, rpb, rmax, cmax)
   if (c4 <= 64) DS2_RA(1);
   else if (c4 <= 128) DS2_RA(2);
   else if (c4 <= 256) DS2_RA(4);

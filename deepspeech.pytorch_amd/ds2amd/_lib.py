@@ -54,6 +54,22 @@ _PROTOS = {
     "ds2_conv2d_dgrad": (_c_int, [_vp, _vp, _vp] + [_c_int] * 11 + [_vp, _sz, _vp]),
     "ds2_conv2d_wgrad_workspace_size": (_sz, [_c_int] * 11),
     "ds2_conv2d_wgrad": (_c_int, [_vp, _vp, _vp, _vp] + [_c_int] * 11 + [_vp, _sz, _vp]),
+    "ds2_conv1d_workspace_size": (_sz, [_c_int] * 7),
+    "ds2_conv1d_fwd": (_c_int, [_vp, _vp, _vp, _vp] + [_c_int] * 7 + [_vp, _sz, _vp]),
+    "ds2_conv1d_fwd_amax": (_c_int, [_vp, _vp, _vp, _vp] + [_c_int] * 7 + [_vp, _vp, _sz, _vp]),
+    "ds2_conv1d_dgrad": (_c_int, [_vp, _vp, _vp] + [_c_int] * 7 + [_vp, _sz, _vp]),
+    "ds2_conv1d_wgrad_workspace_size": (_sz, [_c_int] * 7),
+    "ds2_conv1d_wgrad": (_c_int, [_vp, _vp, _vp, _vp] + [_c_int] * 7 + [_vp, _sz, _vp]),
+    "ds2_conv1d_wgrad_amax": (_c_int, [_vp, _vp, _vp, _vp] + [_c_int] * 7 + [_vp, _vp, _sz, _vp]),
+    "ds2_bn_relu_apply_amax": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                        _vp]),
+    "ds2_nct_to_tnc": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp]),
+    "ds2_glu_fwd": (_c_int, [_vp, _c_int, _c_int, _vp, _vp]),
+    "ds2_glu_bwd": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _vp]),
+    "ds2_bn_relu_apply": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ds2_bn_relu_bwd_workspace_size": (_sz, [_c_int, _c_int]),
+    "ds2_bn_relu_bwd": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                 _vp, _sz, _vp]),
     "ds2_bn_workspace_size": (_sz, [_c_int, _c_int, _c_int]),
     "ds2_bn_train_stats": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_f, _c_f, _vp, _vp, _vp, _vp,
                                     _vp, _sz, _vp]),

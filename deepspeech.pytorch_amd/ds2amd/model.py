@@ -254,8 +254,80 @@ class Hardtanh(nn.Hardtanh):
     pass
 
 
+class Conv1d(nn.Conv1d):
+    """nn.Conv1d parameters and initialiser; forward on time-major [T, N, Cin] through the HIP
+    Conv1d kernels (ops.Conv1dFn).  Dilation 1, groups 1, zero padding: what Wav2Letter builds."""
+
+    def forward(self, x):
+        if x.dim() != 3:
+            raise ValueError("ds2amd.Conv1d expects time-major [T, N, Cin]")
+        if self.dilation[0] != 1 or self.groups != 1 or self.padding_mode != 'zeros' \
+                or isinstance(self.padding, str):
+            raise ValueError("ds2amd.Conv1d supports dilation 1, groups 1, numeric zero padding")
+        return ops.Conv1dFn.apply(x, self.weight, self.bias, self.stride[0], self.padding[0])
+
+
+class GLUModule(nn.Module):
+    """The reference's GLUModule (model.py:112-118): F.glu over the channels, which are the
+    last dimension of the time-major layout."""
+
+    def __init__(self, dim):
+        super().__init__()
+        self.dim = dim
+
+    def forward(self, x):
+        return ops.GLUFn.apply(x)
+
+
+def _bn_args(bn):
+    training = bn.training or not bn.track_running_stats
+    if bn.training and bn.track_running_stats:
+        bn.num_batches_tracked.add_(1)
+    mom = bn.momentum if bn.momentum is not None else 0.0
+    return (bn.weight, bn.bias, bn.running_mean, bn.running_var, training, mom, bn.eps)
+
+
+def Wav2Letter(size, cnn_width, bnm, dropout, not_glu, repeat_layers, kernel_size=13,
+               bnorm=True):
+    """The reference's Wav2Letter builder (model.py:506-562): the same modules in the same
+    order -- so ``nn.Sequential(*modules)`` has the same state_dict keys and, under one seed,
+    the same initial weights -- on the HIP-backed classes.  not_glu: Conv1d -> BatchNorm1d ->
+    ReLU per block; else Conv1d(2 x out) -> GLU -> BatchNorm1d(out).  nn.Dropout follows each
+    block only when dropout > 0 (it shifts the indices, as in the reference)."""
+
+    def _block(in_channels, out_channels, kernel_size, padding=0, stride=1, bnorm=False,
+               bias=True, dropout=0):
+        if not not_glu:
+            out_channels = int(out_channels * 2)
+        res = [Conv1d(in_channels=in_channels, out_channels=out_channels,
+                      kernel_size=kernel_size, padding=padding, stride=stride, bias=bias)]
+        if not_glu:
+            if bnorm:
+                res.append(nn.BatchNorm1d(out_channels, momentum=bnm))
+            res.append(nn.ReLU(inplace=True))
+        else:
+            res.append(GLUModule(dim=1))
+            if bnorm:
+                res.append(nn.BatchNorm1d(int(out_channels // 2), momentum=bnm))
+        if dropout > 0:
+            res.append(nn.Dropout(dropout))
+        return res
+
+    padding = kernel_size // 2
+    modules = _block(161, cnn_width, kernel_size, padding=padding, stride=2, bnorm=bnorm,
+                     bias=not bnorm, dropout=dropout)                          # "prolog"
+    for _ in range(repeat_layers):
+        modules.extend(_block(cnn_width, cnn_width, kernel_size, padding=padding, bnorm=bnorm,
+                              bias=not bnorm, dropout=dropout))
+    modules.extend(_block(cnn_width, size, 31, padding=15, bnorm=bnorm, bias=not bnorm,
+                          dropout=dropout))                                    # "epilog"
+    modules.extend(_block(size, size, 1, bnorm=bnorm, bias=not bnorm, dropout=dropout))
+    return modules
+
+
 class DeepSpeech(nn.Module):
-    """DS2 (ref model.py:183-393, rnn_type in supported_rnns)."""
+    """DS2 (ref model.py:183-393, rnn_type in supported_rnns) and the Wav2Letter acoustic
+    model (rnn_type 'cnn', model.py:217-234, 348-353)."""
 
     def __init__(self, rnn_type='gru', labels="abc", rnn_hidden_size=768, nb_layers=6,
                  audio_conf=None, bidirectional=True, context=20, bnm=0.1, dropout=0,
@@ -276,9 +348,10 @@ class DeepSpeech(nn.Module):
         self._bnm = bnm
         self._dropout = dropout
         self._cnn_width = cnn_width
-        if rnn_type not in supported_rnns:
+        # of the reference's convolutional families (model.py:217-310) only 'cnn' is built
+        if rnn_type not in supported_rnns and rnn_type != 'cnn':
             raise ValueError(f"rnn_type {rnn_type!r} not supported by ds2amd "
-                             f"(have {sorted(supported_rnns)})")
+                             f"(have {sorted(supported_rnns) + ['cnn']})")
 
         sample_rate = self._audio_conf.get("sample_rate", 16000)
         window_size = self._audio_conf.get("window_size", 0.02)
@@ -293,6 +366,20 @@ class DeepSpeech(nn.Module):
             nn.BatchNorm2d(32, momentum=bnm),
             Hardtanh(0, 20, inplace=True),
         ))
+        if rnn_type == 'cnn':
+            # Wav2Letter (model.py:217-234).  self.conv above stays constructed and in the
+            # state_dict although this forward never calls it; get_seq_lens still reads it.
+            if rnn_gemm_precision != 'fp32':
+                raise ValueError("rnn_gemm_precision='bf16' applies to the recurrent layers' "
+                                 "GEMMs; rnn_type 'cnn' has none (fp32 only)")
+            self._rnn_gemm_precision = 'fp32'
+            self.rnns = nn.Sequential(*Wav2Letter(
+                size=rnn_hidden_size, cnn_width=cnn_width, bnm=bnm, dropout=dropout,
+                not_glu=bidirectional, repeat_layers=nb_layers, kernel_size=13))
+            self.fc = nn.Sequential(Conv1d(in_channels=rnn_hidden_size, out_channels=num_classes,
+                                           kernel_size=1))
+            self.lookahead = None
+            return
         rnn_input_size = int(math.floor((sample_rate * window_size + 1e-2) / 2) + 1)
         rnn_input_size = int(math.floor(rnn_input_size + 2 * 20 - 41 + 1e-2) / 2 + 1)
         rnn_input_size = int(math.floor(rnn_input_size + 2 * 10 - 21 + 1e-2) / 2 + 1)
@@ -322,6 +409,11 @@ class DeepSpeech(nn.Module):
     def set_rnn_gemm_precision(self, precision: str):
         """'fp32' | 'bf16' for every recurrent layer's GEMMs (see __init__)."""
         ops.rnn_gemm_precision(precision)          # validates
+        if self._rnn_type == 'cnn':
+            if precision != 'fp32':
+                raise ValueError("rnn_gemm_precision='bf16' applies to the recurrent layers' "
+                                 "GEMMs; rnn_type 'cnn' has none (fp32 only)")
+            return self
         self._rnn_gemm_precision = precision
         for m in self.rnns:
             m.rnn.gemm_precision = precision
@@ -338,6 +430,9 @@ class DeepSpeech(nn.Module):
         lengths = lengths.cpu().int()
         output_lengths = self.get_seq_lens(lengths)
         lens_dev = output_lengths.to(x.device, non_blocking=True)
+        if self._rnn_type == 'cnn':
+            x_tnc = self._forward_cnn(x)
+            return x_tnc.transpose(0, 1), ops.SoftmaxTNCFn.apply(x_tnc), lens_dev
         x = self.conv.forward_collapsed(x, lens_dev)          # T' x N x (32*41)
         for rnn in self.rnns:
             x = rnn(x, lens_dev)
@@ -349,6 +444,36 @@ class DeepSpeech(nn.Module):
         x = x.transpose(0, 1)
         outs = ops.SoftmaxTNCFn.apply(x_tnc)
         return x, outs, lens_dev
+
+    def _forward_cnn(self, x):
+        """model.py:350-353 on the time-major layout: [N,1,161,T] -> logits [T',N,C].  No
+        length masking anywhere, as in the reference: padded frames enter the convolutions
+        and the BatchNorm statistics.  A BatchNorm1d followed by ReLU runs as one pass."""
+        if x.dim() != 4 or x.size(1) != 1:
+            raise ValueError("DeepSpeech(rnn_type='cnn') expects x [N, 1, 161, T]")
+        x = ops.nct_to_tnc(x.detach().reshape(x.size(0), x.size(2), x.size(3)))
+        mods = list(self.rnns) + list(self.fc)
+        i = 0
+        while i < len(mods):
+            m = mods[i]
+            if isinstance(m, nn.BatchNorm1d):
+                t, n, c = x.shape
+                relu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
+                fn = ops.BNReLUFn if relu else ops.SeqBatchNormFn
+                x = fn.apply(x.reshape(t * n, c), *_bn_args(m)).view(t, n, c)
+                i += 2 if relu else 1
+                continue
+            if isinstance(m, nn.ReLU):
+                raise ValueError("rnn_type 'cnn': a ReLU that does not follow a BatchNorm1d")
+            x = m(x)           # Conv1d / GLUModule (HIP); nn.Dropout (torch, only if dropout > 0)
+            i += 1
+        return x
+
+    def unused_parameters(self):
+        """Parameters no forward reads, so they never receive a gradient (rnn_type 'cnn':
+        the MaskConv stack, constructed for state_dict parity only).  An optimizer must
+        leave them alone as torch's do with ``.grad is None`` (no weight decay either)."""
+        return list(self.conv.parameters()) if self._rnn_type == 'cnn' else []
 
     def get_seq_lens(self, input_length):
         """Same float arithmetic as the reference (model.py:382-393)."""

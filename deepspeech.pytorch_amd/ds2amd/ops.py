@@ -302,6 +302,97 @@ def conv2d_wgrad(dy, x, w_shape, stride, padding, with_bias: bool, out_dw=None, 
     return dw, db
 
 
+def conv1d_out_len(t: int, k: int, s: int, p: int) -> int:
+    return (t + 2 * p - k) // s + 1
+
+
+def _conv1d_dims(x_shape, w_shape, stride, padding):
+    t, n, ci = x_shape
+    co, ci_w, k = w_shape
+    if ci_w != ci:
+        raise _lib.Ds2Error(f"conv1d: input has {ci} channels, the weight expects {ci_w}")
+    if conv1d_out_len(t, k, stride, padding) <= 0 and t > 0 and n > 0:
+        raise _lib.Ds2Error(f"conv1d: kernel {k} (padding {padding}) is longer than the "
+                            f"{t}-frame input")
+    return (t, n, ci, co, k, int(stride), int(padding))
+
+
+def conv1d_fwd(x, weight, bias, stride: int, padding: int, x_row_amax=None):
+    """nn.Conv1d on time-major activations: x [T, N, Cin] -> [T_out, N, Cout]; weight
+    [Cout, Cin, k] in torch's layout (ds2_conv1d_fwd_amax).  x_row_amax: x's row maxima
+    (int32 float bits, [T N]) where its producer kept them, else computed by the call."""
+    x = _need(x, "conv1d.x")
+    weight = _need(weight, "conv1d.weight")
+    dims = _conv1d_dims(x.shape, weight.shape, stride, padding)
+    t, n, ci, co, k, s, p = dims
+    y = torch.empty(max(conv1d_out_len(t, k, s, p), 0), n, co, device=x.device, dtype=_F32)
+    ws = _ws(_lib.size("ds2_conv1d_workspace_size", *dims), x.device)
+    _lib.call("ds2_conv1d_fwd_amax", x.data_ptr(), weight.data_ptr(),
+              _p(None if bias is None else _need(bias, "conv1d.bias")), y.data_ptr(), *dims,
+              _p(x_row_amax), ws.data_ptr(), ws.numel(), _stream())
+    return y
+
+
+def conv1d_dgrad(dy, weight, x_shape, stride: int, padding: int):
+    dy = _need(dy, "conv1d.dy")
+    weight = _need(weight, "conv1d.weight")
+    dims = _conv1d_dims(x_shape, weight.shape, stride, padding)
+    dx = torch.empty(tuple(x_shape), device=dy.device, dtype=_F32)
+    ws = _ws(_lib.size("ds2_conv1d_workspace_size", *dims), dy.device)
+    _lib.call("ds2_conv1d_dgrad", dy.data_ptr(), weight.data_ptr(), dx.data_ptr(), *dims,
+              ws.data_ptr(), ws.numel(), _stream())
+    return dx
+
+
+def conv1d_wgrad(dy, x, w_shape, stride: int, padding: int, with_bias: bool, out_dw=None,
+                 out_db=None, x_col_amax=None):
+    """(dw [Cout, Cin, k], dbias [Cout] or None), overwritten, deterministic.  x_col_amax: x's
+    column maxima ([Cin] int32 float bits) where its producer kept them."""
+    dy = _need(dy, "conv1d.dy")
+    x = _need(x, "conv1d.x")
+    dims = _conv1d_dims(x.shape, w_shape, stride, padding)
+    dw = out_dw if out_dw is not None else torch.empty(tuple(w_shape), device=x.device, dtype=_F32)
+    db = None
+    if with_bias:
+        db = out_db if out_db is not None else torch.empty(w_shape[0], device=x.device, dtype=_F32)
+    ws = _ws(_lib.size("ds2_conv1d_wgrad_workspace_size", *dims), x.device)
+    _lib.call("ds2_conv1d_wgrad_amax", dy.data_ptr(), x.data_ptr(), dw.data_ptr(), _p(db), *dims,
+              _p(x_col_amax), ws.data_ptr(), ws.numel(), _stream())
+    return dw, db
+
+
+def nct_to_tnc(x):
+    """[N, C, T] -> [T, N, C] in one pass (ds2_nct_to_tnc): the spectrogram batch into the
+    time-major layout of the Conv1d kernels."""
+    x = _need(x, "nct_to_tnc.x")
+    n, c, t = x.shape
+    y = torch.empty(t, n, c, device=x.device, dtype=_F32)
+    _lib.call("ds2_nct_to_tnc", x.data_ptr(), n, c, t, y.data_ptr(), _stream())
+    return y
+
+
+def glu(x):
+    """a * sigmoid(b) over the last dimension [..., 2C] -> [..., C], a the first C channels
+    (F.glu over the channel dimension; ds2_glu_fwd)."""
+    x = _need(x, "glu.x")
+    c2 = x.shape[-1]
+    if c2 % 2:
+        raise _lib.Ds2Error(f"glu: the channel count {c2} is odd")
+    y = torch.empty(*x.shape[:-1], c2 // 2, device=x.device, dtype=_F32)
+    rows = x.numel() // c2 if c2 else 0
+    _lib.call("ds2_glu_fwd", x.data_ptr(), rows, c2 // 2, y.data_ptr(), _stream())
+    return y
+
+
+def glu_bwd(dy, x):
+    dy = _need(dy, "glu.dy")
+    c2 = x.shape[-1]
+    dx = torch.empty_like(x)
+    rows = x.numel() // c2 if c2 else 0
+    _lib.call("ds2_glu_bwd", dy.data_ptr(), x.data_ptr(), rows, c2 // 2, dx.data_ptr(), _stream())
+    return dx
+
+
 def bn_stats(x, outer, c, inner, eps, momentum, running_mean, running_var, training):
     mean = torch.empty(c, device=x.device, dtype=_F32)
     invstd = torch.empty(c, device=x.device, dtype=_F32)
@@ -1294,3 +1385,94 @@ class SoftmaxTNCFn(torch.autograd.Function):
         _lib.call("ds2_softmax_tnc_bwd", probs.data_ptr(), dprobs.contiguous().data_ptr(), t, n, c,
                   d.data_ptr(), 0, _stream())
         return d
+
+
+class Conv1dFn(torch.autograd.Function):
+    """nn.Conv1d on [T, N, Cin] (Wav2Letter's blocks and fc, model.py:518-520, 233)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, padding):
+        x = x.contiguous()
+        ctx.save_for_backward(x, weight)
+        ctx.bias = bias    # only its identity (gradient slot) is used in backward
+        ctx.cfg = (int(stride), int(padding))
+        # the fp16x3 scales of x the BatchNorm before it kept: rows for this convolution,
+        # columns for its weight gradient
+        t, n, c = x.shape
+        x_r, ctx.x_c = _take_amax(x, t * n, c)
+        return conv1d_fwd(x, weight, bias, stride, padding, x_row_amax=x_r)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        stride, padding = ctx.cfg
+        dy = dy.contiguous()
+        dx = None
+        if ctx.needs_input_grad[0]:     # the spectrogram takes no gradient: no prolog dgrad
+            dx = conv1d_dgrad(dy, weight, x.shape, stride, padding)
+        has_bias = ctx.bias is not None
+        dw, db = conv1d_wgrad(dy, x, weight.shape, stride, padding, with_bias=has_bias,
+                              out_dw=grad_like(weight),
+                              out_db=grad_like(ctx.bias) if has_bias else None,
+                              x_col_amax=ctx.x_c)
+        return dx, dw, db, None, None
+
+
+class GLUFn(torch.autograd.Function):
+    """GLUModule(dim=1) of the reference on the time-major layout (model.py:529)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = x.contiguous()
+        ctx.save_for_backward(x)
+        return glu(x)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        return glu_bwd(dy.contiguous(), x)
+
+
+class BNReLUFn(torch.autograd.Function):
+    """BatchNorm1d over (N, T) then ReLU on x viewed [R, C] (model.py:524, 527), one apply
+    pass; backward = ReLU mask + BatchNorm backward (ds2_bn_relu_bwd)."""
+
+    @staticmethod
+    def forward(ctx, x2d, gamma, beta, running_mean, running_var, training, momentum, eps):
+        x2d = x2d.contiguous()
+        r, c = x2d.shape
+        mean, invstd = bn_stats(x2d, r, c, 1, eps, momentum, running_mean, running_var, training)
+        y = torch.empty_like(x2d)
+        ptrs = (x2d.data_ptr(), y.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
+                gamma.data_ptr(), beta.data_ptr())
+        if c % 4 == 0 and c <= 2048 and r > 0 and not any(p % 16 for p in ptrs):
+            # y's row / column maxima in the same pass, for the Conv1d that reads it next
+            rmax = torch.empty(r, dtype=_I32, device=x2d.device)
+            cmax = torch.empty(c, dtype=_I32, device=x2d.device)
+            _lib.call("ds2_bn_relu_apply_amax", *ptrs[:1], r, c, *ptrs[2:], y.data_ptr(),
+                      rmax.data_ptr(), cmax.data_ptr(), _stream())
+            _tag_amax(y, r, c, rmax, cmax)
+        else:
+            _lib.call("ds2_bn_relu_apply", x2d.data_ptr(), r, c, mean.data_ptr(),
+                      invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(),
+                      _stream())
+        ctx.save_for_backward(x2d, y, gamma, beta, mean, invstd)
+        ctx.training = training
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2d, y, gamma, beta, mean, invstd = ctx.saved_tensors
+        if not ctx.training:
+            raise _lib.Ds2Error("BNReLUFn backward in eval mode is not supported")
+        r, c = x2d.shape
+        dy = dy.contiguous()
+        dx = torch.empty_like(x2d)
+        dgamma = grad_like(gamma)
+        dbeta = grad_like(beta)
+        ws = _ws(_lib.size("ds2_bn_relu_bwd_workspace_size", r, c), x2d.device)
+        _lib.call("ds2_bn_relu_bwd", dy.data_ptr(), y.data_ptr(), x2d.data_ptr(), r, c,
+                  mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                  dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), ws.numel(),
+                  _stream())
+        return dx, dgamma, dbeta, None, None, None, None, None

@@ -32,17 +32,27 @@ class FlatParams:
 
     ALIGN = 64  # elements; keeps every view 256-byte aligned
 
-    def __init__(self, params: List[torch.nn.Parameter], device, adjacent=(), tail: int = 0):
+    def __init__(self, params: List[torch.nn.Parameter], device, adjacent=(), tail: int = 0,
+                 unused=()):
         """adjacent: (first, second) parameter pairs laid out back to back (first, then
         second, no padding between when first fills whole 64-element blocks) -- a
         bidirectional recurrent layer's W_ih of both directions, so its input projection,
         dX and dW_ih GEMMs run as one GEMM over both directions (ops._stacked_rows).
         tail: extra fp32 slots after the last parameter's gradient (``self.tail``), outside
         ``numel`` (no norm, clip or update touches them): the step's status word and loss ride
-        in the last all-reduce bucket there (GradAllReducer, status_slots)."""
+        in the last all-reduce bucket there (GradAllReducer, status_slots).
+        unused: parameters no forward reads (model.unused_parameters()).  They keep their own
+        storage and ``.grad is None``, outside the flat buffers, so no update -- weight decay
+        included -- touches them, as torch's optimizers skip a parameter without a gradient;
+        they keep their place in ``model_params`` (the state_dict's parameter order)."""
         params = [p for p in params if p.requires_grad]
         self.model_params = params                 # model.parameters() order
-        order = list(reversed(params))             # backward-completion order
+        skip = {id(p) for p in unused}
+        self.unused = [p for p in params if id(p) in skip]
+        for p in self.unused:
+            p.data = p.data.to(device)
+            p.grad = None
+        order = [p for p in reversed(params) if id(p) not in skip]   # backward-completion order
         second_of = {id(a): b for a, b in adjacent}
         seconds = {id(b) for _, b in adjacent}
         first_of = {id(b): a for a, b in adjacent}
@@ -165,7 +175,7 @@ class FusedSGD:
     def _model_order(self):
         """(param, flat offset) in the reference optimizer's order: model.parameters()
         (build_optimizer(args, model.parameters()), train.py:139-152, 939)."""
-        return [(p, self.flat.offset_of[id(p)]) for p in self.flat.model_params]
+        return [(p, self.flat.offset_of.get(id(p))) for p in self.flat.model_params]
 
     def _group_defaults(self):
         # the installed torch's own SGD param_group keys, so the dict loads into
@@ -187,6 +197,8 @@ class FusedSGD:
         state = {}
         if self.steps > 0:
             for i, (p, o) in enumerate(order):
+                if o is None:      # never stepped (no gradient): torch keeps no state for it
+                    continue
                 state[i] = {'momentum_buffer': self.buf[o:o + p.numel()].detach().view_as(p)
                             .cpu().clone()}
         group = self._group_defaults()
@@ -230,6 +242,8 @@ class FusedSGD:
             if mb is None:
                 continue
             p, o = order[slot]
+            if o is None:
+                continue
             if tuple(mb.shape) != tuple(p.shape):
                 raise ValueError(f"momentum_buffer {idx}: shape {tuple(mb.shape)} != parameter "
                                  f"{tuple(p.shape)}")
@@ -298,7 +312,7 @@ class FusedAdam:
 
     # ---- torch.optim.Adam's state_dict format (model.py:446 optim_dict; train.py:843) ----
     def _model_order(self):
-        return [(p, self.flat.offset_of[id(p)]) for p in self.flat.model_params]
+        return [(p, self.flat.offset_of.get(id(p))) for p in self.flat.model_params]
 
     def _group_defaults(self):
         # the installed torch's own Adam param_group keys, so the dict loads into
@@ -319,6 +333,8 @@ class FusedAdam:
         state = {}
         if t > 0:
             for i, (p, o) in enumerate(order):
+                if o is None:      # never stepped (no gradient): torch keeps no state for it
+                    continue
                 n = p.numel()
                 state[i] = {'step': torch.tensor(float(t), dtype=torch.float32),
                             'exp_avg': self.exp_avg[o:o + n].detach().view_as(p).cpu().clone(),
@@ -353,9 +369,10 @@ class FusedAdam:
                              f"has amsgrad={g.get('amsgrad')}, maximize={g.get('maximize')}, "
                              f"decoupled_weight_decay={g.get('decoupled_weight_decay')}")
         state = sd['state']
-        have = [idx for idx in g['params'] if state.get(idx)]
-        if have and len(have) != len(order):
-            raise ValueError(f"state for {len(have)} of {len(order)} parameters: Adam keeps "
+        active = [idx for idx, (_, o) in zip(g['params'], order) if o is not None]
+        have = [idx for idx in active if state.get(idx)]
+        if have and len(have) != len(active):
+            raise ValueError(f"state for {len(have)} of {len(active)} parameters: Adam keeps "
                              "either none (no step taken) or all")
         steps, moments = set(), []
         for slot, idx in enumerate(g['params']):
@@ -366,6 +383,8 @@ class FusedAdam:
                 raise ValueError(f"param {idx}: Adam state keys {sorted(self._STATE_KEYS)} "
                                  f"expected, got {sorted(st)}")
             p, o = order[slot]
+            if o is None:
+                continue
             for key in ('exp_avg', 'exp_avg_sq'):
                 if tuple(st[key].shape) != tuple(p.shape):
                     raise ValueError(f"{key} {idx}: shape {tuple(st[key].shape)} != parameter "

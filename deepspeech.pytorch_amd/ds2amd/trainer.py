@@ -111,10 +111,13 @@ class Trainer:
         # per layer for the input projection, dX and dW_ih (ops._stacked_rows)
         pairs = [(m.weight_ih_l0, m.weight_ih_l0_reverse) for m in self.model.modules()
                  if hasattr(m, 'weight_ih_l0_reverse')]
+        # parameters no forward reads (rnn_type 'cnn': the MaskConv stack) stay out of the
+        # flat buffers: no gradient, no update, no weight decay, as torch's optimizers do
+        unused = self.model.unused_parameters() if hasattr(self.model, 'unused_parameters') else []
         # two tail slots after the gradients: (status word, loss), all-reduced with the last
         # bucket (GradAllReducer.set_status_packer) instead of two collectives of their own
         self.flat = FlatParams(list(self.model.parameters()), self.device, adjacent=pairs,
-                               tail=2 if dist.is_initialized() else 0)
+                               tail=2 if dist.is_initialized() else 0, unused=unused)
         if optimizer == 'sgd':
             self.optimizer = FusedSGD(self.flat, lr=lr, momentum=momentum, max_norm=max_norm,
                                       weight_decay=weight_decay)

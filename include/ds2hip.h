@@ -185,6 +185,75 @@ ds2_status_t ds2_conv2d_wgrad(const float* dy, const float* x, float* dw, float*
                               ds2_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
+/* Conv1d of the Wav2Letter acoustic model (rnn_type 'cnn'): nn.Conv1d semantics, dilation 1,
+ * groups 1, on time-major activations.  ref model.py:518-520 (nn.Conv1d in Wav2Letter's
+ * _block via cuDNN), model.py:233 (the fc Conv1d), called at model.py:351-352.
+ *   x [t][n][c_in] -> y [t_out][n][c_out],  t_out = (t + 2 p - k) / s + 1;  w [c_out][c_in][k]
+ * (torch's layout), bias [c_out] or NULL.  Zero padding is predicated in the loaders.
+ * Default: an implicit GEMM on the fp16x3 matrix-core products (fp32-class accuracy; the
+ * weights are re-laid into the workspace and the operand scales computed there per call);
+ * k = 1, s = 1, p = 0 runs on ds2_sgemm_ws; shapes the implicit GEMM declines (channel
+ * counts below 16, dgrad with s > 1) and DS2_CONV1D=0 run general fp32 FMA kernels.
+ * t == 0 or n == 0: DS2_OK, nothing launched; negative sizes, k or s < 1 and t_out <= 0:
+ * DS2_INVALID_VALUE.  One workspace size serves forward and dgrad.               */
+size_t ds2_conv1d_workspace_size(int t, int n, int c_in, int c_out, int k, int s, int p);
+ds2_status_t ds2_conv1d_fwd(const float* x, const float* w, const float* bias, float* y, int t,
+                            int n, int c_in, int c_out, int k, int s, int p, void* ws,
+                            size_t ws_bytes, ds2_stream_t stream);
+/* The same with the fp16x3 row scales of x supplied by its producer: x_row_amax [t n] = the
+ * float bits of max |x| per row (ds2_amax's format, e.g. from ds2_bn_relu_apply_amax; an upper
+ * bound is valid); NULL = computed here.  Ignored unless the implicit GEMM runs.          */
+ds2_status_t ds2_conv1d_fwd_amax(const float* x, const float* w, const float* bias, float* y,
+                                 int t, int n, int c_in, int c_out, int k, int s, int p,
+                                 const unsigned* x_row_amax, void* ws, size_t ws_bytes,
+                                 ds2_stream_t stream);
+/* dx [t][n][c_in] from dy [t_out][n][c_out] (autograd of model.py:351; overwritten). */
+ds2_status_t ds2_conv1d_dgrad(const float* dy, const float* w, float* dx, int t, int n, int c_in,
+                              int c_out, int k, int s, int p, void* ws, size_t ws_bytes,
+                              ds2_stream_t stream);
+/* dw [c_out][c_in][k] = sum over (t_out, n) of dy * window(x); dbias [c_out] = column sums of
+ * dy (if dbias != NULL).  Both overwritten; deterministic: K = t_out n is split into slabs
+ * whose fp32 partials are summed in a fixed order, as ds2_sgemm_ws does.            */
+size_t ds2_conv1d_wgrad_workspace_size(int t, int n, int c_in, int c_out, int k, int s, int p);
+ds2_status_t ds2_conv1d_wgrad(const float* dy, const float* x, float* dw, float* dbias, int t,
+                              int n, int c_in, int c_out, int k, int s, int p, void* ws,
+                              size_t ws_bytes, ds2_stream_t stream);
+/* x [n][c][t] -> y [t][n][c]: the spectrogram batch [N][1][161][T] (ref model.py:350
+ * x.squeeze(1)) into the time-major layout the Conv1d kernels read, one pass.        */
+ds2_status_t ds2_nct_to_tnc(const float* x, int n, int c, int t, float* y, ds2_stream_t stream);
+/* ds2_conv1d_wgrad with the column maxima of x supplied (x_col_amax [c_in], as above). */
+ds2_status_t ds2_conv1d_wgrad_amax(const float* dy, const float* x, float* dw, float* dbias, int t,
+                                   int n, int c_in, int c_out, int k, int s, int p,
+                                   const unsigned* x_col_amax, void* ws, size_t ws_bytes,
+                                   ds2_stream_t stream);
+/* GLU over channels, x [rows][2 c] -> y [rows][c] = a * sigmoid(b), a the first c channels
+ * (ref model.py:529 GLUModule(dim=1) = F.glu on [N][2C][T]), and its backward dx [rows][2 c]. */
+ds2_status_t ds2_glu_fwd(const float* x, int rows, int c, float* y, ds2_stream_t stream);
+ds2_status_t ds2_glu_bwd(const float* dy, const float* x, int rows, int c, float* dx,
+                         ds2_stream_t stream);
+/* BatchNorm1d apply + ReLU in one pass over [rows][c] (ref model.py:524,527: BatchNorm1d then
+ * ReLU over (N, T) per channel; statistics from ds2_bn_train_stats / ds2_bn_eval_stats with
+ * inner = 1): y = max(gamma (x - mean) invstd + beta, 0).  Backward: dz = dy where y > 0,
+ * then the training-mode BatchNorm backward of ds2_bn_backward (dx, dgamma, dbeta
+ * overwritten; dx may not alias dy).                                               */
+ds2_status_t ds2_bn_relu_apply(const float* x, int rows, int c, const float* mean,
+                               const float* invstd, const float* gamma, const float* beta,
+                               float* y, ds2_stream_t stream);
+/* ds2_bn_relu_apply that also writes the fp16x3 scales of y in the same pass, as
+ * ds2_bn_apply_amax does (same shape conditions: c % 4 == 0, c <= 2048, 16-B aligned
+ * operands, else DS2_UNSUPPORTED_SHAPE): row_amax [rows] for the next Conv1d's forward,
+ * col_amax [c] for its weight gradient.                                              */
+ds2_status_t ds2_bn_relu_apply_amax(const float* x, int rows, int c, const float* mean,
+                                    const float* invstd, const float* gamma, const float* beta,
+                                    float* y, unsigned* row_amax, unsigned* col_amax,
+                                    ds2_stream_t stream);
+size_t ds2_bn_relu_bwd_workspace_size(int rows, int c);
+ds2_status_t ds2_bn_relu_bwd(const float* dy, const float* y, const float* x, int rows, int c,
+                             const float* mean, const float* invstd, const float* gamma,
+                             const float* beta, float* dx, float* dgamma, float* dbeta, void* ws,
+                             size_t ws_bytes, ds2_stream_t stream);
+
+/* ------------------------------------------------------------------------ */
 /* BatchNorm (training statistics), x viewed as [outer][c][inner].
  * ref model.py:210,213 (BatchNorm2d), model.py:89,336 (SequenceWise BatchNorm1d).
  * Batch statistics include padded (zeroed) positions, as in the reference.

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("DS2_LIB_PATH") or os.path.join(_HERE, "libds2hip.so")
 
 _c_int = ctypes.c_int
 _c_i64 = ctypes.c_int64
+_c_u64 = ctypes.c_uint64
 _c_f = ctypes.c_float
 _vp = ctypes.c_void_p
 _sz = ctypes.c_size_t
@@ -70,6 +71,12 @@ _PROTOS = {
     "ds2_bn_relu_bwd_workspace_size": (_sz, [_c_int, _c_int]),
     "ds2_bn_relu_bwd": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                  _vp, _sz, _vp]),
+    # dropout of the Wav2Letter blocks (ref model.py:535-536); seed / offset are uint64
+    "ds2_dropout_apply": (_c_int, [_vp, _c_int, _c_int, _c_f, _c_u64, _c_u64, _vp, _vp]),
+    "ds2_bn_dropout_apply_amax": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_int, _c_f,
+                                           _c_u64, _c_u64, _vp, _vp, _vp, _vp]),
+    "ds2_bn_relu_dropout_bwd": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_f,
+                                         _vp, _vp, _vp, _vp, _sz, _vp]),
     "ds2_bn_workspace_size": (_sz, [_c_int, _c_int, _c_int]),
     "ds2_bn_train_stats": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_f, _c_f, _vp, _vp, _vp, _vp,
                                     _vp, _sz, _vp]),

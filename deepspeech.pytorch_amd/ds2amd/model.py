@@ -448,11 +448,26 @@ class DeepSpeech(nn.Module):
     def _forward_cnn(self, x):
         """model.py:350-353 on the time-major layout: [N,1,161,T] -> logits [T',N,C].  No
         length masking anywhere, as in the reference: padded frames enter the convolutions
-        and the BatchNorm statistics.  A BatchNorm1d followed by ReLU runs as one pass."""
+        and the BatchNorm statistics.  A BatchNorm1d followed by ReLU runs as one pass.
+
+        dropout > 0 (model.py:535-536): the nn.Dropout modules stay where the reference puts
+        them; in training mode a BatchNorm1d [+ ReLU] + Dropout runs as one HIP pass that also
+        keeps the next Conv1d's operand scales, a Dropout anywhere else as ops.DropoutFn, and in
+        eval mode it is skipped (no launch, no generator offset consumed).  The masks come
+        from a Philox stream keyed by torch's CUDA generator (ops.dropout_rng), so
+        torch.manual_seed and the saved RNG state reproduce them, but under a given seed they
+        are not the masks torch's native dropout kernel draws.  DS2_DROPOUT=0 runs torch's
+        nn.Dropout instead."""
         if x.dim() != 4 or x.size(1) != 1:
             raise ValueError("DeepSpeech(rnn_type='cnn') expects x [N, 1, 161, T]")
         x = ops.nct_to_tnc(x.detach().reshape(x.size(0), x.size(2), x.size(3)))
         mods = list(self.rnns) + list(self.fc)
+        hip_drop = ops.dropout_enabled()
+
+        def live(j):     # a Dropout at j that draws a mask in this forward, on the HIP path
+            return (hip_drop and j < len(mods) and isinstance(mods[j], nn.Dropout)
+                    and mods[j].training and mods[j].p > 0)
+
         i = 0
         while i < len(mods):
             m = mods[i]
@@ -460,12 +475,20 @@ class DeepSpeech(nn.Module):
                 t, n, c = x.shape
                 relu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
                 fn = ops.BNReLUFn if relu else ops.SeqBatchNormFn
-                x = fn.apply(x.reshape(t * n, c), *_bn_args(m)).view(t, n, c)
                 i += 2 if relu else 1
+                drop = None
+                if live(i):
+                    drop = (float(mods[i].p),) + ops.dropout_rng(x.device)
+                    i += 1
+                x = fn.apply(x.reshape(t * n, c), *_bn_args(m), drop).view(t, n, c)
                 continue
             if isinstance(m, nn.ReLU):
                 raise ValueError("rnn_type 'cnn': a ReLU that does not follow a BatchNorm1d")
-            x = m(x)           # Conv1d / GLUModule (HIP); nn.Dropout (torch, only if dropout > 0)
+            if isinstance(m, nn.Dropout) and hip_drop:
+                if live(i):
+                    x = ops.DropoutFn.apply(x, float(m.p), *ops.dropout_rng(x.device))
+            else:
+                x = m(x)       # Conv1d / GLUModule (HIP); nn.Dropout (torch) under DS2_DROPOUT=0
             i += 1
         return x
 

@@ -453,6 +453,74 @@ def bn_apply_amax(x, rows, c, mean, invstd, gamma, beta):
     return y
 
 
+def dropout_enabled() -> bool:
+    """DS2_DROPOUT=0 keeps torch's nn.Dropout in the Wav2Letter forward (the path before the
+    HIP dropout kernels; the A/B of scripts/bench_w2l.py --dropout)."""
+    return os.environ.get("DS2_DROPOUT", "1") != "0"
+
+
+def dropout_rng(device):
+    """(seed, offset) for one dropout mask, taken from torch's generator of ``device`` as its
+    own Philox kernels take theirs: the offset advances by 4, so torch.manual_seed,
+    torch.cuda.get_rng_state / set_rng_state and a checkpoint resume reproduce the masks."""
+    if torch.cuda.is_current_stream_capturing():
+        raise _lib.Ds2Error("dropout_rng: the generator's offset cannot be read under stream "
+                            "capture; run the dropout forward outside the captured region")
+    device = torch.device(device)
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    torch.cuda.init()
+    gen = torch.cuda.default_generators[idx]
+    try:
+        seed = int(gen.initial_seed()) & 0xFFFFFFFFFFFFFFFF
+        offset = int(gen.get_offset())
+        gen.set_offset(offset + 4)
+    except (RuntimeError, AttributeError) as e:
+        raise _lib.Ds2Error(f"dropout_rng: torch's generator of cuda:{idx} does not expose its "
+                            f"Philox offset ({e}); not reseeding silently") from e
+    return seed, offset
+
+
+def dropout_apply(x, p: float, seed: int, offset: int, out=None):
+    """x with the (seed, offset) Philox mask of ds2hip.h applied and the survivors scaled by
+    1 / (1 - p) (ds2_dropout_apply); the backward is the same call on dy.  out may be x."""
+    x = _need(x, "dropout.x")
+    y = torch.empty_like(x) if out is None else out
+    c = x.shape[-1] if x.dim() else 1
+    rows = x.numel() // c if c else 0
+    _lib.call("ds2_dropout_apply", x.data_ptr(), rows, c, float(p), seed, offset, y.data_ptr(),
+              _stream())
+    return y
+
+
+def _amax_shape_ok(r, c, *tensors):
+    """the shape conditions of ds2_bn_apply_amax / ds2_bn_relu_apply_amax / the dropout form"""
+    return c % 4 == 0 and c <= 2048 and r > 0 and not any(t.data_ptr() % 16 for t in tensors)
+
+
+def bn_dropout_apply_amax(x2d, mean, invstd, gamma, beta, relu: bool, drop):
+    """BatchNorm apply [+ ReLU] + dropout (drop = (p, seed, offset)) over x2d [R, C].  One pass
+    that also keeps y's row / column maxima for the next Conv1d (ds2_bn_dropout_apply_amax);
+    where its shape conditions fail, the unfused apply followed by ds2_dropout_apply."""
+    r, c = x2d.shape
+    p, seed, offset = drop
+    y = torch.empty_like(x2d)
+    if _amax_shape_ok(r, c, x2d, y, mean, invstd, gamma, beta):
+        rmax = torch.empty(r, dtype=_I32, device=x2d.device)
+        cmax = torch.empty(c, dtype=_I32, device=x2d.device)
+        _lib.call("ds2_bn_dropout_apply_amax", x2d.data_ptr(), r, c, mean.data_ptr(),
+                  invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), int(relu), float(p), seed,
+                  offset, y.data_ptr(), rmax.data_ptr(), cmax.data_ptr(), _stream())
+        _tag_amax(y, r, c, rmax, cmax)
+        return y
+    if relu:
+        _lib.call("ds2_bn_relu_apply", x2d.data_ptr(), r, c, mean.data_ptr(), invstd.data_ptr(),
+                  gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), _stream())
+    else:
+        _lib.call("ds2_bn_apply", x2d.data_ptr(), r, c, 1, mean.data_ptr(), invstd.data_ptr(),
+                  gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), _stream())
+    return dropout_apply(y, p, seed, offset, out=y)
+
+
 def bn_backward(dy, dy_layout, x, outer, c, d, t, mean, invstd, gamma, beta, masked=False,
                 lens=None, lo=0.0, hi=20.0, want_dbias=False, bias=None):
     """dgamma / dbeta (/ dbias of the preceding conv) land in the parameters' gradient
@@ -813,18 +881,25 @@ class ConvBlockFn(torch.autograd.Function):
 
 
 class SeqBatchNormFn(torch.autograd.Function):
-    """SequenceWise(BatchNorm1d) on x viewed [R, C] (model.py:28-43, 89, 336)."""
+    """SequenceWise(BatchNorm1d) on x viewed [R, C] (model.py:28-43, 89, 336).  drop =
+    (p, seed, offset): the nn.Dropout after it (Wav2Letter's GLU form, model.py:535-536) in the
+    same pass; its backward regenerates the mask on dy."""
 
     @staticmethod
-    def forward(ctx, x2d, gamma, beta, running_mean, running_var, training, momentum, eps):
+    def forward(ctx, x2d, gamma, beta, running_mean, running_var, training, momentum, eps,
+                drop=None):
         x2d = x2d.contiguous()
         r, c = x2d.shape
         mean, invstd = bn_stats(x2d, r, c, 1, eps, momentum, running_mean, running_var, training)
-        # with the fp16x3 GEMMs, y's row / column maxima for the input projection and dW_ih
-        y = (bn_apply_amax(x2d, r, c, mean, invstd, gamma, beta) if h3_enabled()
-             else bn_apply(x2d, r, c, 1, mean, invstd, gamma, beta))
+        if drop is not None:
+            y = bn_dropout_apply_amax(x2d, mean, invstd, gamma, beta, False, drop)
+        else:
+            # with the fp16x3 GEMMs, y's row / column maxima for the input projection and dW_ih
+            y = (bn_apply_amax(x2d, r, c, mean, invstd, gamma, beta) if h3_enabled()
+                 else bn_apply(x2d, r, c, 1, mean, invstd, gamma, beta))
         ctx.save_for_backward(x2d, gamma, beta, mean, invstd)
         ctx.training = training
+        ctx.drop = drop
         return y
 
     @staticmethod
@@ -833,9 +908,11 @@ class SeqBatchNormFn(torch.autograd.Function):
         if not ctx.training:
             raise _lib.Ds2Error("SeqBatchNormFn backward in eval mode is not supported")
         r, c = x2d.shape
-        dx, dgamma, dbeta, _ = bn_backward(dy.contiguous(), 0, x2d, r, c, 1, 1, mean, invstd,
-                                           gamma, beta)
-        return dx.view(r, c), dgamma, dbeta, None, None, None, None, None
+        dy = dy.contiguous()
+        if ctx.drop is not None:
+            dy = dropout_apply(dy, *ctx.drop)
+        dx, dgamma, dbeta, _ = bn_backward(dy, 0, x2d, r, c, 1, 1, mean, invstd, gamma, beta)
+        return dx.view(r, c), dgamma, dbeta, None, None, None, None, None, None
 
 
 class LinearFn(torch.autograd.Function):
@@ -1435,13 +1512,22 @@ class GLUFn(torch.autograd.Function):
 
 class BNReLUFn(torch.autograd.Function):
     """BatchNorm1d over (N, T) then ReLU on x viewed [R, C] (model.py:524, 527), one apply
-    pass; backward = ReLU mask + BatchNorm backward (ds2_bn_relu_bwd)."""
+    pass; backward = ReLU mask + BatchNorm backward (ds2_bn_relu_bwd).  drop = (p, seed,
+    offset): the nn.Dropout after the ReLU (model.py:535-536) in the same pass; the backward
+    reads "active and kept" off the stored output (ds2_bn_relu_dropout_bwd)."""
 
     @staticmethod
-    def forward(ctx, x2d, gamma, beta, running_mean, running_var, training, momentum, eps):
+    def forward(ctx, x2d, gamma, beta, running_mean, running_var, training, momentum, eps,
+                drop=None):
         x2d = x2d.contiguous()
         r, c = x2d.shape
         mean, invstd = bn_stats(x2d, r, c, 1, eps, momentum, running_mean, running_var, training)
+        ctx.training = training
+        ctx.drop = drop
+        if drop is not None:
+            y = bn_dropout_apply_amax(x2d, mean, invstd, gamma, beta, True, drop)
+            ctx.save_for_backward(x2d, y, gamma, beta, mean, invstd)
+            return y
         y = torch.empty_like(x2d)
         ptrs = (x2d.data_ptr(), y.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
                 gamma.data_ptr(), beta.data_ptr())
@@ -1457,7 +1543,6 @@ class BNReLUFn(torch.autograd.Function):
                       invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(),
                       _stream())
         ctx.save_for_backward(x2d, y, gamma, beta, mean, invstd)
-        ctx.training = training
         return y
 
     @staticmethod
@@ -1471,8 +1556,28 @@ class BNReLUFn(torch.autograd.Function):
         dgamma = grad_like(gamma)
         dbeta = grad_like(beta)
         ws = _ws(_lib.size("ds2_bn_relu_bwd_workspace_size", r, c), x2d.device)
-        _lib.call("ds2_bn_relu_bwd", dy.data_ptr(), y.data_ptr(), x2d.data_ptr(), r, c,
-                  mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                  dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), ws.numel(),
-                  _stream())
-        return dx, dgamma, dbeta, None, None, None, None, None
+        if ctx.drop is not None:
+            _lib.call("ds2_bn_relu_dropout_bwd", dy.data_ptr(), y.data_ptr(), x2d.data_ptr(), r,
+                      c, mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                      float(ctx.drop[0]), dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
+                      ws.data_ptr(), ws.numel(), _stream())
+        else:
+            _lib.call("ds2_bn_relu_bwd", dy.data_ptr(), y.data_ptr(), x2d.data_ptr(), r, c,
+                      mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                      dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(),
+                      ws.numel(), _stream())
+        return dx, dgamma, dbeta, None, None, None, None, None, None
+
+
+class DropoutFn(torch.autograd.Function):
+    """nn.Dropout in training mode wherever it does not follow a BatchNorm1d (model.py:535-536
+    in general position): ds2_dropout_apply forward, the same call on dy backward."""
+
+    @staticmethod
+    def forward(ctx, x, p, seed, offset):
+        ctx.drop = (float(p), int(seed), int(offset))
+        return dropout_apply(x, *ctx.drop)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return dropout_apply(dy.contiguous(), *ctx.drop), None, None, None

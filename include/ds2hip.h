@@ -254,6 +254,47 @@ ds2_status_t ds2_bn_relu_bwd(const float* dy, const float* y, const float* x, in
                              size_t ws_bytes, ds2_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
+/* Dropout of the Wav2Letter blocks (ref model.py:535-536: nn.Dropout appended to every block
+ * when --dropout > 0), training mode.  No mask is stored: element i of the row-major
+ * [rows][c] matrix (i = r c + col, 64-bit) is decided by a counter-based stream,
+ *   Philox4x32-10 (multipliers D2511F53 / CD9E8D57, key increments 9E3779B9 / BB67AE85),
+ *   key     = (seed & 0xffffffff, seed >> 32),
+ *   counter = (g & 0xffffffff, g >> 32, offset & 0xffffffff, offset >> 32),  g = i / 4,
+ *   word    = output word i % 4 of that call,
+ *   thr     = floor(p * 2^32) in double;  element i is dropped iff word < thr,
+ * and y[i] = dropped ? 0 : x[i] * scale with scale = 1.0f / (1.0f - p) in float (one float
+ * multiply, torch's formula).  p == 0 is the identity, p == 1 writes zeros.  The same
+ * (seed, offset) gives the same mask on every call, so a backward regenerates it; a caller
+ * advances offset between masks (ds2amd: by 4, torch's generator granularity).  These masks
+ * are not the ones torch's native dropout draws under the same seed.
+ * Every entry: p outside [0, 1] or NaN and negative sizes are DS2_INVALID_VALUE before any
+ * HIP call; rows == 0 or c == 0 is DS2_OK with nothing launched.                        */
+/* y = dropout(x), any c and alignment (y may alias x).  The backward is the same call on dy.
+ * ref model.py:535-536.                                                                  */
+ds2_status_t ds2_dropout_apply(const float* x, int rows, int c, float p, uint64_t seed,
+                               uint64_t offset, float* y, ds2_stream_t stream);
+/* BatchNorm1d apply [+ ReLU if relu != 0] + dropout in one pass, with the fp16x3 scales of
+ * the y it stored (row_amax [rows], col_amax [c]) as ds2_bn_relu_apply_amax /
+ * ds2_bn_apply_amax write them: y = dropout(act(gamma (x - mean) invstd + beta)), the affine
+ * and ReLU bit for bit those entries'.  Same shape conditions (c % 4 == 0, c <= 2048, 16-B
+ * aligned operands, else DS2_UNSUPPORTED_SHAPE).  ref model.py:535-536 after 524-531.    */
+ds2_status_t ds2_bn_dropout_apply_amax(const float* x, int rows, int c, const float* mean,
+                                       const float* invstd, const float* gamma,
+                                       const float* beta, int relu, float p, uint64_t seed,
+                                       uint64_t offset, float* y, unsigned* row_amax,
+                                       unsigned* col_amax, ds2_stream_t stream);
+/* Backward of the relu != 0 form from its stored output y: y > 0 already means "passed the
+ * ReLU and kept", so dz = dy * scale where y > 0 (else 0), then ds2_bn_backward as
+ * ds2_bn_relu_bwd does (workspace ds2_bn_relu_bwd_workspace_size; dx may not alias dy).
+ * The relu == 0 form's backward is ds2_dropout_apply on dy, then ds2_bn_backward.
+ * ref model.py:535-536.                                                                  */
+ds2_status_t ds2_bn_relu_dropout_bwd(const float* dy, const float* y, const float* x, int rows,
+                                     int c, const float* mean, const float* invstd,
+                                     const float* gamma, const float* beta, float p, float* dx,
+                                     float* dgamma, float* dbeta, void* ws, size_t ws_bytes,
+                                     ds2_stream_t stream);
+
+/* ------------------------------------------------------------------------ */
 /* BatchNorm (training statistics), x viewed as [outer][c][inner].
  * ref model.py:210,213 (BatchNorm2d), model.py:89,336 (SequenceWise BatchNorm1d).
  * Batch statistics include padded (zeroed) positions, as in the reference.

@@ -14,6 +14,13 @@ Achieved TF per kernel comes from a separate profiler run (the profiler slows th
     python scripts/bench_w2l.py --forms relu --kernel-stats DIR/.../w2l_kernel_stats.csv
 --profile runs warm-up + --steps fast-path steps of one form and nothing else; --kernel-stats
 merges that run's per-kernel times (divided by its step count) into the JSON line.
+
+--dropout P (default 0: everything above, unchanged) times the model built with dropout=P
+instead: the HIP dropout fused into the BatchNorm apply pass, DS2_DROPOUT=0 (torch's
+nn.Dropout on the same model) and the dropout-free model, alternating round by round in one
+process; one JSON line per form, appended to --out (default profiles/w2l_dropout_bench.jsonl).
+With --profile the dropout model's steps are followed by as many of the dropout-free model,
+so one trace holds the DROP and the plain instantiation of the apply kernel at one shape.
 """
 from __future__ import annotations
 
@@ -71,11 +78,11 @@ def make_batch(batch, frames, label_len, seed=11):
     return x, tg, tl, pct
 
 
-def build(form, args):
+def build(form, args, dropout=0):
     torch.manual_seed(1)
     m = dsm.DeepSpeech(rnn_type='cnn', labels=LABELS, rnn_hidden_size=args.hidden_size,
                        nb_layers=args.hidden_layers, bidirectional=FORMS[form],
-                       cnn_width=args.cnn_width)
+                       cnn_width=args.cnn_width, dropout=dropout)
     return Trainer(m, LABELS, lr=1e-4, momentum=0.9, max_norm=100.0, device="cuda:0",
                    verbose=False, decode=False)
 
@@ -85,6 +92,13 @@ def set_path(fast: bool):
         os.environ.pop("DS2_CONV1D", None)
     else:
         os.environ["DS2_CONV1D"] = "0"
+
+
+def set_dropout_path(hip: bool):
+    if hip:
+        os.environ.pop("DS2_DROPOUT", None)
+    else:
+        os.environ["DS2_DROPOUT"] = "0"
 
 
 def timed_steps(tr, data, n):
@@ -113,6 +127,45 @@ def summarize(ms):
     return {"ms_per_step": statistics.median(ms), "min": min(ms), "max": max(ms), "rounds": len(ms)}
 
 
+def bench_dropout(args, data):
+    """fused HIP dropout / torch's nn.Dropout (DS2_DROPOUT=0) / the dropout-free model"""
+    out_path = args.out or os.path.join(REPO, "profiles", "w2l_dropout_bench.jsonl")
+    audio_s = args.batch * (args.frames - 1) / 100.0
+    for form in args.forms.split(","):
+        tr_p, tr_0 = build(form, args, args.dropout), build(form, args)
+        legs = (("fused", tr_p, True), ("torch", tr_p, False), ("none", tr_0, True))
+        ms = {name: [] for name, _, _ in legs}
+        for _, tr, hip in legs:
+            set_dropout_path(hip)
+            timed_steps(tr, data, args.warmup)
+        for _ in range(args.rounds):
+            for name, tr, hip in legs:                                # alternating
+                set_dropout_path(hip)
+                ms[name].append(timed_steps(tr, data, args.steps))
+        set_dropout_path(True)
+        tr_p.close()
+        tr_0.close()
+        res = {k: summarize(v) for k, v in ms.items()}
+        for r in res.values():
+            r["audio_s_per_s"] = audio_s / (r["ms_per_step"] / 1e3)
+        gain = res["torch"]["ms_per_step"] - res["fused"]["ms_per_step"]
+        spread = max(r["max"] - r["min"] for r in (res["fused"], res["torch"]))
+        line = json.dumps({
+            "bench": "w2l_dropout_train_step", "form": form, "dropout": args.dropout,
+            "batch": args.batch, "frames": args.frames, "cnn_width": args.cnn_width,
+            "hidden_size": args.hidden_size, "hidden_layers": args.hidden_layers,
+            "steps_per_round": args.steps, "fused": res["fused"],
+            "torch_DS2_DROPOUT_0": res["torch"], "dropout_free": res["none"],
+            "torch_over_fused": res["torch"]["ms_per_step"] / res["fused"]["ms_per_step"],
+            "fused_over_dropout_free": res["fused"]["ms_per_step"] / res["none"]["ms_per_step"],
+            "fused_not_slower": res["fused"]["ms_per_step"] <= res["torch"]["ms_per_step"],
+            "gain_ms": gain, "rounds_spread_ms": spread, "gain_inside_spread": gain <= spread})
+        print(line, flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "a") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawTextHelpFormatter)
     ap.add_argument("--forms", default="relu,glu")
@@ -128,6 +181,8 @@ def main():
     ap.add_argument("--general-steps", type=int, default=12,
                     help="DS2_CONV1D=0 steps per round (about ten times slower per step)")
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--dropout", type=float, default=0.0,
+                    help="P > 0: time the dropout=P model, fused HIP path against DS2_DROPOUT=0")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file")
     ap.add_argument("--profile", metavar="FORM", default=None,
                     help="profiler mode: warm-up + --steps fast-path steps of FORM only")
@@ -139,11 +194,20 @@ def main():
     data = make_batch(args.batch, args.frames, args.label_len)
     if args.profile:
         set_path(True)
-        tr = build(args.profile, args)
+        tr = build(args.profile, args, args.dropout)
         ms = timed_steps(tr, data, args.warmup + args.steps)
-        print(json.dumps({"profile": args.profile, "steps": args.warmup + args.steps,
-                          "ms_per_step_under_profiler": ms}), flush=True)
+        rec = {"profile": args.profile, "steps": args.warmup + args.steps,
+               "ms_per_step_under_profiler": ms}
         tr.close()
+        if args.dropout > 0:      # the dropout-free model next, for the plain apply kernel
+            tr = build(args.profile, args)
+            rec.update(dropout=args.dropout, dropout_path=os.environ.get("DS2_DROPOUT", "1"),
+                       ms_per_step_dropout_free=timed_steps(tr, data, args.warmup + args.steps))
+            tr.close()
+        print(json.dumps(rec), flush=True)
+        return
+    if args.dropout > 0:
+        bench_dropout(args, data)
         return
 
     for form in args.forms.split(","):

@@ -18,7 +18,7 @@
 // Gate math follows ATen's GRU cell (gate rows ordered r, z, n):
 //   r = sigmoid(hr + xr), z = sigmoid(hz + xz), n = tanh(xn + r*hn),
 //   h' = (h - n) * z + n
-#include "rnn_common.h"
+#include "rnn_host.h"
 
 #include <algorithm>
 #include <mutex>
@@ -1046,105 +1046,142 @@ __global__ void gru_db_final_kernel(const double* __restrict__ dbp, int BT, int 
 
 }  // namespace ds2
 
-namespace ds2 {
-// gru_split.hip: the same direct-operand recurrences with the W_hh contraction on the bf16
-// matrix cores at fp32 accuracy (default; DS2_GRU_X6=0 selects the fp32-MFMA kernels above)
-bool launch_gru_fwd_x6(int t_max, int n, int h, int num_dirs, const float* xproj,
-                       const float* w_hh_f, const float* w_hh_r, const float* b_hh_f,
-                       const float* b_hh_r, const int* lens, float* h_all, float* gates,
-                       float* ring, unsigned* ctrs, unsigned* err, unsigned long long* stamps,
-                       size_t lds_pad, hipStream_t st);
-bool launch_gru_bwd_x6(int t_max, int n, int h, int num_dirs, const float* dy, int dy_dirs,
-                       const float* w_hh_f, const float* w_hh_r, const float* h_all,
-                       const float* gates, const int* lens, float* dgates_x, float* dgates_h,
-                       float* ring, unsigned* ctrs, unsigned* err, unsigned long long* stamps,
-                       double* dbp, size_t lds_pad, hipStream_t st, unsigned* camax,
-                       bool* camax_done);
-int gru_bwd_x6_grid(int n, int h, int num_dirs);
-bool launch_rnn_fwd_h3(int t_max, int n, int h, int num_dirs, const float* xproj,
-                       const float* w_hh_f, const float* w_hh_r, const float* b_hh_f,
-                       const float* b_hh_r, const int* lens, float* h_all, float* ring,
-                       unsigned* ctrs, unsigned* err, unsigned long long* stamps, size_t lds_pad,
-                       hipStream_t st);
-bool launch_rnn_bwd_h3(int t_max, int n, int h, int num_dirs, const float* dy, int dy_dirs,
-                       const float* w_hh_f, const float* w_hh_r, const float* h_all,
-                       const int* lens, float* dgates, float* ring, unsigned* ctrs, unsigned* err,
-                       unsigned long long* stamps, size_t lds_pad, hipStream_t st,
-                       unsigned* camax);
-int rnn_h3_grid(int n, int h, int num_dirs);
-// gru_xl.hip: the XCD-local groups (default where the shape fits: 32 units x 8 samples per
-// workgroup, a group of H / 32 workgroups in one XCD)
-int gru_xl_groups(int n, int h, int num_dirs);
-int gru_xl_active(int n, int h, int num_dirs);
-size_t gru_xl_ctr_words();
-bool launch_gru_fwd_xl(int t_max, int n, int h, int num_dirs, const float* xproj,
-                       const float* w_hh_f, const float* w_hh_r, const float* b_hh_f,
-                       const float* b_hh_r, const int* lens, float* h_all, float* gates,
-                       float* ring, unsigned* ctrs, size_t ctr_bytes, unsigned* xl, unsigned* err,
-                       unsigned* err_out, unsigned long long* stamps, size_t lds_pad,
-                       hipStream_t st);
-bool launch_gru_bwd_xl(int t_max, int n, int h, int num_dirs, const float* dy, int dy_dirs,
-                       const float* w_hh_f, const float* w_hh_r, const float* h_all,
-                       const float* gates, const int* lens, float* dgates_x, float* dgates_h,
-                       float* ring, unsigned* ctrs, size_t ctr_bytes, unsigned* xl, unsigned* err,
-                       unsigned* err_out, unsigned long long* stamps, double* dbp, size_t lds_pad,
-                       hipStream_t st, unsigned* camax, float* rowp);
-size_t gru_xl_rowp_bytes(int t_max, int n, int h, int num_dirs);
-void launch_gru_xl_row_amax(int t_max, int n, int h, int num_dirs, const float* rowp,
-                            unsigned* out, hipStream_t st);
-}  // namespace ds2
-
 using namespace ds2;
 
-extern "C" {
+// K = 16-unit blocks per wave (direct-operand, fp32 MFMA) or k-steps per wave (LDS-staged
+// persistent, per-step)
+static const Instance kFwdDop[] = {
+    inst(1, gru_fwd_dop_kernel<1>), inst(2, gru_fwd_dop_kernel<2>), inst(3, gru_fwd_dop_kernel<3>),
+    inst(4, gru_fwd_dop_kernel<4>), inst(5, gru_fwd_dop_kernel<5>), inst(6, gru_fwd_dop_kernel<6>),
+    inst(7, gru_fwd_dop_kernel<7>), inst(8, gru_fwd_dop_kernel<8>)};
+static const Instance kBwdDop[] = {
+    inst(1, gru_bwd_dop_kernel<1>),   inst(2, gru_bwd_dop_kernel<2>),
+    inst(3, gru_bwd_dop_kernel<3>),   inst(4, gru_bwd_dop_kernel<4>),
+    inst(6, gru_bwd_dop_kernel<6>),   inst(8, gru_bwd_dop_kernel<8>),
+    inst(10, gru_bwd_dop_kernel<10>), inst(13, gru_bwd_dop_kernel<13>),
+    inst(16, gru_bwd_dop_kernel<16>), inst(19, gru_bwd_dop_kernel<19>),
+    inst(22, gru_bwd_dop_kernel<22>), inst(24, gru_bwd_dop_kernel<24>)};
+static const Instance kFwdPersist[] = {
+    inst(8, gru_fwd_persist_kernel<8>), inst(16, gru_fwd_persist_kernel<16>),
+    inst(25, gru_fwd_persist_kernel<25>), inst(32, gru_fwd_persist_kernel<32>)};
+static const Instance kBwdPersist[] = {
+    inst(8, gru_bwd_persist_kernel<8>),   inst(16, gru_bwd_persist_kernel<16>),
+    inst(25, gru_bwd_persist_kernel<25>), inst(32, gru_bwd_persist_kernel<32>),
+    inst(48, gru_bwd_persist_kernel<48>), inst(64, gru_bwd_persist_kernel<64>),
+    inst(75, gru_bwd_persist_kernel<75>)};
+static const Instance kFwdStep[] = {
+    inst(8, gru_fwd_step_kernel<8>),   inst(16, gru_fwd_step_kernel<16>),
+    inst(32, gru_fwd_step_kernel<32>), inst(48, gru_fwd_step_kernel<48>),
+    inst(64, gru_fwd_step_kernel<64>), inst(80, gru_fwd_step_kernel<80>),
+    inst(96, gru_fwd_step_kernel<96>)};
+static const Instance kBwdStep[] = {
+    inst(8, gru_bwd_step_kernel<8>),   inst(16, gru_bwd_step_kernel<16>),
+    inst(32, gru_bwd_step_kernel<32>), inst(48, gru_bwd_step_kernel<48>),
+    inst(64, gru_bwd_step_kernel<64>), inst(80, gru_bwd_step_kernel<80>),
+    inst(96, gru_bwd_step_kernel<96>)};
 
-static inline int stamp_mode() {
-  const char* e = getenv("DS2_GRU_STAMPS");
-  return e == nullptr ? 0 : (e[0] == '1' ? 1 : (e[0] == '2' ? 2 : 0));
-}
-// the dynamic LDS of the direct-operand kernels: one workgroup per CU
-constexpr unsigned kDopPadLds = 80 * 1024;
-// smallest instantiated blocks-per-wave >= need (extra blocks are predicated off)
-static const void* bwd_dop_fn(int need) {
-#define DS2_BDOP(K) \
-  if (need <= K) return reinterpret_cast<const void*>(gru_bwd_dop_kernel<K>);
-  DS2_BDOP(1) DS2_BDOP(2) DS2_BDOP(3) DS2_BDOP(4) DS2_BDOP(6) DS2_BDOP(8) DS2_BDOP(10)
-  DS2_BDOP(13) DS2_BDOP(16) DS2_BDOP(19) DS2_BDOP(22) DS2_BDOP(24)
-#undef DS2_BDOP
-  return nullptr;
-}
+// ---------------------------------------------------------------------------------------
+// Workspace layouts.  The counter region, shared by the GRU and one-gate RNN workspaces:
 // group counters, the error word, 64 per-producer flags per group, then 64 per-producer XCC
 // ids per group (the same-XCD groups of gru_split.hip); the XCD-local kernels (gru_xl.hip) use
-// gru_xl_ctr_words() words after the error word instead
-static inline size_t ctr_words(int n, int num_dirs) {
-  const int groups = num_dirs * ((n + GB - 1) / GB);
-  const size_t a = (size_t)groups * 128, b = gru_xl_ctr_words();
-  return (size_t)groups + 1 + (a > b ? a : b);
+// gru_xl_ctr_words() words after the error word instead.  The stamp slots follow.
+static size_t ctr_flag_bytes(const RnnShape& s) {
+  const size_t a = (size_t)s.groups() * 128, b = gru_xl_ctr_words();
+  return align256(((size_t)s.groups() + 1 + std::max(a, b)) * sizeof(unsigned));
 }
-static inline size_t counter_bytes(int n, int num_dirs) {
+static size_t counter_bytes(const RnnShape& s) {
   const size_t trace = stamp_mode() == 2 ? (size_t)kTraceSteps * 1024 * 5 : 16;
-  return align256(ctr_words(n, num_dirs) * sizeof(unsigned)) + trace * sizeof(unsigned long long);
-}
-static inline unsigned long long* stamp_slots(unsigned* ctrs, int n, int num_dirs) {
-  if (stamp_mode() == 0) return nullptr;
-  return reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ctrs) +
-                                               align256(ctr_words(n, num_dirs) * sizeof(unsigned)));
+  return ctr_flag_bytes(s) + trace * sizeof(unsigned long long);
 }
 
 // ring of hand-off tiles for the direct-operand kernels (gates tiles per unit block: 1
 // forward, 3 backward).  Forward: kRingSlots slots of the sentinel ring, doubled for the
 // plainly stored copy the same-XCD groups read.  Backward: 2 slots of the flag hand-off plus
 // the 2 slots of plain copies, tiles sized for the pre-split form (1.5 KB, gru_split.hip).
-static inline size_t ring_bytes(int n, int h, int num_dirs, int tiles) {
-  const size_t UB = (h + GU - 1) / GU, BT = (n + GB - 1) / GB;
+static size_t ring_bytes(const RnnShape& s, int tiles) {
   const size_t tile_floats = tiles == 3 ? 384 : 256;
   const size_t slots = tiles == 3 ? 4 : 2 * kRingSlots;
-  return align256(slots * (size_t)num_dirs * BT * UB * tiles * tile_floats * sizeof(float));
+  return slots * (size_t)s.d * s.BT() * s.UB() * tiles * tile_floats * sizeof(float);
 }
-// every word of the forward's sentinel ring starts as the sentinel
-static inline hipError_t ring_reset(float* ring, int n, int h, int num_dirs, hipStream_t st) {
-  return hipMemsetAsync(ring, 0xFF, ring_bytes(n, h, num_dirs, 1), st);
+
+// The hand-off part of a workspace: counters (with the stamp slots), then the ring.
+struct HandoffLayout {
+  size_t ctrs, ctr_bytes, ring, ring_bytes;
+  void take(Carve& c, const RnnShape& s, int tiles) {
+    ctr_bytes = counter_bytes(s);
+    ring_bytes = align256(::ring_bytes(s, tiles));
+    ctrs = c.take(ctr_bytes);
+    ring = c.take(ring_bytes);
+  }
+  // the Handoff of a launch over the whole batch in 16-sample tiles; `all_stamps`: the
+  // LDS-staged kernels also write the phase stamps of DS2_GRU_STAMPS=1
+  Handoff at(void* ws, const RnnShape& s, unsigned* err_out, bool all_stamps = false) const {
+    unsigned* c = ws_at<unsigned>(ws, ctrs);
+    const bool st = stamp_mode() == 2 || (all_stamps && stamp_mode() == 1);
+    return Handoff{ws_at<float>(ws, ring), c, ctr_bytes, err_word(c, s.groups()), err_out,
+                   st ? ws_at<unsigned long long>(ws, ctrs + ctr_flag_bytes(s)) : nullptr,
+                   kDopPadLds};
+  }
+};
+
+struct GruFwdLayout {
+  size_t wp;   // W_hh in MFMA-fragment order (LDS-staged and per-step kernels)
+  HandoffLayout ho;
+  size_t total;
+};
+static GruFwdLayout gru_fwd_layout(const RnnShape& s) {
+  GruFwdLayout L;
+  Carve c;
+  const int64_t UB = s.UB(), KS = (s.h + 3) / 4;
+  L.wp = c.take((size_t)(s.d * UB * KS * 3 * 64) * sizeof(float));
+  L.ho.take(c, s, 1);
+  c.take(256);
+  L.total = c.end;
+  return L;
 }
+
+struct GruBwdLayout {
+  size_t wpt;   // W_hh^T in MFMA-fragment order
+  size_t dhs;   // the carried dh, two steps
+  HandoffLayout ho;
+  // bias-gradient partial sums [batch tile][direction][4][H] fp64 (8-sample tiles: the
+  // XCD-local kernel's; the 16-sample kernels use the first half)
+  size_t dbp, dbp_bytes;
+  size_t total;      // ds2_gru_bwd_workspace_size
+  size_t rowp;       // the row-maximum partials of dgates_x (ds2_gru_row_amax), = total
+  size_t row_total;  // ds2_gru_row_amax_workspace_size
+};
+static GruBwdLayout gru_bwd_layout(const RnnShape& s) {
+  GruBwdLayout L;
+  Carve c;
+  const int64_t UB = s.UB(), KS = (3 * s.h + 3) / 4;
+  L.wpt = c.take((size_t)(s.d * UB * KS * 64) * sizeof(float));
+  L.dhs = c.take((size_t)2 * s.n * s.d * s.h * sizeof(float));
+  L.ho.take(c, s, 3);
+  c.take(512);
+  L.dbp_bytes = align256((size_t)((s.n + 7) / 8) * s.d * 4 * s.h * sizeof(double));
+  L.dbp = c.take(L.dbp_bytes);
+  L.total = c.end;
+  L.rowp = c.take(gru_xl_rowp_bytes(s.t, s.n, s.h, s.d));
+  L.row_total = c.end;
+  return L;
+}
+
+// the one-gate RNN: only the hand-off part (ring tiles: 1 forward, 3 backward)
+struct RnnLayout {
+  HandoffLayout ho;
+  size_t total;
+};
+static RnnLayout rnn_layout(const RnnShape& s, int tiles) {
+  RnnLayout L;
+  Carve c;
+  L.ho.take(c, s, tiles);
+  c.take(256);
+  L.total = c.end;
+  return L;
+}
+
+extern "C" {
 
 // the gate cache: [T][N][D][4H] (r, z, n, W_hn h + b_hn)
 size_t ds2_gru_cache_floats(int t_max, int n, int h, int num_dirs) {
@@ -1153,28 +1190,13 @@ size_t ds2_gru_cache_floats(int t_max, int n, int h, int num_dirs) {
 }
 
 size_t ds2_gru_fwd_workspace_size(int n, int h, int num_dirs) {
-  const int64_t UB = (h + GU - 1) / GU;
-  const int64_t KS = (h + 3) / 4;
-  return align256((size_t)(num_dirs * UB * KS * 3 * 64) * sizeof(float)) +
-         align256(counter_bytes(n, num_dirs)) + ring_bytes(n, h, num_dirs, 1) + 256;
+  return gru_fwd_layout(RnnShape{0, n, h, num_dirs}).total;
 }
 
-#define DS2_FWD_CASE(K)                                                                    \
-  case K:                                                                                  \
-    hipLaunchKernelGGL(gru_fwd_step_kernel<K>, dim3(grid), dim3(GT), 0, st, s, t_max, n, h, \
-                       num_dirs, UB, BT, xproj, wp, b_hh_f, b_hh_r, lens, h_all, gates);    \
-    break;
-
-static int pick_ksw(int per) {
-  const int opts[] = {8, 16, 32, 48, 64, 80, 96};
-  for (int k : opts)
-    if (per <= k) return k;
-  return -1;
-}
-
-// Kernel choice (forward and backward alike): the direct-operand persistent kernels where
-// H % 16 == 0 and the grid fits the chip -- bf16x6 (gru_split.hip) by default, the fp32-MFMA
-// forms with DS2_GRU_X6=0 --, else the LDS-staged persistent kernels (H % 4 == 0), else one
+// Kernel choice (forward and backward alike; DESIGN.md "Recurrent dispatch"): where
+// H % 16 == 0 and the grid fits the chip, the XCD-local kernels (gru_xl.hip), then the 16-unit
+// fp16x3 / bf16x6 kernels (gru_split.hip), then the fp32-MFMA direct-operand kernels
+// (DS2_GRU_X6=0 selects them); else the LDS-staged persistent kernels (H % 4 == 0), else one
 // launch per step (also DS2_RNN_PERSISTENT=0).
 ds2_status_t ds2_gru_fwd(int t_max, int n, int h, int num_dirs, const float* xproj,
                          const float* w_hh_f, const float* w_hh_r, const float* b_hh_f,
@@ -1183,8 +1205,9 @@ ds2_status_t ds2_gru_fwd(int t_max, int n, int h, int num_dirs, const float* xpr
   if (t_max < 0 || n < 0 || h < 1 || (num_dirs != 1 && num_dirs != 2)) return DS2_INVALID_VALUE;
   if (h > KC_FWD) return DS2_UNSUPPORTED_SHAPE;
   if (t_max == 0 || n == 0) return DS2_OK;
-  if (ws == nullptr || ws_bytes < ds2_gru_fwd_workspace_size(n, h, num_dirs))
-    return DS2_WORKSPACE_TOO_SMALL;
+  const RnnShape s = {t_max, n, h, num_dirs};
+  const GruFwdLayout L = gru_fwd_layout(s);
+  if (ws == nullptr || ws_bytes < L.total) return DS2_WORKSPACE_TOO_SMALL;
   if (num_dirs == 1) {
     w_hh_r = w_hh_f;
     b_hh_r = b_hh_f;
@@ -1192,115 +1215,60 @@ ds2_status_t ds2_gru_fwd(int t_max, int n, int h, int num_dirs, const float* xpr
   hipStream_t st = as_stream(stream);
   apply_spin_limit_env();
   apply_rnn_tune_env();
-  const int UB = (h + GU - 1) / GU;
+  int T = t_max, N = n, H = h, D = num_dirs, UB = s.UB(), BT = s.BT();
   const int KS = (h + 3) / 4;
-  const int BT = (n + GB - 1) / GB;
-  const int ksw = pick_ksw((KS + GW - 1) / GW);
-  if (ksw < 0) return DS2_UNSUPPORTED_SHAPE;
-  float* wp = static_cast<float*>(ws);
+  const void* step_fn = pick_instance(kFwdStep, (KS + GW - 1) / GW);
+  if (step_fn == nullptr) return DS2_UNSUPPORTED_SHAPE;
+  float* wp = ws_at<float>(ws, L.wp);
   const int grid = mapped_grid(UB * num_dirs, BT);
-  const bool persistent = persistent_enabled() && grid <= num_cus() &&
-                          (int64_t)t_max * n * num_dirs * h * 4 < (1ll << 31);
-  unsigned* ctrs = reinterpret_cast<unsigned*>(
-      static_cast<char*>(ws) + align256((size_t)num_dirs * UB * KS * 3 * 64 * sizeof(float)));
-  unsigned* err = ctrs + num_dirs * BT;
+  const bool persistent = persistent_enabled() && grid <= num_cus() && s.fits32(1);
+  ds2_status_t rc = DS2_OK;
   if (persistent && (h % GU) == 0 && UB <= 8 * GW) {
-    int T_ = t_max, N_ = n, H_ = h, D_ = num_dirs, UB_ = UB, BT_ = BT;
-    unsigned long long* stamps = stamp_mode() == 2 ? stamp_slots(ctrs, n, num_dirs) : nullptr;
-    float* ring = reinterpret_cast<float*>(reinterpret_cast<char*>(ctrs) +
-                                           align256(counter_bytes(n, num_dirs)));
-    void* args[] = {&T_, &N_, &H_, &D_, &UB_, &BT_, &xproj, &w_hh_f, &w_hh_r, &b_hh_f,
-                    &b_hh_r, &lens, &h_all, &gates, &ring, &ctrs, &err, &stamps};
+    const RecFwd a = {xproj, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lens, h_all, nullptr, gates};
+    Handoff ho = L.ho.at(ws, s, err_out);
     // the XCD-local launch prepares the counters and its part of the ring itself and reports
     // into err_out from the kernel: no fills and no fold launch around it
-    if (launch_gru_fwd_xl(t_max, n, h, num_dirs, xproj, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lens,
-                          h_all, gates, ring, ctrs, counter_bytes(n, num_dirs), err + 1, err,
-                          err_out, stamps, kDopPadLds, st))
-      return launch_status("ds2_gru_fwd");
+    if (launch_gru_fwd_xl(s, a, ho, st)) return launch_status("ds2_gru_fwd");
     (void)hipGetLastError();
-    if (hipMemsetAsync(ctrs, 0, counter_bytes(n, num_dirs), st) != hipSuccess)
-      return launch_status("ds2_gru counters");
-    if (ring_reset(ring, n, h, num_dirs, st) != hipSuccess) return launch_status("ds2_gru ring");
-    if (launch_gru_fwd_x6(t_max, n, h, num_dirs, xproj, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lens,
-                          h_all, gates, ring, ctrs, err, stamps, kDopPadLds, st)) {
-      fold_err(err, err_out, st);
-      return launch_status("ds2_gru_fwd");
-    }
-    (void)hipGetLastError();
-    const void* fn = nullptr;
-#define DS2_FDOP(K) \
-  case K: fn = reinterpret_cast<const void*>(gru_fwd_dop_kernel<K>); break;
-    switch ((UB + GW - 1) / GW) {
-      DS2_FDOP(1) DS2_FDOP(2) DS2_FDOP(3) DS2_FDOP(4) DS2_FDOP(5) DS2_FDOP(6) DS2_FDOP(7)
-      DS2_FDOP(8)
-      default: break;
-    }
-#undef DS2_FDOP
+    if (rung("ds2_gru_fwd", ho, true, L.ho.ring_bytes, st, &rc,
+             [&] { return launch_fwd16(3, s, a, ho, st); }))
+      return rc;
     // the dynamic LDS keeps one workgroup per CU (every workgroup gets a whole CU's SIMDs)
-    if (fn != nullptr &&
-        rnn_launch(fn, dim3(grid), dim3(GT), args, kDopPadLds, st) == hipSuccess) {
-      fold_err(err, err_out, st);
-      return launch_status("ds2_gru_fwd");
-    }
-    (void)hipGetLastError();
+    void* args[] = {&T, &N, &H, &D, &UB, &BT, &xproj, &w_hh_f, &w_hh_r, &b_hh_f,
+                    &b_hh_r, &lens, &h_all, &gates, &ho.ring, &ho.ctrs, &ho.err, &ho.stamps};
+    const void* fn = pick_instance(kFwdDop, (UB + GW - 1) / GW);
+    if (rung("ds2_gru_fwd", ho, false, 0, st, &rc,
+             [&] { return launch_fn(fn, grid, GT, args, kDopPadLds, st); }))
+      return rc;
   }
   hipLaunchKernelGGL(pack_fwd_kernel<3>, dim3(grid_cap((int64_t)num_dirs * UB * KS * 192)),
                      dim3(256), 0, st, w_hh_f, w_hh_r, h, num_dirs, UB, KS, wp);
   if (persistent && (h % 4) == 0) {
-    if (hipMemsetAsync(ctrs, 0, counter_bytes(n, num_dirs), st) != hipSuccess)
-      return launch_status("ds2_gru counters");
-    int T_ = t_max, N_ = n, H_ = h, D_ = num_dirs, UB_ = UB, BT_ = BT;
-    unsigned long long* stamps = stamp_slots(ctrs, n, num_dirs);
-    int trace_ = stamp_mode() == 2 ? 1 : 0;
-    void* args[] = {&T_, &N_, &H_, &D_, &UB_, &BT_, &xproj, &wp, &b_hh_f, &b_hh_r, &lens,
-                    &h_all, &gates, &ctrs, &err, &stamps, &trace_};
-    const void* fn = nullptr;
-    const int kp = persist_ksw((KS + GW - 1) / GW, KC_FWD);
-    switch (kp) {
-      case 8: fn = reinterpret_cast<const void*>(gru_fwd_persist_kernel<8>); break;
-      case 16: fn = reinterpret_cast<const void*>(gru_fwd_persist_kernel<16>); break;
-      case 25: fn = reinterpret_cast<const void*>(gru_fwd_persist_kernel<25>); break;
-      case 32: fn = reinterpret_cast<const void*>(gru_fwd_persist_kernel<32>); break;
-      default: break;
-    }
-    if (fn != nullptr &&
-        rnn_launch(fn, dim3(grid), dim3(GT), args, 0, st) == hipSuccess) {
-      fold_err(err, err_out, st);
-      return launch_status("ds2_gru_fwd");
-    }
-    (void)hipGetLastError();   // fall back to one launch per step
+    Handoff ho = L.ho.at(ws, s, err_out, true);
+    int trace = stamp_mode() == 2 ? 1 : 0;
+    void* args[] = {&T, &N, &H, &D, &UB, &BT, &xproj, &wp, &b_hh_f, &b_hh_r, &lens,
+                    &h_all, &gates, &ho.ctrs, &ho.err, &ho.stamps, &trace};
+    const void* fn = pick_instance(kFwdPersist, persist_ksw((KS + GW - 1) / GW, KC_FWD));
+    if (rung("ds2_gru_fwd", ho, true, 0, st, &rc,
+             [&] { return launch_fn(fn, grid, GT, args, 0, st); }))
+      return rc;   // else one launch per step
   }
-  for (int s = 0; s < t_max; ++s) {
-    switch (ksw) {
-      DS2_FWD_CASE(8) DS2_FWD_CASE(16) DS2_FWD_CASE(32) DS2_FWD_CASE(48) DS2_FWD_CASE(64)
-      DS2_FWD_CASE(80) DS2_FWD_CASE(96)
-    }
-  }
+
+  int step = 0;
+  void* args[] = {&step, &T, &N, &H, &D, &UB, &BT, &xproj, &wp, &b_hh_f, &b_hh_r, &lens,
+                  &h_all, &gates};
+  for (step = 0; step < t_max; ++step)
+    (void)hipLaunchKernel(step_fn, dim3(grid), dim3(GT), args, 0, st);
   return launch_status("ds2_gru_fwd");
 }
 
-static size_t gru_bwd_ws_base(int n, int h, int num_dirs) {
-  const int64_t UB = (h + GU - 1) / GU;
-  const int64_t KS = (3 * h + 3) / 4;
-  return align256((size_t)(num_dirs * UB * KS * 64) * sizeof(float)) +
-         align256((size_t)2 * n * num_dirs * h * sizeof(float)) +
-         align256(counter_bytes(n, num_dirs)) + ring_bytes(n, h, num_dirs, 3) + 512;
-}
-
-// bias-gradient partial sums [batch tile][direction][4][H] fp64, at the end of the workspace
-// (8-sample tiles: the XCD-local kernel's; the 16-sample kernels use the first half)
-static size_t gru_db_bytes(int n, int h, int num_dirs) {
-  return align256((size_t)((n + 7) / 8) * num_dirs * 4 * h * sizeof(double));
-}
-
 size_t ds2_gru_bwd_workspace_size(int n, int h, int num_dirs) {
-  return gru_bwd_ws_base(n, h, num_dirs) + gru_db_bytes(n, h, num_dirs);
+  return gru_bwd_layout(RnnShape{0, n, h, num_dirs}).total;
 }
 
 size_t ds2_gru_row_amax_workspace_size(int t_max, int n, int h, int num_dirs) {
   if (t_max < 0 || n < 0 || h < 1 || (num_dirs != 1 && num_dirs != 2)) return 0;
-  return ds2_gru_bwd_workspace_size(n, h, num_dirs) +
-         align256(gru_xl_rowp_bytes(t_max, n, h, num_dirs));
+  return gru_bwd_layout(RnnShape{t_max, n, h, num_dirs}).row_total;
 }
 
 // Which workspace holds valid row-maximum partials, and of which call: set when the XCD-local
@@ -1326,70 +1294,165 @@ ds2_status_t ds2_gru_row_amax(int t_max, int n, int h, int num_dirs, const void*
   if (t_max < 0 || n < 0 || h < 1 || (num_dirs != 1 && num_dirs != 2)) return DS2_INVALID_VALUE;
   if (t_max == 0 || n == 0) return DS2_OK;
   if (ws == nullptr || row_amax == nullptr) return DS2_INVALID_VALUE;
+  const GruBwdLayout L = gru_bwd_layout(RnnShape{t_max, n, h, num_dirs});
   {
     std::lock_guard<std::mutex> lk(g_row_mu);
     const RowRec r = g_row_rec;
     if (r.ws != ws || r.t != t_max || r.n != n || r.h != h || r.d != num_dirs ||
-        ws_bytes < ds2_gru_row_amax_workspace_size(t_max, n, h, num_dirs))
+        ws_bytes < L.row_total)
       return DS2_UNSUPPORTED_SHAPE;
   }
-  const float* rowp = reinterpret_cast<const float*>(static_cast<const char*>(ws) +
-                                                     ds2_gru_bwd_workspace_size(n, h, num_dirs));
-  launch_gru_xl_row_amax(t_max, n, h, num_dirs, rowp, row_amax, as_stream(stream));
+  launch_gru_xl_row_amax(t_max, n, h, num_dirs, ws_at<const float>(const_cast<void*>(ws), L.rowp),
+                         row_amax, as_stream(stream));
   return launch_status("ds2_gru_row_amax");
 }
-
-#define DS2_BWD_CASE(K)                                                                     \
-  case K:                                                                                   \
-    hipLaunchKernelGGL(gru_bwd_step_kernel<K>, dim3(grid), dim3(GT), 0, st, s, t_max, n, h,  \
-                       num_dirs, UB, BT, dy, dy_dirs, wpt, h_all, gates, lens, dgates_x,     \
-                       dgates_h, dhs);                                                       \
-    break;
 
 // workgroups the persistent backward launch holds at once (gru_bwd_run's choice), 0 for the
 // per-step kernels
 int ds2_gru_bwd_grid(int n, int h, int num_dirs) {
   if (n < 1 || h < 1 || (num_dirs != 1 && num_dirs != 2)) return 0;
-  const int UB = (h + GU - 1) / GU, BT = (n + GB - 1) / GB;
-  const int grid = mapped_grid(UB * num_dirs, BT);
+  const RnnShape s = {1, n, h, num_dirs};
+  const int grid = mapped_grid(s.UB() * num_dirs, s.BT());
   if (!persistent_enabled() || grid > num_cus()) return 0;
-  if ((h % GU) == 0 && UB <= 8 * GW) {
-    // the XCD-local or x6 launch may decline at run time and fall back to the direct-operand
-    // kernel at `grid`: report the largest so the CU guard never budgets for fewer workgroups
-    // than run
-    const int g = gru_bwd_x6_grid(n, h, num_dirs);
-    const int x = gru_xl_active(n, h, num_dirs);
-    const int m = g > x ? g : x;
-    return m > grid ? m : grid;
+  if ((h % GU) == 0 && s.UB() <= 8 * GW) {
+    // the XCD-local or 16-unit launch may decline at run time and fall back to the
+    // direct-operand kernel at `grid`: report the largest so the CU guard never budgets for
+    // fewer workgroups than run
+    return std::max({bwd16_grid(3, s, s.BT()), gru_xl_active(n, h, num_dirs), grid});
   }
   return (3 * h <= KC_BWD && (h % 4) == 0) ? grid : 0;
 }
 
-ds2_status_t ds2_gru_bwd(int t_max, int n, int h, int num_dirs, const float* dy, int dy_dirs,
-                         const float* w_hh_f, const float* w_hh_r, const float* h_all,
-                         const float* gates, const int* lens, float* dgates_x, float* dgates_h,
-                         unsigned* err_out, void* ws, size_t ws_bytes, ds2_stream_t stream) {
-  return ds2_gru_bwd_bias(t_max, n, h, num_dirs, dy, dy_dirs, w_hh_f, w_hh_r, h_all, gates, lens,
-                          dgates_x, dgates_h, nullptr, nullptr, nullptr, nullptr, err_out, ws,
-                          ws_bytes, stream);
+// What the recurrence left besides dgates: whether the kernel summed the bias partials
+// (a.dbp) and the column maxima (a.camax) itself, over how many batch tiles, and whether the
+// row-maximum partials (a.rowp) are valid.
+struct BwdDone {
+  bool summed, camax, rowp;
+  int db_tiles;
+};
+
+static ds2_status_t gru_bwd_run(const RnnShape& s, RecBwd a, unsigned* err_out, void* ws,
+                                const GruBwdLayout& L, hipStream_t st, BwdDone& done) {
+  apply_spin_limit_env();
+  apply_rnn_tune_env();
+  int T = s.t, N = s.n, H = s.h, D = s.d, UB = s.UB(), BT = s.BT();
+  const int KS = (3 * s.h + 3) / 4;
+  const int chunk_ks = (std::min(3 * s.h, KC_BWD) + 3) / 4;
+  const void* step_fn = pick_instance(kBwdStep, (chunk_ks + GW - 1) / GW + 1);
+  if (step_fn == nullptr) return DS2_UNSUPPORTED_SHAPE;
+  float* wpt = ws_at<float>(ws, L.wpt);
+  float* dhs = ws_at<float>(ws, L.dhs);
+  const int grid = mapped_grid(UB * D, BT);
+  const bool persistent = persistent_enabled() && grid <= num_cus() && s.fits32(3);
+  const size_t camax_bytes = (size_t)2 * D * 3 * H * sizeof(unsigned);
+  const bool dop = persistent && (H % GU) == 0 && UB <= 8 * GW;
+  Handoff ho = L.ho.at(ws, s, err_out);
+  // the XCD-local launch zeroes the counters and camax itself and reports into err_out from
+  // the kernel: no fills and no fold launch around it
+  if (dop && launch_gru_bwd_xl(s, a, ho, st)) {
+    done = BwdDone{a.dbp != nullptr, a.camax != nullptr, a.rowp != nullptr, (s.n + 7) / 8};
+    return launch_status("ds2_gru_bwd");
+  }
+  if (dop) (void)hipGetLastError();
+  if (a.camax != nullptr && hipMemsetAsync(a.camax, 0, camax_bytes, st) != hipSuccess)
+    return launch_status("ds2_gru_bwd_bias_amax");
+  ds2_status_t rc = DS2_OK;
+  if (dop) {
+    void* args[] = {&T, &N, &H, &D, &UB, &BT, &a.dy, &a.dy_dirs, &a.w_hh_f, &a.w_hh_r, &a.state,
+                    &a.gates, &a.lens, &a.dgx, &a.dgh, &ho.ring, &ho.ctrs, &ho.err, &ho.stamps,
+                    &a.dbp};
+    const void* fn = pick_instance(kBwdDop, (3 * UB + GW - 1) / GW);
+    if (rung("ds2_gru_bwd", ho, true, 0, st, &rc,
+             [&] { return launch_bwd16(3, s, a, ho, st, 0, BT, &done.camax); }) ||
+        rung("ds2_gru_bwd", ho, false, 0, st, &rc,
+             [&] { return launch_fn(fn, grid, GT, args, kDopPadLds, st); })) {
+      done.summed = a.dbp != nullptr;   // both sum the bias partials themselves
+      return rc;
+    }
+  }
+  hipLaunchKernelGGL(pack_bwd_kernel<3>, dim3(grid_cap((int64_t)D * UB * KS * 64)), dim3(256), 0,
+                     st, a.w_hh_f, a.w_hh_r, H, D, UB, KS, wpt);
+  if (persistent && 3 * H <= KC_BWD && (H % 4) == 0) {
+    void* args[] = {&T, &N, &H, &D, &UB, &BT, &a.dy, &a.dy_dirs, &wpt, &a.state, &a.gates,
+                    &a.lens, &a.dgx, &a.dgh, &ho.ctrs, &ho.err, &ho.stamps};
+    const void* fn = pick_instance(kBwdPersist, persist_ksw((KS + GW - 1) / GW, KC_BWD));
+    if (rung("ds2_gru_bwd", ho, true, 0, st, &rc,
+             [&] { return launch_fn(fn, grid, GT, args, 0, st); }))
+      return rc;
+  }
+
+  int step = 0;
+  void* args[] = {&step, &T, &N, &H, &D, &UB, &BT, &a.dy, &a.dy_dirs, &wpt, &a.state, &a.gates,
+                  &a.lens, &a.dgx, &a.dgh, &dhs};
+  for (step = 0; step < s.t; ++step)
+    (void)hipLaunchKernel(step_fn, dim3(grid), dim3(GT), args, 0, st);
+  return launch_status("ds2_gru_bwd");
 }
 
 // the recurrence; then, with db_ih_f non-null, the bias gradients (summed by the
-// direct-operand kernel itself, else from dgates_x / dgates_h)
-static ds2_status_t gru_bwd_run(int t_max, int n, int h, int num_dirs, const float* dy, int dy_dirs,
-                                const float* w_hh_f, const float* w_hh_r, const float* h_all,
-                                const float* gates, const int* lens, float* dgates_x,
-                                float* dgates_h, unsigned* err_out, void* ws, hipStream_t st,
-                                double* dbp, bool& summed, unsigned* camax, bool& camax_done,
-                                int& db_tiles, float* rowp, bool& rowp_done);
-
+// direct-operand kernel itself, else from dgates_x / dgates_h); with camax non-null the
+// column maxima of dgates_x / dgates_h
 static ds2_status_t gru_bwd_bias_impl(int t_max, int n, int h, int num_dirs, const float* dy,
                                       int dy_dirs, const float* w_hh_f, const float* w_hh_r,
                                       const float* h_all, const float* gates, const int* lens,
                                       float* dgates_x, float* dgates_h, float* db_ih_f,
                                       float* db_hh_f, float* db_ih_r, float* db_hh_r,
                                       unsigned* err_out, void* ws, size_t ws_bytes,
-                                      unsigned* camax, ds2_stream_t stream);
+                                      unsigned* camax, ds2_stream_t stream) {
+  if (t_max < 0 || n < 0 || h < 1 || (num_dirs != 1 && num_dirs != 2)) return DS2_INVALID_VALUE;
+  if (gates == nullptr) return DS2_INVALID_VALUE;
+  if (dy_dirs != 1 && dy_dirs != num_dirs) return DS2_INVALID_VALUE;
+  const bool want_db = db_ih_f != nullptr;
+  if (want_db && (db_hh_f == nullptr || (num_dirs == 2 && (db_ih_r == nullptr || db_hh_r == nullptr))))
+    return DS2_INVALID_VALUE;
+  const RnnShape s = {t_max, n, h, num_dirs};
+  const GruBwdLayout L = gru_bwd_layout(s);
+  if (ws == nullptr || ws_bytes < L.total) return DS2_WORKSPACE_TOO_SMALL;
+  hipStream_t st = as_stream(stream);
+  double* dbp = ws_at<double>(ws, L.dbp);
+  row_rec_clear(ws);
+  if (t_max == 0 || n == 0) {
+    if (camax != nullptr &&
+        hipMemsetAsync(camax, 0, (size_t)2 * num_dirs * 3 * h * sizeof(unsigned), st) != hipSuccess)
+      return launch_status("ds2_gru_bwd_bias_amax");
+    if (!want_db) return DS2_OK;
+    // no rows: zero bias gradients (one tile's partials even when n == 0)
+    const size_t one_tile = align256((size_t)num_dirs * 4 * h * sizeof(double));
+    if (hipMemsetAsync(dbp, 0, std::max(L.dbp_bytes, one_tile), st) != hipSuccess)
+      return launch_status("ds2_gru_bwd_bias");
+    hipLaunchKernelGGL(gru_db_final_kernel, dim3(cdiv(num_dirs * 4 * h, 256)), dim3(256), 0, st,
+                       dbp, 1, num_dirs, h, db_ih_f, db_hh_f, db_ih_r, db_hh_r);
+    return launch_status("ds2_gru_bwd_bias");
+  }
+  // the row-maximum partials of dgates_x (ds2_gru_row_amax): behind the plain workspace,
+  // kept only when the caller sized it with ds2_gru_row_amax_workspace_size
+  float* rowp = camax != nullptr && ws_bytes >= L.row_total ? ws_at<float>(ws, L.rowp) : nullptr;
+  const RecBwd a = {dy, dy_dirs, w_hh_f, num_dirs == 1 ? w_hh_f : w_hh_r, h_all, gates, lens,
+                    dgates_x, dgates_h, want_db ? dbp : nullptr, camax, rowp};
+  BwdDone done = {false, false, false, s.BT()};
+  const ds2_status_t rc = gru_bwd_run(s, a, err_out, ws, L, st, done);
+  if (rc != DS2_OK) return rc;
+  if (done.rowp) row_rec_set(ws, t_max, n, h, num_dirs);
+  if (camax != nullptr && !done.camax) {
+    // a kernel without the fused maxima ran: one column pass over each of dgx, dgh
+    const ds2_status_t ra = ds2_amax(dgates_x, t_max * n, num_dirs * 3 * h, num_dirs * 3 * h,
+                                     nullptr, camax, stream);
+    const ds2_status_t rb = ra != DS2_OK ? ra
+        : ds2_amax(dgates_h, t_max * n, num_dirs * 3 * h, num_dirs * 3 * h, nullptr,
+                   camax + num_dirs * 3 * h, stream);
+    if (rb != DS2_OK) return rb;
+  }
+  if (!want_db) return DS2_OK;
+  int bt = done.db_tiles;
+  if (!done.summed) {
+    hipLaunchKernelGGL(gru_db_cols_kernel, dim3(num_dirs * 4 * h), dim3(256), 0, st, dgates_x,
+                       dgates_h, t_max * n, num_dirs, h, dbp);
+    bt = 1;
+  }
+  hipLaunchKernelGGL(gru_db_final_kernel, dim3(cdiv(num_dirs * 4 * h, 256)), dim3(256), 0, st, dbp,
+                     bt, num_dirs, h, db_ih_f, db_hh_f, db_ih_r, db_hh_r);
+  return launch_status("ds2_gru_bwd_bias");
+}
 
 ds2_status_t ds2_gru_bwd_bias(int t_max, int n, int h, int num_dirs, const float* dy, int dy_dirs,
                               const float* w_hh_f, const float* w_hh_r, const float* h_all,
@@ -1399,6 +1462,15 @@ ds2_status_t ds2_gru_bwd_bias(int t_max, int n, int h, int num_dirs, const float
                               ds2_stream_t stream) {
   return gru_bwd_bias_impl(t_max, n, h, num_dirs, dy, dy_dirs, w_hh_f, w_hh_r, h_all, gates, lens,
                            dgates_x, dgates_h, db_ih_f, db_hh_f, db_ih_r, db_hh_r, err_out, ws,
+                           ws_bytes, nullptr, stream);
+}
+
+ds2_status_t ds2_gru_bwd(int t_max, int n, int h, int num_dirs, const float* dy, int dy_dirs,
+                         const float* w_hh_f, const float* w_hh_r, const float* h_all,
+                         const float* gates, const int* lens, float* dgates_x, float* dgates_h,
+                         unsigned* err_out, void* ws, size_t ws_bytes, ds2_stream_t stream) {
+  return gru_bwd_bias_impl(t_max, n, h, num_dirs, dy, dy_dirs, w_hh_f, w_hh_r, h_all, gates, lens,
+                           dgates_x, dgates_h, nullptr, nullptr, nullptr, nullptr, err_out, ws,
                            ws_bytes, nullptr, stream);
 }
 
@@ -1415,193 +1487,21 @@ ds2_status_t ds2_gru_bwd_bias_amax(int t_max, int n, int h, int num_dirs, const 
                            ws_bytes, col_amax, stream);
 }
 
-static ds2_status_t gru_bwd_bias_impl(int t_max, int n, int h, int num_dirs, const float* dy,
-                                      int dy_dirs, const float* w_hh_f, const float* w_hh_r,
-                                      const float* h_all, const float* gates, const int* lens,
-                                      float* dgates_x, float* dgates_h, float* db_ih_f,
-                                      float* db_hh_f, float* db_ih_r, float* db_hh_r,
-                                      unsigned* err_out, void* ws, size_t ws_bytes,
-                                      unsigned* camax, ds2_stream_t stream) {
-  if (t_max < 0 || n < 0 || h < 1 || (num_dirs != 1 && num_dirs != 2)) return DS2_INVALID_VALUE;
-  if (gates == nullptr) return DS2_INVALID_VALUE;
-  if (dy_dirs != 1 && dy_dirs != num_dirs) return DS2_INVALID_VALUE;
-  const bool want_db = db_ih_f != nullptr;
-  if (want_db && (db_hh_f == nullptr || (num_dirs == 2 && (db_ih_r == nullptr || db_hh_r == nullptr))))
-    return DS2_INVALID_VALUE;
-  if (ws == nullptr || ws_bytes < ds2_gru_bwd_workspace_size(n, h, num_dirs))
-    return DS2_WORKSPACE_TOO_SMALL;
-  hipStream_t st = as_stream(stream);
-  double* dbp = reinterpret_cast<double*>(static_cast<char*>(ws) + gru_bwd_ws_base(n, h, num_dirs));
-  const size_t camax_bytes = (size_t)2 * num_dirs * 3 * h * sizeof(unsigned);
-  row_rec_clear(ws);
-  if (t_max == 0 || n == 0) {
-    if (camax != nullptr && hipMemsetAsync(camax, 0, camax_bytes, st) != hipSuccess)
-      return launch_status("ds2_gru_bwd_bias_amax");
-    if (!want_db) return DS2_OK;
-    // no rows: zero bias gradients
-    if (hipMemsetAsync(dbp, 0, gru_db_bytes(n > 0 ? n : 1, h, num_dirs), st) != hipSuccess)
-      return launch_status("ds2_gru_bwd_bias");
-    hipLaunchKernelGGL(gru_db_final_kernel, dim3(cdiv(num_dirs * 4 * h, 256)), dim3(256), 0, st,
-                       dbp, 1, num_dirs, h, db_ih_f, db_hh_f, db_ih_r, db_hh_r);
-    return launch_status("ds2_gru_bwd_bias");
-  }
-  bool summed = false, camax_done = false, rowp_done = false;
-  int db_tiles = (n + GB - 1) / GB;
-  // the row-maximum partials of dgates_x (ds2_gru_row_amax): behind the plain workspace,
-  // kept only when the caller sized it with ds2_gru_row_amax_workspace_size
-  float* rowp = nullptr;
-  if (camax != nullptr && ws_bytes >= ds2_gru_row_amax_workspace_size(t_max, n, h, num_dirs))
-    rowp = reinterpret_cast<float*>(static_cast<char*>(ws) +
-                                    ds2_gru_bwd_workspace_size(n, h, num_dirs));
-  const ds2_status_t rc = gru_bwd_run(t_max, n, h, num_dirs, dy, dy_dirs, w_hh_f, w_hh_r, h_all,
-                                      gates, lens, dgates_x, dgates_h, err_out, ws, st,
-                                      want_db ? dbp : nullptr, summed, camax, camax_done, db_tiles,
-                                      rowp, rowp_done);
-  if (rc != DS2_OK) return rc;
-  if (rowp_done) row_rec_set(ws, t_max, n, h, num_dirs);
-  if (camax != nullptr && !camax_done) {
-    // a kernel without the fused maxima ran: one column pass over each of dgx, dgh
-    const ds2_status_t ra = ds2_amax(dgates_x, t_max * n, num_dirs * 3 * h, num_dirs * 3 * h,
-                                     nullptr, camax, stream);
-    const ds2_status_t rb = ra != DS2_OK ? ra
-        : ds2_amax(dgates_h, t_max * n, num_dirs * 3 * h, num_dirs * 3 * h, nullptr,
-                   camax + num_dirs * 3 * h, stream);
-    if (rb != DS2_OK) return rb;
-  }
-  if (!want_db) return DS2_OK;
-  int bt = db_tiles;
-  if (!summed) {
-    hipLaunchKernelGGL(gru_db_cols_kernel, dim3(num_dirs * 4 * h), dim3(256), 0, st, dgates_x,
-                       dgates_h, t_max * n, num_dirs, h, dbp);
-    bt = 1;
-  }
-  hipLaunchKernelGGL(gru_db_final_kernel, dim3(cdiv(num_dirs * 4 * h, 256)), dim3(256), 0, st, dbp,
-                     bt, num_dirs, h, db_ih_f, db_hh_f, db_ih_r, db_hh_r);
-  return launch_status("ds2_gru_bwd_bias");
-}
-
-static ds2_status_t gru_bwd_run(int t_max, int n, int h, int num_dirs, const float* dy, int dy_dirs,
-                                const float* w_hh_f, const float* w_hh_r, const float* h_all,
-                                const float* gates, const int* lens, float* dgates_x,
-                                float* dgates_h, unsigned* err_out, void* ws, hipStream_t st,
-                                double* dbp, bool& summed, unsigned* camax, bool& camax_done,
-                                int& db_tiles, float* rowp, bool& rowp_done) {
-  if (num_dirs == 1) w_hh_r = w_hh_f;
-  apply_spin_limit_env();
-  apply_rnn_tune_env();
-  const int UB = (h + GU - 1) / GU;
-  const int KS = (3 * h + 3) / 4;
-  const int BT = (n + GB - 1) / GB;
-  const int chunk_ks = (std::min(3 * h, KC_BWD) + 3) / 4;
-  const int ksw = pick_ksw((chunk_ks + GW - 1) / GW + 1);
-  if (ksw < 0) return DS2_UNSUPPORTED_SHAPE;
-  float* wpt = static_cast<float*>(ws);
-  size_t off = align256((size_t)num_dirs * UB * KS * 64 * sizeof(float));
-  float* dhs = reinterpret_cast<float*>(static_cast<char*>(ws) + off);
-  const int grid = mapped_grid(UB * num_dirs, BT);
-  const bool persistent = persistent_enabled() && grid <= num_cus() &&
-                          (int64_t)t_max * n * num_dirs * 3 * h * 4 < (1ll << 31);
-  unsigned* ctrs = reinterpret_cast<unsigned*>(
-      reinterpret_cast<char*>(dhs) + align256((size_t)2 * n * num_dirs * h * sizeof(float)));
-  unsigned* err = ctrs + num_dirs * BT;
-  const size_t camax_bytes = (size_t)2 * num_dirs * 3 * h * sizeof(unsigned);
-  const bool dop = persistent && (h % GU) == 0 && UB <= 8 * GW;
-  if (dop) {
-    // the XCD-local launch zeroes the counters and camax itself and reports into err_out from
-    // the kernel: no fills and no fold launch around it
-    unsigned long long* stamps = stamp_mode() == 2 ? stamp_slots(ctrs, n, num_dirs) : nullptr;
-    float* ring = reinterpret_cast<float*>(reinterpret_cast<char*>(ctrs) +
-                                           align256(counter_bytes(n, num_dirs)));
-    if (launch_gru_bwd_xl(t_max, n, h, num_dirs, dy, dy_dirs, w_hh_f, w_hh_r, h_all, gates,
-                          lens, dgates_x, dgates_h, ring, ctrs, counter_bytes(n, num_dirs),
-                          err + 1, err, err_out, stamps, dbp, kDopPadLds, st, camax, rowp)) {
-      summed = dbp != nullptr;
-      camax_done = camax != nullptr;
-      rowp_done = rowp != nullptr;
-      db_tiles = (n + 7) / 8;
-      return launch_status("ds2_gru_bwd");
-    }
-    (void)hipGetLastError();
-  }
-  if (camax != nullptr && hipMemsetAsync(camax, 0, camax_bytes, st) != hipSuccess)
-    return launch_status("ds2_gru_bwd_bias_amax");
-  if (dop) {
-    if (hipMemsetAsync(ctrs, 0, counter_bytes(n, num_dirs), st) != hipSuccess)
-      return launch_status("ds2_gru counters");
-    int T_ = t_max, N_ = n, H_ = h, D_ = num_dirs, UB_ = UB, BT_ = BT, DYD_ = dy_dirs;
-    unsigned long long* stamps = stamp_mode() == 2 ? stamp_slots(ctrs, n, num_dirs) : nullptr;
-    float* ring = reinterpret_cast<float*>(reinterpret_cast<char*>(ctrs) +
-                                           align256(counter_bytes(n, num_dirs)));
-    void* args[] = {&T_, &N_, &H_, &D_, &UB_, &BT_, &dy, &DYD_, &w_hh_f, &w_hh_r, &h_all,
-                    &gates, &lens, &dgates_x, &dgates_h, &ring, &ctrs, &err, &stamps, &dbp};
-    if (launch_gru_bwd_x6(t_max, n, h, num_dirs, dy, dy_dirs, w_hh_f, w_hh_r, h_all, gates,
-                          lens, dgates_x, dgates_h, ring, ctrs, err, stamps, dbp, kDopPadLds, st,
-                          camax, &camax_done)) {
-      fold_err(err, err_out, st);
-      summed = dbp != nullptr;
-      return launch_status("ds2_gru_bwd");
-    }
-    (void)hipGetLastError();
-    const void* fn = bwd_dop_fn((3 * UB + GW - 1) / GW);
-    if (fn != nullptr &&
-        rnn_launch(fn, dim3(grid), dim3(GT), args, kDopPadLds, st) == hipSuccess) {
-      fold_err(err, err_out, st);
-      summed = dbp != nullptr;
-      return launch_status("ds2_gru_bwd");
-    }
-    (void)hipGetLastError();
-  }
-  hipLaunchKernelGGL(pack_bwd_kernel<3>, dim3(grid_cap((int64_t)num_dirs * UB * KS * 64)),
-                     dim3(256), 0, st, w_hh_f, w_hh_r, h, num_dirs, UB, KS, wpt);
-  if (persistent && 3 * h <= KC_BWD && (h % 4) == 0) {
-    if (hipMemsetAsync(ctrs, 0, counter_bytes(n, num_dirs), st) != hipSuccess)
-      return launch_status("ds2_gru counters");
-    int T_ = t_max, N_ = n, H_ = h, D_ = num_dirs, UB_ = UB, BT_ = BT, DYD_ = dy_dirs;
-    unsigned long long* stamps = stamp_mode() == 2 ? stamp_slots(ctrs, n, num_dirs) : nullptr;
-    void* args[] = {&T_, &N_, &H_, &D_, &UB_, &BT_, &dy, &DYD_, &wpt, &h_all, &gates, &lens,
-                    &dgates_x, &dgates_h, &ctrs, &err, &stamps};
-    const void* fn = nullptr;
-    const int kp = persist_ksw((KS + GW - 1) / GW, KC_BWD);
-    switch (kp) {
-      case 8: fn = reinterpret_cast<const void*>(gru_bwd_persist_kernel<8>); break;
-      case 16: fn = reinterpret_cast<const void*>(gru_bwd_persist_kernel<16>); break;
-      case 25: fn = reinterpret_cast<const void*>(gru_bwd_persist_kernel<25>); break;
-      case 32: fn = reinterpret_cast<const void*>(gru_bwd_persist_kernel<32>); break;
-      case 48: fn = reinterpret_cast<const void*>(gru_bwd_persist_kernel<48>); break;
-      case 64: fn = reinterpret_cast<const void*>(gru_bwd_persist_kernel<64>); break;
-      case 75: fn = reinterpret_cast<const void*>(gru_bwd_persist_kernel<75>); break;
-      default: break;
-    }
-    if (fn != nullptr &&
-        rnn_launch(fn, dim3(grid), dim3(GT), args, 0, st) == hipSuccess) {
-      fold_err(err, err_out, st);
-      return launch_status("ds2_gru_bwd");
-    }
-    (void)hipGetLastError();
-  }
-  for (int s = 0; s < t_max; ++s) {
-    switch (ksw) {
-      DS2_BWD_CASE(8) DS2_BWD_CASE(16) DS2_BWD_CASE(32) DS2_BWD_CASE(48) DS2_BWD_CASE(64)
-      DS2_BWD_CASE(80) DS2_BWD_CASE(96)
-    }
-  }
-  return launch_status("ds2_gru_bwd");
-}
-
 // ---------------------------------------------------------------------------------------
 // supported_rnns['rnn'] (nn.RNN, tanh; model.py:15) on the persistent machinery: the
 // one-gate fp16x3 instantiations of the GRU recurrences (gru_split.hip), falling back to the
 // per-step kernels of rnn.hip (ds2_rnn_fwd / ds2_rnn_bwd) where they decline the shape or
 // DS2_RNN_PERSISTENT=0.  Workspace: the counters and the hand-off ring.
-static bool rnn_persistent_ok(int t_max, int n, int h, int num_dirs) {
-  const int g = rnn_h3_grid(n, h, num_dirs);
-  return persistent_enabled() && g > 0 && g <= num_cus() &&
-         (int64_t)t_max * n * num_dirs * h * 4 < (1ll << 31);
+
+// the grid of the one-gate launches (forward and backward alike), 0 when they decline
+static int rnn_grid(const RnnShape& s) {
+  const int g = fwd16_grid(1, s) < 0 ? -1 : bwd16_grid(1, s, s.BT());
+  return persistent_enabled() && g > 0 && g <= num_cus() ? g : 0;
 }
 
 size_t ds2_rnn_fwd_workspace_size(int n, int h, int num_dirs) {
   if (n < 1 || h < 1 || num_dirs < 1) return 256;
-  return align256(counter_bytes(n, num_dirs)) + ring_bytes(n, h, num_dirs, 1) + 256;
+  return rnn_layout(RnnShape{0, n, h, num_dirs}, 1).total;
 }
 
 ds2_status_t ds2_rnn_fwd_ws(int t_max, int n, int h, int num_dirs, const float* xproj,
@@ -1620,20 +1520,15 @@ ds2_status_t ds2_rnn_fwd_ws(int t_max, int n, int h, int num_dirs, const float* 
     b_hh_r = b_hh_f;
   }
   hipStream_t st = as_stream(stream);
-  if (rnn_persistent_ok(t_max, n, h, num_dirs)) {
-    unsigned* ctrs = static_cast<unsigned*>(ws);
-    unsigned* err = ctrs + num_dirs * ((n + GB - 1) / GB);
-    float* ring = reinterpret_cast<float*>(static_cast<char*>(ws) + align256(counter_bytes(n, num_dirs)));
-    if (hipMemsetAsync(ctrs, 0, counter_bytes(n, num_dirs), st) != hipSuccess)
-      return launch_status("ds2_rnn counters");
-    if (ring_reset(ring, n, h, num_dirs, st) != hipSuccess) return launch_status("ds2_rnn ring");
-    unsigned long long* stamps = stamp_mode() == 2 ? stamp_slots(ctrs, n, num_dirs) : nullptr;
-    if (launch_rnn_fwd_h3(t_max, n, h, num_dirs, xproj, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lens,
-                          h_all, ring, ctrs, err, stamps, kDopPadLds, st)) {
-      fold_err(err, err_out, st);
-      return launch_status("ds2_rnn_fwd");
-    }
-    (void)hipGetLastError();
+  const RnnShape s = {t_max, n, h, num_dirs};
+  if (rnn_grid(s) > 0 && s.fits32(1)) {
+    const RnnLayout L = rnn_layout(s, 1);
+    const Handoff ho = L.ho.at(ws, s, err_out);
+    const RecFwd a = {xproj, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lens, h_all, nullptr, nullptr};
+    ds2_status_t rc = DS2_OK;
+    if (rung("ds2_rnn_fwd", ho, true, L.ho.ring_bytes, st, &rc,
+             [&] { return launch_fwd16(1, s, a, ho, st); }))
+      return rc;
   }
   return ds2_rnn_fwd(t_max, n, h, num_dirs, xproj, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lens, h_all,
                      stream);
@@ -1641,13 +1536,12 @@ ds2_status_t ds2_rnn_fwd_ws(int t_max, int n, int h, int num_dirs, const float* 
 
 size_t ds2_rnn_bwd_workspace_size(int n, int h, int num_dirs) {
   if (n < 1 || h < 1 || num_dirs < 1) return 256;
-  return align256(counter_bytes(n, num_dirs)) + ring_bytes(n, h, num_dirs, 3) + 256;
+  return rnn_layout(RnnShape{0, n, h, num_dirs}, 3).total;
 }
 
 int ds2_rnn_bwd_grid(int n, int h, int num_dirs) {
   if (n < 1 || h < 1 || (num_dirs != 1 && num_dirs != 2)) return 0;
-  const int g = rnn_h3_grid(n, h, num_dirs);
-  return persistent_enabled() && g > 0 && g <= num_cus() ? g : 0;
+  return rnn_grid(RnnShape{1, n, h, num_dirs});
 }
 
 ds2_status_t ds2_rnn_bwd_ws(int t_max, int n, int h, int num_dirs, const float* dy, int dy_dirs,
@@ -1667,19 +1561,15 @@ ds2_status_t ds2_rnn_bwd_ws(int t_max, int n, int h, int num_dirs, const float* 
       dgates == nullptr || (num_dirs == 2 && w_hh_r == nullptr))
     return DS2_INVALID_VALUE;
   if (num_dirs == 1) w_hh_r = w_hh_f;
-  if (rnn_persistent_ok(t_max, n, h, num_dirs)) {
-    unsigned* ctrs = static_cast<unsigned*>(ws);
-    unsigned* err = ctrs + num_dirs * ((n + GB - 1) / GB);
-    float* ring = reinterpret_cast<float*>(static_cast<char*>(ws) + align256(counter_bytes(n, num_dirs)));
-    if (hipMemsetAsync(ctrs, 0, counter_bytes(n, num_dirs), st) != hipSuccess)
-      return launch_status("ds2_rnn counters");
-    unsigned long long* stamps = stamp_mode() == 2 ? stamp_slots(ctrs, n, num_dirs) : nullptr;
-    if (launch_rnn_bwd_h3(t_max, n, h, num_dirs, dy, dy_dirs, w_hh_f, w_hh_r, h_all, lens, dgates,
-                          ring, ctrs, err, stamps, kDopPadLds, st, col_amax)) {
-      fold_err(err, err_out, st);
-      return launch_status("ds2_rnn_bwd");
-    }
-    (void)hipGetLastError();
+  const RnnShape s = {t_max, n, h, num_dirs};
+  if (rnn_grid(s) > 0 && s.fits32(1)) {
+    const Handoff ho = rnn_layout(s, 3).ho.at(ws, s, err_out);
+    const RecBwd a = {dy, dy_dirs, w_hh_f, w_hh_r, h_all, nullptr, lens, dgates, nullptr,
+                      nullptr, col_amax, nullptr};
+    ds2_status_t rc = DS2_OK;
+    if (rung("ds2_rnn_bwd", ho, true, 0, st, &rc,
+             [&] { return launch_bwd16(1, s, a, ho, st, 0, s.BT(), nullptr); }))
+      return rc;
   }
   const ds2_status_t rc = ds2_rnn_bwd(t_max, n, h, num_dirs, dy, dy_dirs, w_hh_f, w_hh_r, h_all,
                                       lens, dgates, stream);

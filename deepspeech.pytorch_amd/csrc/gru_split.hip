@@ -20,7 +20,7 @@
 // lane (r, q) holds tile 2p + (j >> 2), k = 4q + (j & 3) -- exactly the 16 bytes that lane
 // loads from each 1-KB tile, so the hand-off tiles, ring layout and protocols are those of
 // gru_fwd_dop_kernel / gru_bwd_dop_kernel (gru.hip) unchanged.
-#include "rnn_common.h"
+#include "rnn_host.h"
 
 namespace ds2 {
 
@@ -1441,242 +1441,125 @@ __global__ __launch_bounds__(BW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 }
 
 // ---------------------------------------------------------------------------------------
-// host launchers (called by ds2_gru_fwd / ds2_gru_bwd in gru.hip with their workspace
-// carve-up); false = shape not covered (caller falls back to the fp32-MFMA kernels)
+// host launchers (rnn_host.h; called by gru.hip and lstm.hip with their workspace carve-up);
+// false = shape or switches not covered, the caller goes on to its next rung
 
-// on by default; DS2_GRU_X6=0 selects the fp32-MFMA kernels (gru.hip: the accuracy
-// cross-check of the tests)
-static inline bool x6_enabled() {
-  const char* e = getenv("DS2_GRU_X6");
-  return !(e != nullptr && e[0] == '0');
+// forward, K = producer pairs per wave: the GRU on fp16x3 (default since round 5) or bf16x6
+// (DS2_GRU_H3=0), the tanh RNN on the one-gate fp16x3 instantiations
+static const Instance kGruFwdH3[] = {
+    inst(1, gru_fwd_x6_kernel<1, true>), inst(2, gru_fwd_x6_kernel<2, true>),
+    inst(3, gru_fwd_x6_kernel<3, true>), inst(4, gru_fwd_x6_kernel<4, true>),
+    inst(5, gru_fwd_x6_kernel<5, true>), inst(6, gru_fwd_x6_kernel<6, true>),
+    inst(7, gru_fwd_x6_kernel<7, true>)};
+static const Instance kGruFwdX6[] = {
+    inst(1, gru_fwd_x6_kernel<1, false>), inst(2, gru_fwd_x6_kernel<2, false>),
+    inst(3, gru_fwd_x6_kernel<3, false>), inst(4, gru_fwd_x6_kernel<4, false>),
+    inst(5, gru_fwd_x6_kernel<5, false>), inst(6, gru_fwd_x6_kernel<6, false>),
+    inst(7, gru_fwd_x6_kernel<7, false>)};
+static const Instance kRnnFwd[] = {
+    inst(1, gru_fwd_x6_kernel<1, true, 1>), inst(2, gru_fwd_x6_kernel<2, true, 1>),
+    inst(3, gru_fwd_x6_kernel<3, true, 1>), inst(4, gru_fwd_x6_kernel<4, true, 1>),
+    inst(5, gru_fwd_x6_kernel<5, true, 1>), inst(6, gru_fwd_x6_kernel<6, true, 1>),
+    inst(7, gru_fwd_x6_kernel<7, true, 1>)};
+// backward, K = producers (fp16x3) or producer pairs (bf16x6, DS2_GRU_H3_BWD=0) per wave
+static const Instance kGruBwdX6[] = {
+    inst(1, gru_bwd_x6_kernel<1>), inst(2, gru_bwd_x6_kernel<2>), inst(3, gru_bwd_x6_kernel<3>),
+    inst(4, gru_bwd_x6_kernel<4>), inst(6, gru_bwd_x6_kernel<6>), inst(8, gru_bwd_x6_kernel<8>),
+    inst(10, gru_bwd_x6_kernel<10>), inst(12, gru_bwd_x6_kernel<12>)};
+static const Instance kGruBwdH3[] = {
+    inst(1, gru_bwd_h3_kernel<1>), inst(2, gru_bwd_h3_kernel<2>), inst(3, gru_bwd_h3_kernel<3>),
+    inst(4, gru_bwd_h3_kernel<4>), inst(5, gru_bwd_h3_kernel<5>), inst(6, gru_bwd_h3_kernel<6>),
+    inst(7, gru_bwd_h3_kernel<7>), inst(8, gru_bwd_h3_kernel<8>)};
+static const Instance kRnnBwd[] = {
+    inst(1, gru_bwd_h3_kernel<1, 1>), inst(2, gru_bwd_h3_kernel<2, 1>),
+    inst(3, gru_bwd_h3_kernel<3, 1>), inst(4, gru_bwd_h3_kernel<4, 1>),
+    inst(5, gru_bwd_h3_kernel<5, 1>), inst(6, gru_bwd_h3_kernel<6, 1>),
+    inst(7, gru_bwd_h3_kernel<7, 1>), inst(8, gru_bwd_h3_kernel<8, 1>)};
+static const Instance kLstmBwd[] = {
+    inst(1, gru_bwd_h3_kernel<1, 4>), inst(2, gru_bwd_h3_kernel<2, 4>),
+    inst(3, gru_bwd_h3_kernel<3, 4>), inst(4, gru_bwd_h3_kernel<4, 4>),
+    inst(5, gru_bwd_h3_kernel<5, 4>), inst(6, gru_bwd_h3_kernel<6, 4>),
+    inst(7, gru_bwd_h3_kernel<7, 4>), inst(8, gru_bwd_h3_kernel<8, 4>)};
+static const Instance kLstmBwdH1[] = {
+    inst(1, lstm_bwd_h1_kernel<1>), inst(2, lstm_bwd_h1_kernel<2>),
+    inst(4, lstm_bwd_h1_kernel<4>), inst(8, lstm_bwd_h1_kernel<8>)};
+
+// What a launch runs: the kernel, its grid and the same-XCD flag (the groups on their own
+// XCDs where they tile the 8: cfg2 backward 5.82 -> 5.43 us per step in isolation; DS2_GRU_XCD=0
+// keeps map_work's interleaved layout, bit-identical results).  The grid queries and the
+// launches both come through here.  fn == nullptr: declined.
+struct Pick16 {
+  const void* fn;
+  int grid, same_xcd;
+  bool h3;   // an fp16x3 backward: it also leaves the column maxima (camax)
+};
+
+// the GRU kernels are on by default; DS2_GRU_X6=0 selects the fp32-MFMA kernels (gru.hip: the
+// accuracy cross-check of the tests)
+static bool declines16(int ng, int h) {
+  return (h % GU) != 0 || (ng == 3 && env_off("DS2_GRU_X6"));
 }
 
-// the forward's W_hh product on fp16x3 (default since round 5; DS2_GRU_H3=0 keeps bf16x6)
-static inline bool fwd_h3_enabled() {
-  const char* e = getenv("DS2_GRU_H3");
-  return !(e != nullptr && e[0] == '0');
+static Pick16 pick_fwd16(int ng, const RnnShape& s) {
+  Pick16 p = {nullptr, -1, 0, false};
+  if (declines16(ng, s.h) || (ng != 1 && ng != 3)) return p;
+  const int need = ((s.UB() + 1) / 2 + XW - 1) / XW;
+  p.fn = ng == 1                 ? pick_instance(kRnnFwd, need)
+         : env_off("DS2_GRU_H3") ? pick_instance(kGruFwdX6, need)
+                                 : pick_instance(kGruFwdH3, need);
+  if (p.fn != nullptr) p.grid = group_grid(s.UB(), s.BT(), s.d, &p.same_xcd);
+  return p;
 }
 
-static const void* fwd_x6_fn(int need) {
-  const bool h3 = fwd_h3_enabled();
-#define DS2_FX6(K)                                                                  \
-  if (need <= K)                                                                    \
-    return h3 ? reinterpret_cast<const void*>(gru_fwd_x6_kernel<K, true>)           \
-              : reinterpret_cast<const void*>(gru_fwd_x6_kernel<K, false>);
-  DS2_FX6(1) DS2_FX6(2) DS2_FX6(3) DS2_FX6(4) DS2_FX6(5) DS2_FX6(6) DS2_FX6(7)
-#undef DS2_FX6
-  return nullptr;
+static Pick16 pick_bwd16(int ng, const RnnShape& s, int bt_launch) {
+  Pick16 p = {nullptr, -1, 0, false};
+  if (declines16(ng, s.h)) return p;
+  const int UB = s.UB(), need = (UB + BW - 1) / BW;
+  p.fn = ng == 1   ? pick_instance(kRnnBwd, need)
+         : ng == 4 ? pick_instance(kLstmBwd, need)
+         : env_off("DS2_GRU_H3_BWD") ? nullptr : pick_instance(kGruBwdH3, need);
+  p.h3 = p.fn != nullptr;
+  if (p.fn == nullptr && ng == 3) p.fn = pick_instance(kGruBwdX6, ((3 * UB + 1) / 2 + BW - 1) / BW);
+  if (p.fn != nullptr) p.grid = group_grid(UB, bt_launch, s.d, &p.same_xcd);
+  return p;
 }
 
-static const void* bwd_x6_fn(int pairs) {
-  const int need = (pairs + BW - 1) / BW;
-#define DS2_BP6(K) \
-  if (need <= K) return reinterpret_cast<const void*>(gru_bwd_x6_kernel<K>);
-  DS2_BP6(1) DS2_BP6(2) DS2_BP6(3) DS2_BP6(4) DS2_BP6(6) DS2_BP6(8) DS2_BP6(10) DS2_BP6(12)
-#undef DS2_BP6
-  return nullptr;
-}
+int fwd16_grid(int ng, RnnShape s) { return pick_fwd16(ng, s).grid; }
+int bwd16_grid(int ng, RnnShape s, int bt_launch) { return pick_bwd16(ng, s, bt_launch).grid; }
 
-// same-XCD hand-off groups (rnn_common.h map_work_xgrp), default on where the groups tile the
-// 8 XCDs: cfg2 backward 5.82 -> 5.43 us per step in isolation, 6.14 -> 5.69 in the training
-// step; DS2_GRU_XCD=0 keeps map_work's interleaved layout (bit-identical results)
-static inline bool xcd_groups(int UB, int BT, int num_dirs) {
-  return xcd_groups_on() && xgrp_fits(UB, BT, num_dirs);
-}
-
-bool launch_gru_fwd_x6(int t_max, int n, int h, int num_dirs, const float* xproj,
-                       const float* w_hh_f, const float* w_hh_r, const float* b_hh_f,
-                       const float* b_hh_r, const int* lens, float* h_all, float* gates,
-                       float* ring, unsigned* ctrs, unsigned* err, unsigned long long* stamps,
-                       size_t lds_pad, hipStream_t st) {
-  if (!x6_enabled() || (h % GU) != 0) return false;
-  apply_spin_limit_env();     // this translation unit's copies of the device knobs
-  apply_rnn_tune_env();
-  const int UB = h / GU, BT = (n + GB - 1) / GB;
-  const int need = ((UB + 1) / 2 + XW - 1) / XW;
-  const void* fn = fwd_x6_fn(need);
-  if (fn == nullptr) return false;
-  int XM_ = xcd_groups(UB, BT, num_dirs) ? 1 : 0;
-  const int grid = XM_ ? xgrp_grid(UB, BT, num_dirs) : mapped_grid(UB * num_dirs, BT);
-  int T_ = t_max, N_ = n, H_ = h, D_ = num_dirs, UB_ = UB, BT_ = BT;
-  void* args[] = {&T_, &N_, &H_, &D_, &UB_, &BT_, &xproj, &w_hh_f, &w_hh_r, &b_hh_f,
-                  &b_hh_r, &lens, &h_all, &gates, &ring, &ctrs, &err, &stamps, &XM_};
-  return rnn_launch(fn, dim3(grid), dim3(XT), args, lds_pad, st) == hipSuccess;
-}
-
-// grid of the x6 backward launch_gru_bwd_x6 would make, -1 if it declines the shape
-int gru_bwd_x6_grid(int n, int h, int num_dirs) {
-  if (!x6_enabled() || (h % GU) != 0) return -1;
-  const int UB = h / GU, BT = (n + GB - 1) / GB;
-  if (bwd_x6_fn((3 * UB + 1) / 2) == nullptr) return -1;
-  return xcd_groups(UB, BT, num_dirs) ? xgrp_grid(UB, BT, num_dirs)
-                                      : mapped_grid(UB * num_dirs, BT);
-}
-
-// the backward's W_hh^T product on fp16x3 (default since round 5; DS2_GRU_H3_BWD=0 keeps
-// the bf16x6 pre-split kernel)
-static inline bool bwd_h3_enabled() {
-  const char* e = getenv("DS2_GRU_H3_BWD");
-  return !(e != nullptr && e[0] == '0');
-}
-
-static const void* bwd_h3_fn(int UB) {
-  const int need = (UB + BW - 1) / BW;
-#define DS2_BH3(K) \
-  if (need <= K) return reinterpret_cast<const void*>(gru_bwd_h3_kernel<K>);
-  DS2_BH3(1) DS2_BH3(2) DS2_BH3(3) DS2_BH3(4) DS2_BH3(5) DS2_BH3(6) DS2_BH3(7) DS2_BH3(8)
-#undef DS2_BH3
-  return nullptr;
-}
-
-// camax (nullable, zeroed by the caller): the fp16x3 backward also leaves the column maxima
-// of dgates_x / dgates_h there; *camax_done says whether the kernel that ran did
-bool launch_gru_bwd_x6(int t_max, int n, int h, int num_dirs, const float* dy, int dy_dirs,
-                       const float* w_hh_f, const float* w_hh_r, const float* h_all,
-                       const float* gates, const int* lens, float* dgates_x, float* dgates_h,
-                       float* ring, unsigned* ctrs, unsigned* err, unsigned long long* stamps,
-                       double* dbp, size_t lds_pad, hipStream_t st, unsigned* camax,
-                       bool* camax_done) {
-  if (camax_done != nullptr) *camax_done = false;
-  if (!x6_enabled() || (h % GU) != 0) return false;
+// this translation unit's copies of the device knobs
+static void apply_knobs() {
   apply_spin_limit_env();
   apply_rnn_tune_env();
-  const int UB = h / GU, BT = (n + GB - 1) / GB;
-  const void* fn = bwd_h3_enabled() ? bwd_h3_fn(UB) : nullptr;
-  const bool h3 = fn != nullptr;
-  if (fn == nullptr) fn = bwd_x6_fn((3 * UB + 1) / 2);
-  if (fn == nullptr) return false;
-  int XM_ = xcd_groups(UB, BT, num_dirs) ? 1 : 0;
-  const int grid = XM_ ? xgrp_grid(UB, BT, num_dirs) : mapped_grid(UB * num_dirs, BT);
-  int T_ = t_max, N_ = n, H_ = h, D_ = num_dirs, UB_ = UB, BT_ = BT, DYD_ = dy_dirs, NB_ = 0;
-  void* args[] = {&T_, &N_, &H_, &D_, &UB_, &BT_, &dy, &DYD_, &w_hh_f, &w_hh_r, &h_all,
-                  &gates, &lens, &dgates_x, &dgates_h, &ring, &ctrs, &err, &stamps, &dbp, &XM_,
-                  &camax, &NB_};
-  const bool ok = rnn_launch(fn, dim3(grid), dim3(BW * 64), args, lds_pad, st) == hipSuccess;
-  if (ok && h3 && camax != nullptr && camax_done != nullptr) *camax_done = true;
+}
+
+bool launch_fwd16(int ng, RnnShape s, RecFwd a, Handoff ho, hipStream_t st) {
+  Pick16 p = pick_fwd16(ng, s);
+  if (p.fn == nullptr) return false;
+  apply_knobs();
+  int UB = s.UB(), BT = s.BT();
+  void* args[] = {&s.t, &s.n, &s.h, &s.d, &UB, &BT, &a.xproj, &a.w_hh_f, &a.w_hh_r, &a.b_hh_f,
+                  &a.b_hh_r, &a.lens, &a.h_all, &a.gates, &ho.ring, &ho.ctrs, &ho.err,
+                  &ho.stamps, &p.same_xcd};
+  return rnn_launch(p.fn, dim3(p.grid), dim3(XT), args, ho.lds_pad, st) == hipSuccess;
+}
+
+// a.camax (nullable) is zeroed by the caller; ring and counters are sized for bt_launch groups
+// per direction (the LSTM's caller runs consecutive chunks when all tiles would not fit the
+// chip).  The one-gate form has no gates cache, dgh or dbp; only the GRU has dgh and dbp.
+bool launch_bwd16(int ng, RnnShape s, RecBwd a, Handoff ho, hipStream_t st, int tile0,
+                  int bt_launch, bool* camax_fused) {
+  if (camax_fused != nullptr) *camax_fused = false;
+  Pick16 p = pick_bwd16(ng, s, bt_launch);
+  if (p.fn == nullptr) return false;
+  apply_knobs();
+  int UB = s.UB(), NB = tile0 * GB;
+  void* args[] = {&s.t, &s.n, &s.h, &s.d, &UB, &bt_launch, &a.dy, &a.dy_dirs, &a.w_hh_f,
+                  &a.w_hh_r, &a.state, &a.gates, &a.lens, &a.dgx, &a.dgh, &ho.ring, &ho.ctrs,
+                  &ho.err, &ho.stamps, &a.dbp, &p.same_xcd, &a.camax, &NB};
+  const bool ok = rnn_launch(p.fn, dim3(p.grid), dim3(BW * 64), args, ho.lds_pad, st) == hipSuccess;
+  if (ok && p.h3 && a.camax != nullptr && camax_fused != nullptr) *camax_fused = true;
   return ok;
-}
-
-
-// ---------------------------------------------------------------------------------------
-// supported_rnns['rnn'] (nn.RNN, tanh) on the same machinery: the one-gate instantiations of
-// the fp16x3 forward / backward (NG = 1), same groups, hand-offs and rings (ds2_rnn_fwd_ws /
-// ds2_rnn_bwd_ws in gru.hip carve the workspace).  false = not covered (caller falls back to
-// the per-step kernels of rnn.hip).
-static const void* rnn_fwd_fn(int need) {
-#define DS2_RF(K) \
-  if (need <= K) return reinterpret_cast<const void*>(gru_fwd_x6_kernel<K, true, 1>);
-  DS2_RF(1) DS2_RF(2) DS2_RF(3) DS2_RF(4) DS2_RF(5) DS2_RF(6) DS2_RF(7)
-#undef DS2_RF
-  return nullptr;
-}
-
-static const void* rnn_bwd_fn(int UB) {
-  const int need = (UB + BW - 1) / BW;
-#define DS2_RB(K) \
-  if (need <= K) return reinterpret_cast<const void*>(gru_bwd_h3_kernel<K, 1>);
-  DS2_RB(1) DS2_RB(2) DS2_RB(3) DS2_RB(4) DS2_RB(5) DS2_RB(6) DS2_RB(7) DS2_RB(8)
-#undef DS2_RB
-  return nullptr;
-}
-
-bool launch_rnn_fwd_h3(int t_max, int n, int h, int num_dirs, const float* xproj,
-                       const float* w_hh_f, const float* w_hh_r, const float* b_hh_f,
-                       const float* b_hh_r, const int* lens, float* h_all, float* ring,
-                       unsigned* ctrs, unsigned* err, unsigned long long* stamps, size_t lds_pad,
-                       hipStream_t st) {
-  if ((h % GU) != 0) return false;
-  apply_spin_limit_env();
-  apply_rnn_tune_env();
-  const int UB = h / GU, BT = (n + GB - 1) / GB;
-  const void* fn = rnn_fwd_fn(((UB + 1) / 2 + XW - 1) / XW);
-  if (fn == nullptr) return false;
-  int XM_ = xcd_groups(UB, BT, num_dirs) ? 1 : 0;
-  const int grid = XM_ ? xgrp_grid(UB, BT, num_dirs) : mapped_grid(UB * num_dirs, BT);
-  int T_ = t_max, N_ = n, H_ = h, D_ = num_dirs, UB_ = UB, BT_ = BT;
-  float* gates = nullptr;
-  void* args[] = {&T_, &N_, &H_, &D_, &UB_, &BT_, &xproj, &w_hh_f, &w_hh_r, &b_hh_f,
-                  &b_hh_r, &lens, &h_all, &gates, &ring, &ctrs, &err, &stamps, &XM_};
-  return rnn_launch(fn, dim3(grid), dim3(XT), args, lds_pad, st) == hipSuccess;
-}
-
-// dgates: [T][N][D][H] gradient wrt the pre-activation; camax (nullable, zeroed by the
-// caller): its column maxima
-bool launch_rnn_bwd_h3(int t_max, int n, int h, int num_dirs, const float* dy, int dy_dirs,
-                       const float* w_hh_f, const float* w_hh_r, const float* h_all,
-                       const int* lens, float* dgates, float* ring, unsigned* ctrs, unsigned* err,
-                       unsigned long long* stamps, size_t lds_pad, hipStream_t st,
-                       unsigned* camax) {
-  if ((h % GU) != 0) return false;
-  apply_spin_limit_env();
-  apply_rnn_tune_env();
-  const int UB = h / GU, BT = (n + GB - 1) / GB;
-  const void* fn = rnn_bwd_fn(UB);
-  if (fn == nullptr) return false;
-  int XM_ = xcd_groups(UB, BT, num_dirs) ? 1 : 0;
-  const int grid = XM_ ? xgrp_grid(UB, BT, num_dirs) : mapped_grid(UB * num_dirs, BT);
-  int T_ = t_max, N_ = n, H_ = h, D_ = num_dirs, UB_ = UB, BT_ = BT, DYD_ = dy_dirs, NB_ = 0;
-  const float* gates = nullptr;
-  float* dgh = nullptr;
-  double* dbp = nullptr;
-  void* args[] = {&T_, &N_, &H_, &D_, &UB_, &BT_, &dy, &DYD_, &w_hh_f, &w_hh_r, &h_all,
-                  &gates, &lens, &dgates, &dgh, &ring, &ctrs, &err, &stamps, &dbp, &XM_,
-                  &camax, &NB_};
-  return rnn_launch(fn, dim3(grid), dim3(BW * 64), args, lds_pad, st) == hipSuccess;
-}
-
-// grid of the one-gate launches, -1 if they decline the shape
-int rnn_h3_grid(int n, int h, int num_dirs) {
-  if ((h % GU) != 0) return -1;
-  const int UB = h / GU, BT = (n + GB - 1) / GB;
-  if (rnn_bwd_fn(UB) == nullptr || rnn_fwd_fn(((UB + 1) / 2 + XW - 1) / XW) == nullptr) return -1;
-  return xcd_groups(UB, BT, num_dirs) ? xgrp_grid(UB, BT, num_dirs) : mapped_grid(UB * num_dirs, BT);
-}
-
-// supported_rnns['lstm'] backward on the same machinery (NG = 4): one launch over the
-// 16-sample tiles [tile0, tile0 + BT_launch) of the batch (the caller runs consecutive chunks
-// when all tiles would not fit the chip); ring and counters sized for BT_launch groups.
-// camax (nullable, zeroed by the caller): column maxima of dgates over every launch.
-static const void* lstm_bwd_fn(int UB) {
-  const int need = (UB + BW - 1) / BW;
-#define DS2_LB(K) \
-  if (need <= K) return reinterpret_cast<const void*>(gru_bwd_h3_kernel<K, 4>);
-  DS2_LB(1) DS2_LB(2) DS2_LB(3) DS2_LB(4) DS2_LB(5) DS2_LB(6) DS2_LB(7) DS2_LB(8)
-#undef DS2_LB
-  return nullptr;
-}
-
-// grid of one LSTM fp16x3 backward launch over bt_launch tiles, -1 if it declines the shape
-int lstm_h3_grid(int h, int num_dirs, int bt_launch) {
-  if ((h % GU) != 0) return -1;
-  const int UB = h / GU;
-  if (lstm_bwd_fn(UB) == nullptr) return -1;
-  return xcd_groups(UB, bt_launch, num_dirs) ? xgrp_grid(UB, bt_launch, num_dirs)
-                                            : mapped_grid(UB * num_dirs, bt_launch);
-}
-
-bool launch_lstm_bwd_h3(int t_max, int n, int h, int num_dirs, const float* dy, int dy_dirs,
-                        const float* w_hh_f, const float* w_hh_r, const float* c_all,
-                        const float* gates, const int* lens, float* dgates, float* ring,
-                        unsigned* ctrs, unsigned* err, size_t lds_pad, hipStream_t st,
-                        unsigned* camax, int tile0, int bt_launch) {
-  if ((h % GU) != 0) return false;
-  apply_spin_limit_env();
-  apply_rnn_tune_env();
-  const int UB = h / GU;
-  const void* fn = lstm_bwd_fn(UB);
-  if (fn == nullptr) return false;
-  int XM_ = xcd_groups(UB, bt_launch, num_dirs) ? 1 : 0;
-  const int grid = XM_ ? xgrp_grid(UB, bt_launch, num_dirs) : mapped_grid(UB * num_dirs, bt_launch);
-  int T_ = t_max, N_ = n, H_ = h, D_ = num_dirs, UB_ = UB, BT_ = bt_launch, DYD_ = dy_dirs;
-  int NB_ = tile0 * GB;
-  float* dgh = nullptr;
-  double* dbp = nullptr;
-  unsigned long long* stamps = nullptr;
-  void* args[] = {&T_, &N_, &H_, &D_, &UB_, &BT_, &dy, &DYD_, &w_hh_f, &w_hh_r, &c_all,
-                  &gates, &lens, &dgates, &dgh, &ring, &ctrs, &err, &stamps, &dbp, &XM_,
-                  &camax, &NB_};
-  return rnn_launch(fn, dim3(grid), dim3(BW * 64), args, lds_pad, st) == hipSuccess;
 }
 
 // ring bytes of the fp16x3 backward records (2 slots, doubled for the same-XCD plain copies)
@@ -1686,46 +1569,33 @@ size_t h3_bwd_ring_bytes(int n_tiles, int h, int num_dirs, int ng) {
   return 4 * (size_t)num_dirs * n_tiles * UB * hb * sizeof(float);
 }
 
-// the single-term LSTM backward (cfg4's bf16 mode): one launch over ceil(n / 32) 32-sample
-// tiles; false = not covered
-static const void* lstm_bwd_h1_fn(int UB) {
-  const int need = (UB + BW - 1) / BW;
-#define DS2_L1(K) \
-  if (need <= K) return reinterpret_cast<const void*>(lstm_bwd_h1_kernel<K>);
-  DS2_L1(1) DS2_L1(2) DS2_L1(4) DS2_L1(8)
-#undef DS2_L1
-  return nullptr;
+// The single-term LSTM backward (cfg4's bf16 mode): one launch over ceil(n / 32) 32-sample
+// tiles.  Its kernel takes a shorter argument list (no dgh, stamps, dbp or tile offset), so it
+// keeps a launcher of its own.
+static Pick16 pick_h1(const RnnShape& s) {
+  Pick16 p = {nullptr, -1, 0, false};
+  if ((s.h % GU) != 0) return p;
+  p.fn = pick_instance(kLstmBwdH1, (s.UB() + BW - 1) / BW);
+  if (p.fn != nullptr) p.grid = group_grid(s.UB(), s.BT(L1B), s.d, &p.same_xcd);
+  return p;
 }
 
-int lstm_h1_grid(int n, int h, int num_dirs) {
-  if ((h % GU) != 0) return -1;
-  const int UB = h / GU, BT = (n + L1B - 1) / L1B;
-  if (lstm_bwd_h1_fn(UB) == nullptr) return -1;
-  return xcd_groups(UB, BT, num_dirs) ? xgrp_grid(UB, BT, num_dirs) : mapped_grid(UB * num_dirs, BT);
-}
+int lstm_h1_grid(RnnShape s) { return pick_h1(s).grid; }
 
 size_t lstm_h1_ring_bytes(int n, int h, int num_dirs) {
   const size_t UB = (h + GU - 1) / GU, BT = (n + L1B - 1) / L1B;
   return 4 * (size_t)num_dirs * BT * UB * HBL1 * sizeof(float);
 }
 
-bool launch_lstm_bwd_h1(int t_max, int n, int h, int num_dirs, const float* dy, int dy_dirs,
-                        const float* w_hh_f, const float* w_hh_r, const float* c_all,
-                        const float* gates, const int* lens, float* dgates, float* ring,
-                        unsigned* ctrs, unsigned* err, size_t lds_pad, hipStream_t st,
-                        unsigned* camax) {
-  if ((h % GU) != 0) return false;
-  apply_spin_limit_env();
-  apply_rnn_tune_env();
-  const int UB = h / GU, BT = (n + L1B - 1) / L1B;
-  const void* fn = lstm_bwd_h1_fn(UB);
-  if (fn == nullptr) return false;
-  int XM_ = xcd_groups(UB, BT, num_dirs) ? 1 : 0;
-  const int grid = XM_ ? xgrp_grid(UB, BT, num_dirs) : mapped_grid(UB * num_dirs, BT);
-  int T_ = t_max, N_ = n, H_ = h, D_ = num_dirs, UB_ = UB, BT_ = BT, DYD_ = dy_dirs;
-  void* args[] = {&T_, &N_, &H_, &D_, &UB_, &BT_, &dy, &DYD_, &w_hh_f, &w_hh_r, &c_all,
-                  &gates, &lens, &dgates, &ring, &ctrs, &err, &XM_, &camax};
-  return rnn_launch(fn, dim3(grid), dim3(BW * 64), args, lds_pad, st) == hipSuccess;
+bool launch_lstm_bwd_h1(RnnShape s, RecBwd a, Handoff ho, hipStream_t st) {
+  Pick16 p = pick_h1(s);
+  if (p.fn == nullptr) return false;
+  apply_knobs();
+  int UB = s.UB(), BT = s.BT(L1B);
+  void* args[] = {&s.t, &s.n, &s.h, &s.d, &UB, &BT, &a.dy, &a.dy_dirs, &a.w_hh_f, &a.w_hh_r,
+                  &a.state, &a.gates, &a.lens, &a.dgx, &ho.ring, &ho.ctrs, &ho.err, &p.same_xcd,
+                  &a.camax};
+  return rnn_launch(p.fn, dim3(p.grid), dim3(BW * 64), args, ho.lds_pad, st) == hipSuccess;
 }
 
 }  // namespace ds2

@@ -35,7 +35,7 @@
 // deterministic sums).  Backward: per-producer flags (the record after a drain, then the
 // flag), each wave waiting for the flags of its own producers only; records multiplied in a
 // fixed order, three in flight per wave beside the one multiplied.
-#include "rnn_common.h"
+#include "rnn_host.h"
 
 #include <algorithm>
 
@@ -960,20 +960,14 @@ __global__ __launch_bounds__(256) void gru_xl_row_amax_kernel(const float* __res
 }
 
 // ---------------------------------------------------------------------------------------
-// host side (called by ds2_gru_fwd / ds2_gru_bwd in gru.hip with their workspace carve-up)
+// host side (rnn_host.h; called by ds2_gru_fwd / ds2_gru_bwd in gru.hip with their workspace
+// carve-up)
 
-static inline bool env_off(const char* name) {
-  const char* e = getenv(name);
-  return e != nullptr && e[0] == '0';
-}
 // DS2_GRU_XL=0 keeps the 16-unit kernels of gru_split.hip; the XCD-local kernels are fp16x3,
 // so DS2_GRU_X6=0 (fp32 MFMA) and DS2_GRU_H3[_BWD]=0 (bf16x6) select the others as before.
 // DS2_GRU_XL=2 (test) runs every group GLOBAL (sc1 stores), whatever the placement.
 static inline bool xl_enabled() { return !env_off("DS2_GRU_XL") && !env_off("DS2_GRU_X6"); }
-static inline int xl_force_global() {
-  const char* e = getenv("DS2_GRU_XL");
-  return (e != nullptr && e[0] == '2') ? 1 : 0;
-}
+static inline int xl_force_global() { return env_digit("DS2_GRU_XL") == 2 ? 1 : 0; }
 
 // the shapes the XCD-local kernels take: H a multiple of 32 with a group (H / 32 workgroups)
 // inside one XCD's 32 CUs, at most 8 groups (D x ceil(N / 8)), W_hh fragments within the
@@ -994,26 +988,16 @@ int gru_xl_active(int n, int h, int num_dirs) {
 // counter words the kernels use after the error word: 8 x 32 XCC ids, 8 x 32 flags, 8 mode words
 size_t gru_xl_ctr_words() { return 520; }
 
-// producers per wave: NPW in registers + one from LDS
-static const void* fwd_xl_fn(int UBX) {
-  const int need = (UBX + LW - 1) / LW;
-#define DS2_FXL(K) \
-  if (need <= K + 1) return reinterpret_cast<const void*>(gru_fwd_xl_kernel<K>);
-  DS2_FXL(1) DS2_FXL(3) DS2_FXL(6)
-#undef DS2_FXL
-  return nullptr;
-}
-
-static const void* bwd_xl_fn(int UBX, bool rows) {
-  const int need = (UBX + LW - 1) / LW;
-#define DS2_BXL(K)                                                                    \
-  if (need <= K + 1)                                                                  \
-    return rows ? reinterpret_cast<const void*>(gru_bwd_xl_kernel<K, true>)           \
-                : reinterpret_cast<const void*>(gru_bwd_xl_kernel<K, false>);
-  DS2_BXL(1) DS2_BXL(3) DS2_BXL(6)
-#undef DS2_BXL
-  return nullptr;
-}
+// K = producers per wave: K - 1 in registers + one from LDS
+static const Instance kFwdXl[] = {inst(2, gru_fwd_xl_kernel<1>), inst(4, gru_fwd_xl_kernel<3>),
+                                  inst(7, gru_fwd_xl_kernel<6>)};
+static const Instance kBwdXl[] = {inst(2, gru_bwd_xl_kernel<1, false>),
+                                  inst(4, gru_bwd_xl_kernel<3, false>),
+                                  inst(7, gru_bwd_xl_kernel<6, false>)};
+// the same with the row-maximum partials of dgates_x
+static const Instance kBwdXlRows[] = {inst(2, gru_bwd_xl_kernel<1, true>),
+                                      inst(4, gru_bwd_xl_kernel<3, true>),
+                                      inst(7, gru_bwd_xl_kernel<6, true>)};
 
 // ring bytes: forward 4 slots of 1-KB tiles, backward 2 slots of records (both within the
 // rings ds2_gru_fwd / ds2_gru_bwd carve for the 16-unit kernels)
@@ -1034,53 +1018,46 @@ static bool xl_prepare(unsigned* ctrs, size_t ctr_bytes, unsigned* zb, size_t nb
   return hipGetLastError() == hipSuccess;
 }
 
-// ctrs: the counter area ([ctrs, + ctr_bytes), `xl` and `err` inside it): these launches zero
-// it and set the ring's sentinels themselves, so the caller fills nothing when they answer
-// true; on false the caller prepares the area for the kernel it falls back to.  err_out
-// (nullable): the caller's status word, OR-ed by the kernel itself (no fold launch).
-bool launch_gru_fwd_xl(int t_max, int n, int h, int num_dirs, const float* xproj,
-                       const float* w_hh_f, const float* w_hh_r, const float* b_hh_f,
-                       const float* b_hh_r, const int* lens, float* h_all, float* gates,
-                       float* ring, unsigned* ctrs, size_t ctr_bytes, unsigned* xl, unsigned* err,
-                       unsigned* err_out, unsigned long long* stamps, size_t lds_pad,
-                       hipStream_t st) {
-  if (gru_xl_groups(n, h, num_dirs) == 0 || env_off("DS2_GRU_H3")) return false;
+// The counter area [ho.ctrs, + ho.ctr_bytes) holds ho.err (the error word of the 16-unit
+// launch over the same batch) and, right behind it, these kernels' own words.  The launches
+// zero the area and set the ring's sentinels themselves, so the caller fills nothing when
+// they answer true; on false the caller prepares the area for the kernel it falls back to.
+// ho.err_out (nullable): the caller's status word, OR-ed by the kernel itself (no fold launch).
+bool launch_gru_fwd_xl(RnnShape s, RecFwd a, Handoff ho, hipStream_t st) {
+  if (gru_xl_groups(s.n, s.h, s.d) == 0 || env_off("DS2_GRU_H3")) return false;
   apply_spin_limit_env();
   apply_rnn_tune_env();
-  const int UBX = h / LU, BTX = (n + LB - 1) / LB;
-  const void* fn = fwd_xl_fn(UBX);
+  int UBX = s.h / LU, BTX = s.BT(LB), FG = xl_force_global();
+  const void* fn = pick_instance(kFwdXl, (UBX + LW - 1) / LW);
   if (fn == nullptr) return false;
-  if (!xl_prepare(ctrs, ctr_bytes, nullptr, 0, ring, gru_xl_ring_bytes(n, h, num_dirs, false), st))
+  if (!xl_prepare(ho.ctrs, ho.ctr_bytes, nullptr, 0, ho.ring,
+                  gru_xl_ring_bytes(s.n, s.h, s.d, false), st))
     return false;
-  int T_ = t_max, N_ = n, H_ = h, D_ = num_dirs, UB_ = UBX, BT_ = BTX, FG_ = xl_force_global();
-  void* args[] = {&T_, &N_, &H_, &D_, &UB_, &BT_, &xproj, &w_hh_f, &w_hh_r, &b_hh_f,
-                  &b_hh_r, &lens, &h_all, &gates, &ring, &xl, &err, &err_out, &stamps, &FG_};
-  return rnn_launch(fn, dim3(8 * UBX), dim3(LT), args, lds_pad, st) == hipSuccess;
+  unsigned* xl = ho.err + 1;
+  void* args[] = {&s.t, &s.n, &s.h, &s.d, &UBX, &BTX, &a.xproj, &a.w_hh_f, &a.w_hh_r, &a.b_hh_f,
+                  &a.b_hh_r, &a.lens, &a.h_all, &a.gates, &ho.ring, &xl, &ho.err, &ho.err_out,
+                  &ho.stamps, &FG};
+  return rnn_launch(fn, dim3(8 * UBX), dim3(LT), args, ho.lds_pad, st) == hipSuccess;
 }
 
-// dbp: [ceil(n / 8)][D][4][H] partials (nullable); camax as launch_gru_bwd_x6's (zeroed by the
-// preparation launch); rowp: [T N][D][h / 32] row-maximum partials of dgates_x (nullable)
-bool launch_gru_bwd_xl(int t_max, int n, int h, int num_dirs, const float* dy, int dy_dirs,
-                       const float* w_hh_f, const float* w_hh_r, const float* h_all,
-                       const float* gates, const int* lens, float* dgates_x, float* dgates_h,
-                       float* ring, unsigned* ctrs, size_t ctr_bytes, unsigned* xl, unsigned* err,
-                       unsigned* err_out, unsigned long long* stamps, double* dbp, size_t lds_pad,
-                       hipStream_t st, unsigned* camax, float* rowp) {
-  if (gru_xl_groups(n, h, num_dirs) == 0 || env_off("DS2_GRU_H3_BWD")) return false;
+// a.dbp: [ceil(n / 8)][D][4][H] partials (nullable); a.camax as launch_bwd16's, but zeroed by
+// the preparation launch; a.rowp: [T N][D][h / 32] row-maximum partials of dgates_x (nullable)
+bool launch_gru_bwd_xl(RnnShape s, RecBwd a, Handoff ho, hipStream_t st) {
+  if (gru_xl_groups(s.n, s.h, s.d) == 0 || env_off("DS2_GRU_H3_BWD")) return false;
   apply_spin_limit_env();
   apply_rnn_tune_env();
-  const int UBX = h / LU, BTX = (n + LB - 1) / LB;
-  const void* fn = bwd_xl_fn(UBX, rowp != nullptr);
+  int UBX = s.h / LU, BTX = s.BT(LB), FG = xl_force_global();
+  const int need = (UBX + LW - 1) / LW;
+  const void* fn = a.rowp != nullptr ? pick_instance(kBwdXlRows, need) : pick_instance(kBwdXl, need);
   if (fn == nullptr) return false;
-  if (!xl_prepare(ctrs, ctr_bytes, camax, camax != nullptr ? (size_t)2 * num_dirs * 3 * h : 0,
-                  nullptr, 0, st))
+  if (!xl_prepare(ho.ctrs, ho.ctr_bytes, a.camax,
+                  a.camax != nullptr ? (size_t)2 * s.d * 3 * s.h : 0, nullptr, 0, st))
     return false;
-  int T_ = t_max, N_ = n, H_ = h, D_ = num_dirs, UB_ = UBX, BT_ = BTX, DYD_ = dy_dirs;
-  int FG_ = xl_force_global();
-  void* args[] = {&T_, &N_, &H_, &D_, &UB_, &BT_, &dy, &DYD_, &w_hh_f, &w_hh_r, &h_all,
-                  &gates, &lens, &dgates_x, &dgates_h, &ring, &xl, &err, &err_out, &stamps, &dbp,
-                  &camax, &rowp, &FG_};
-  return rnn_launch(fn, dim3(8 * UBX), dim3(LT), args, lds_pad, st) == hipSuccess;
+  unsigned* xl = ho.err + 1;
+  void* args[] = {&s.t, &s.n, &s.h, &s.d, &UBX, &BTX, &a.dy, &a.dy_dirs, &a.w_hh_f, &a.w_hh_r,
+                  &a.state, &a.gates, &a.lens, &a.dgx, &a.dgh, &ho.ring, &xl, &ho.err,
+                  &ho.err_out, &ho.stamps, &a.dbp, &a.camax, &a.rowp, &FG};
+  return rnn_launch(fn, dim3(8 * UBX), dim3(LT), args, ho.lds_pad, st) == hipSuccess;
 }
 
 // the row-maximum partials of launch_gru_bwd_xl: bytes, and their reduction to out[t_max n]

@@ -17,7 +17,7 @@
 // Persistent variants (one cooperative launch per layer, W_hh in registers, the
 // hand-off of gru.hip) run when the grid fits the chip; otherwise one launch per
 // time step carries the cell state through a ping-pong buffer.
-#include "rnn_common.h"
+#include "rnn_host.h"
 
 #include <algorithm>
 
@@ -794,42 +794,49 @@ __global__ __launch_bounds__(GT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
   }
 }
 
-// per-step kernels: forward needs <= 32 (H <= 1024), backward <= 64 (2048-column chunks)
-static int lstm_pick_ksw(int per) {
-  const int opts[] = {8, 16, 32, 64};
-  for (int k : opts)
-    if (per <= k) return k;
-  return -1;
-}
-
-// gru_split.hip: the fp16x3 backward with the LSTM cell (gru_bwd_h3_kernel<., 4>)
-int lstm_h3_grid(int h, int num_dirs, int bt_launch);
-bool launch_lstm_bwd_h3(int t_max, int n, int h, int num_dirs, const float* dy, int dy_dirs,
-                        const float* w_hh_f, const float* w_hh_r, const float* c_all,
-                        const float* gates, const int* lens, float* dgates, float* ring,
-                        unsigned* ctrs, unsigned* err, size_t lds_pad, hipStream_t st,
-                        unsigned* camax, int tile0, int bt_launch);
-size_t h3_bwd_ring_bytes(int n_tiles, int h, int num_dirs, int ng);
-// gru_split.hip: the single-term backward of cfg4's bf16 mode (lstm_bwd_h1_kernel)
-int lstm_h1_grid(int n, int h, int num_dirs);
-size_t lstm_h1_ring_bytes(int n, int h, int num_dirs);
-bool launch_lstm_bwd_h1(int t_max, int n, int h, int num_dirs, const float* dy, int dy_dirs,
-                        const float* w_hh_f, const float* w_hh_r, const float* c_all,
-                        const float* gates, const int* lens, float* dgates, float* ring,
-                        unsigned* ctrs, unsigned* err, size_t lds_pad, hipStream_t st,
-                        unsigned* camax);
-
 }  // namespace ds2
 
 using namespace ds2;
 
-extern "C" {
-
-// counters (one per group) + error word + per-producer flags (64 per group)
-static inline size_t lstm_counter_bytes(int n, int num_dirs) {
-  const size_t groups = (size_t)num_dirs * ((n + GB - 1) / GB);
-  return align256((groups + 1 + groups * 64) * sizeof(unsigned));
-}
+// forward direct-operand kernels [fp16x3 (DS2_LSTM_H3, default) or fp32 MFMA][BTS - 1], K =
+// 16-unit blocks per wave.  8 blocks per wave (H > 512): W_hh's 128 fragment registers leave
+// no room for the sentinel spin's live state (it spills), so those run the flag hand-off
+// (HM = 0); the others the sentinel ring (HM = 1).
+static const Instance kFwdDop[2][2][4] = {
+    {{inst(1, lstm_fwd_dop_kernel<1, 1, 1>), inst(2, lstm_fwd_dop_kernel<2, 1, 1>),
+      inst(4, lstm_fwd_dop_kernel<4, 1, 1>), inst(8, lstm_fwd_dop_kernel<8, 0, 1>)},
+     {inst(1, lstm_fwd_dop_kernel<1, 1, 2>), inst(2, lstm_fwd_dop_kernel<2, 1, 2>),
+      inst(4, lstm_fwd_dop_kernel<4, 1, 2>), inst(8, lstm_fwd_dop_kernel<8, 0, 2>)}},
+    {{inst(1, lstm_fwd_dop_kernel<1, 1, 1, true>), inst(2, lstm_fwd_dop_kernel<2, 1, 1, true>),
+      inst(4, lstm_fwd_dop_kernel<4, 1, 1, true>), inst(8, lstm_fwd_dop_kernel<8, 0, 1, true>)},
+     {inst(1, lstm_fwd_dop_kernel<1, 1, 2, true>), inst(2, lstm_fwd_dop_kernel<2, 1, 2, true>),
+      inst(4, lstm_fwd_dop_kernel<4, 1, 2, true>), inst(8, lstm_fwd_dop_kernel<8, 0, 2, true>)}}};
+// LDS-staged persistent forward [BTS - 1], K = k-steps per wave
+static const Instance kFwdPersist[2][4] = {
+    {inst(8, lstm_fwd_persist_kernel<8, 1>), inst(16, lstm_fwd_persist_kernel<16, 1>),
+     inst(25, lstm_fwd_persist_kernel<25, 1>), inst(32, lstm_fwd_persist_kernel<32, 1>)},
+    {inst(8, lstm_fwd_persist_kernel<8, 2>), inst(16, lstm_fwd_persist_kernel<16, 2>),
+     inst(25, lstm_fwd_persist_kernel<25, 2>), inst(32, lstm_fwd_persist_kernel<32, 2>)}};
+// per-step kernels: forward needs <= 32 (H <= 1024), backward <= 64 (2048-column chunks)
+static const Instance kFwdStep[] = {inst(8, lstm_fwd_step_kernel<8>),
+                                    inst(16, lstm_fwd_step_kernel<16>),
+                                    inst(32, lstm_fwd_step_kernel<32>)};
+static const Instance kBwdStep[] = {
+    inst(8, lstm_bwd_step_kernel<8>), inst(16, lstm_bwd_step_kernel<16>),
+    inst(32, lstm_bwd_step_kernel<32>), inst(64, lstm_bwd_step_kernel<64>)};
+// LDS-staged persistent backward: (k-steps per wave per chunk, chunks, BTS), matched exactly;
+// fn the interleaved layout, fx the same-XCD groups
+struct LstmBwdPersist {
+  int k, c, b;
+  const void *fn, *fx;
+};
+#define DS2_LBP(K, C, B)                                                              \
+  {K, C, B, reinterpret_cast<const void*>(lstm_bwd_persist_kernel<K, C, B, false>),   \
+   reinterpret_cast<const void*>(lstm_bwd_persist_kernel<K, C, B, true>)}
+static const LstmBwdPersist kBwdPersist[] = {
+    DS2_LBP(8, 1, 1),  DS2_LBP(16, 1, 1), DS2_LBP(25, 1, 1), DS2_LBP(32, 1, 1), DS2_LBP(48, 1, 1),
+    DS2_LBP(64, 1, 1), DS2_LBP(48, 2, 1), DS2_LBP(64, 2, 1), DS2_LBP(32, 1, 2), DS2_LBP(32, 2, 2)};
+#undef DS2_LBP
 
 // Batch chunking of the persistent launches: the largest number of 16-sample tiles per
 // launch whose grid fits the chip (one workgroup per CU); a batch with more tiles runs as
@@ -848,37 +855,81 @@ static inline int lstm_bts(int UB, int D, int BT) {
   const bool fits2 = mapped_grid(UB * D, (BT + 1) / 2) <= num_cus();
   return mapped_grid(UB * D, BT) > num_cus() && fits2 ? 2 : 1;
 }
-
-// ring of 1-KB hand-off tiles of the direct-operand forward: kRingSlots slots of
-// (direction, 16-sample tile rounded up to a 32-sample workgroup, unit block)
-static inline size_t lstm_ring_bytes(int n, int h, int num_dirs) {
-  const size_t UB = (h + GU - 1) / GU, BT2 = 2 * (((size_t)n + 2 * GB - 1) / (2 * GB));
-  return align256(kRingSlots * (size_t)num_dirs * BT2 * UB * 256 * sizeof(float));
+// the LDS-staged backward's: 32-sample workgroups stage chunks of at most 1024 gate columns
+// (32 rows in LDS); past two chunks (H > 512) the W_hh^T fragments and a chunk's in-flight
+// loads exceed the 256 VGPRs, so the batch runs in 16-sample chunks instead
+static inline int lstm_bwd_bts(const RnnShape& s) {
+  const int bts = lstm_bts(s.UB(), s.d, s.BT());
+  return bts == 2 && 4 * s.h > 2 * 4 * GW * 32 ? 1 : bts;
 }
-constexpr unsigned kLstmDopPadLds = 80 * 1024;   // dynamic LDS: one workgroup per CU
 
-// the recurrences' W_hh products on fp16x3 (default since round 5; DS2_LSTM_H3=0 keeps the
-// fp32-MFMA kernels)
-static inline bool lstm_h3_on() {
-  const char* e = getenv("DS2_LSTM_H3");
-  return !(e != nullptr && e[0] == '0');
+// ---------------------------------------------------------------------------------------
+// Workspace layouts.  Counter regions: group counters + error word + per-producer flags (64
+// per group); the fp16x3 backward's as the GRU's (64 flags and 64 XCC ids per group).
+static size_t lstm_counter_bytes(const RnnShape& s, int per_group) {
+  const size_t groups = s.groups();
+  return align256((groups + 1 + groups * per_group) * sizeof(unsigned));
 }
+
+struct LstmFwdLayout {
+  size_t wp;   // W_hh in MFMA-fragment order (LDS-staged and per-step kernels)
+  size_t cs;   // the carried cell state, two steps
+  size_t ctrs, ctr_bytes;
+  // ring of 1-KB hand-off tiles of the direct-operand forward: kRingSlots slots of
+  // (direction, 16-sample tile rounded up to a 32-sample workgroup, unit block)
+  size_t ring, ring_bytes;
+  size_t total;
+};
+static LstmFwdLayout lstm_fwd_layout(const RnnShape& s) {
+  LstmFwdLayout L;
+  Carve c;
+  const int64_t UB = s.UB(), KS = (s.h + 3) / 4;
+  const size_t BT2 = 2 * (size_t)s.BT(2 * GB);
+  L.wp = c.take((size_t)(s.d * UB * KS * 4 * 64) * sizeof(float));
+  L.cs = c.take((size_t)2 * s.n * s.d * s.h * sizeof(float));
+  L.ctr_bytes = lstm_counter_bytes(s, 64);
+  L.ctrs = c.take(L.ctr_bytes);
+  L.ring_bytes = align256(kRingSlots * (size_t)s.d * BT2 * UB * 256 * sizeof(float));
+  L.ring = c.take(L.ring_bytes);
+  c.take(256);
+  L.total = c.end;
+  return L;
+}
+
+struct LstmBwdLayout {
+  size_t wpt;   // W_hh^T in MFMA-fragment order
+  size_t dcs;   // the carried dc / dh, two steps
+  size_t ctrs, ctr_bytes;     // the LDS-staged kernels' counters
+  size_t ctrs3, ctr3_bytes;   // the fp16x3 and single-term kernels' counters ...
+  size_t ring3;               // ... and record ring (the larger of the two forms')
+  size_t total;
+};
+static LstmBwdLayout lstm_bwd_layout(const RnnShape& s) {
+  LstmBwdLayout L;
+  Carve c;
+  const int64_t UB = s.UB(), KS = s.h;
+  L.wpt = c.take((size_t)(s.d * UB * KS * 64) * sizeof(float));
+  L.dcs = c.take((size_t)2 * s.n * s.d * s.h * sizeof(float));
+  L.ctr_bytes = lstm_counter_bytes(s, 64);
+  L.ctrs = c.take(L.ctr_bytes);
+  L.ctr3_bytes = lstm_counter_bytes(s, 128);
+  L.ctrs3 = c.take(L.ctr3_bytes);
+  L.ring3 = c.take(std::max(h3_bwd_ring_bytes(s.BT(), s.h, s.d, 4),
+                            lstm_h1_ring_bytes(s.n, s.h, s.d)));
+  c.take(256);
+  L.total = c.end;
+  return L;
+}
+
+extern "C" {
 
 size_t ds2_lstm_fwd_workspace_size(int n, int h, int num_dirs) {
-  const int64_t UB = (h + GU - 1) / GU;
-  const int64_t KS = (h + 3) / 4;
-  return align256((size_t)(num_dirs * UB * KS * 4 * 64) * sizeof(float)) +
-         align256((size_t)2 * n * num_dirs * h * sizeof(float)) + lstm_counter_bytes(n, num_dirs) +
-         lstm_ring_bytes(n, h, num_dirs) + 256;
+  return lstm_fwd_layout(RnnShape{0, n, h, num_dirs}).total;
 }
 
-#define DS2_LFWD_CASE(K)                                                                    \
-  case K:                                                                                   \
-    hipLaunchKernelGGL(lstm_fwd_step_kernel<K>, dim3(grid), dim3(GT), 0, st, s, t_max, n, h, \
-                       num_dirs, UB, BT, xproj, wp, b_hh_f, b_hh_r, lens, h_all, c_all, gates, \
-                       cs);                                                                 \
-    break;
-
+// Ladder (DESIGN.md "Recurrent dispatch"): the direct-operand persistent kernels (H % 16 == 0;
+// fp16x3, or fp32 MFMA with DS2_LSTM_H3=0), the LDS-staged persistent kernels (H % 4 == 0),
+// one launch per step (also DS2_RNN_PERSISTENT=0).
 ds2_status_t ds2_lstm_fwd(int t_max, int n, int h, int num_dirs, const float* xproj,
                           const float* w_hh_f, const float* w_hh_r, const float* b_hh_f,
                           const float* b_hh_r, const int* lens, float* h_all, float* c_all,
@@ -887,152 +938,105 @@ ds2_status_t ds2_lstm_fwd(int t_max, int n, int h, int num_dirs, const float* xp
   if (t_max < 0 || n < 0 || h < 1 || (num_dirs != 1 && num_dirs != 2)) return DS2_INVALID_VALUE;
   if (h > LKC_FWD) return DS2_UNSUPPORTED_SHAPE;
   if (t_max == 0 || n == 0) return DS2_OK;
-  if (ws == nullptr || ws_bytes < ds2_lstm_fwd_workspace_size(n, h, num_dirs))
-    return DS2_WORKSPACE_TOO_SMALL;
+  const RnnShape s = {t_max, n, h, num_dirs};
+  const LstmFwdLayout L = lstm_fwd_layout(s);
+  if (ws == nullptr || ws_bytes < L.total) return DS2_WORKSPACE_TOO_SMALL;
   if (num_dirs == 1) {
     w_hh_r = w_hh_f;
     b_hh_r = b_hh_f;
   }
   hipStream_t st = as_stream(stream);
   apply_spin_limit_env();
-  const int UB = (h + GU - 1) / GU;
+  int T = t_max, N = n, H = h, D = num_dirs, UB = s.UB(), BT = s.BT();
   const int KS = (h + 3) / 4;
-  const int BT = (n + GB - 1) / GB;
-  const int ksw = lstm_pick_ksw((KS + GW - 1) / GW);
-  if (ksw < 0 || ksw > 32) return DS2_UNSUPPORTED_SHAPE;
-  float* wp = static_cast<float*>(ws);
-  size_t off = align256((size_t)num_dirs * UB * KS * 4 * 64 * sizeof(float));
-  float* cs = reinterpret_cast<float*>(static_cast<char*>(ws) + off);
-  off += align256((size_t)2 * n * num_dirs * h * sizeof(float));
-  unsigned* ctrs = reinterpret_cast<unsigned*>(static_cast<char*>(ws) + off);
-  float* ring = reinterpret_cast<float*>(static_cast<char*>(ws) + off +
-                                         lstm_counter_bytes(n, num_dirs));
-  // direct-operand persistent kernels (W_hh read unpacked; no LDS staging of h)
-  if (persistent_enabled() && (h % GU) == 0 && UB <= 8 * GW &&
-      (int64_t)t_max * n * num_dirs * h * 4 < (1ll << 31)) {
-    int hm = 1;   // the sentinel ring
-    const int bts = lstm_bts(UB, num_dirs, BT);
-    const int BTW = (BT + bts - 1) / bts;
-    const int ct = lstm_chunk_tiles(UB, num_dirs, BTW);
-    // NBW = blocks per wave, rounded up to an instantiated 1, 2, 4 or 8 (extra blocks are
-    // predicated off)
-    const int need = (UB + GW - 1) / GW;
-    const int nbw = need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : 8;
-    // 8 blocks per wave (H > 512): W_hh's 128 fragment registers leave no room for the
-    // sentinel spin's live state (it spills), so those run the flag hand-off
-    if (nbw == 8) hm = 0;
-    const void* fn = nullptr;
-    const bool h3 = lstm_h3_on();
-#define DS2_LDOP(K, HM)                                                                       \
-  case K:                                                                                     \
-    if (h3)                                                                                   \
-      fn = bts == 2 ? reinterpret_cast<const void*>(lstm_fwd_dop_kernel<K, HM, 2, true>)      \
-                    : reinterpret_cast<const void*>(lstm_fwd_dop_kernel<K, HM, 1, true>);     \
-    else                                                                                      \
-      fn = bts == 2 ? reinterpret_cast<const void*>(lstm_fwd_dop_kernel<K, HM, 2>)            \
-                    : reinterpret_cast<const void*>(lstm_fwd_dop_kernel<K, HM, 1>);           \
-    break;
-    switch (nbw) {
-      DS2_LDOP(1, 1) DS2_LDOP(2, 1) DS2_LDOP(4, 1) DS2_LDOP(8, 0)
-      default: break;
-    }
-#undef DS2_LDOP
-    bool ok = fn != nullptr && mapped_grid(UB * num_dirs, ct) <= num_cus();
-    bool launched = false;
-    for (int b0 = 0; ok && b0 < BTW; b0 += ct) {
-      int T_ = t_max, N_ = n, H_ = h, D_ = num_dirs, UB_ = UB, BT_ = std::min(ct, BTW - b0);
-      int NB_ = b0 * GB * bts;
-      unsigned* err = ctrs + num_dirs * BT_;
-      if (hipMemsetAsync(ctrs, 0, lstm_counter_bytes(n, num_dirs), st) != hipSuccess)
-        return launch_status("ds2_lstm counters");
-      if (hm != 0 && hipMemsetAsync(ring, 0xFF, lstm_ring_bytes(n, h, num_dirs), st) != hipSuccess)
-        return launch_status("ds2_lstm ring");
-      // same-XCD groups (DS2_GRU_XCD) where they tile the XCDs: cfg4 bf16 144.9 -> 143.7 ms
-      int XG_ = xcd_groups_on() && xgrp_fits(UB, BT_, num_dirs) ? 1 : 0;
-      void* args[] = {&T_, &N_, &H_, &D_, &UB_, &BT_, &xproj, &w_hh_f, &w_hh_r, &b_hh_f,
-                      &b_hh_r, &lens, &h_all, &c_all, &gates, &ring, &ctrs, &err, &NB_, &XG_};
-      ok = rnn_launch(fn,
-                      dim3(XG_ ? xgrp_grid(UB, BT_, num_dirs) : mapped_grid(UB * num_dirs, BT_)),
-                      dim3(GT), args, kLstmDopPadLds, st) == hipSuccess;
-      if (ok) fold_err(err, err_out, st);
-      if (!ok && launched) return launch_status("ds2_lstm_fwd chunk");
-      launched = launched || ok;
-    }
-    if (ok) return launch_status("ds2_lstm_fwd");
-    (void)hipGetLastError();
+  const void* step_fn = pick_instance(kFwdStep, (KS + GW - 1) / GW);
+  if (step_fn == nullptr) return DS2_UNSUPPORTED_SHAPE;
+  float* wp = ws_at<float>(ws, L.wp);
+  float* cs = ws_at<float>(ws, L.cs);
+  const Handoff ho = {ws_at<float>(ws, L.ring), ws_at<unsigned>(ws, L.ctrs), L.ctr_bytes,
+                      nullptr, err_out, nullptr, kDopPadLds};
+  const int bts = lstm_bts(UB, D, BT);
+  const int BTW = (BT + bts - 1) / bts;   // workgroup batch tiles
+  const int ct = lstm_chunk_tiles(UB, D, BTW);
+  const bool persistent = persistent_enabled() && s.fits32(1) && mapped_grid(UB * D, ct) <= num_cus();
+  ds2_status_t rc = DS2_OK;
+  // direct-operand persistent kernels (W_hh read unpacked; no LDS staging of h); blocks per
+  // wave rounded up to an instantiated 1, 2, 4 or 8 (extra blocks are predicated off)
+  if (persistent && (h % GU) == 0 && UB <= 8 * GW) {
+    const int nbw = (UB + GW - 1) / GW;
+    const void* fn = pick_instance(kFwdDop[env_off("DS2_LSTM_H3") ? 0 : 1][bts - 1], nbw);
+    const size_t ring_fill = nbw > 4 ? 0 : L.ring_bytes;   // the sentinel ring (HM = 1)
+    if (fn != nullptr &&
+        for_each_chunk("ds2_lstm_fwd", ho, D, BTW, ct, ring_fill, st, &rc,
+                       [&](int b0, int bt, Handoff c) {
+                         int NB = b0 * GB * bts, XG = 0;
+                         // same-XCD groups where they tile the XCDs: cfg4 bf16 144.9 -> 143.7 ms
+                         const int grid = group_grid(UB, bt, D, &XG);
+                         void* args[] = {&T, &N, &H, &D, &UB, &bt, &xproj, &w_hh_f, &w_hh_r,
+                                         &b_hh_f, &b_hh_r, &lens, &h_all, &c_all, &gates, &c.ring,
+                                         &c.ctrs, &c.err, &NB, &XG};
+                         return launch_fn(fn, grid, GT, args, kDopPadLds, st);
+                       }))
+      return rc;
   }
   hipLaunchKernelGGL(pack_fwd_kernel<4>, dim3(grid_cap((int64_t)num_dirs * UB * KS * 256)),
                      dim3(256), 0, st, w_hh_f, w_hh_r, h, num_dirs, UB, KS, wp);
-  const int grid = mapped_grid(UB * num_dirs, BT);
   const int kp = persist_ksw((KS + GW - 1) / GW, LKC_FWD);
-  const int bts = lstm_bts(UB, num_dirs, BT);
-  const int BTW = (BT + bts - 1) / bts;                   // workgroup batch tiles
-  const int ct = lstm_chunk_tiles(UB, num_dirs, BTW);
-  if (persistent_enabled() && (h % 4) == 0 && mapped_grid(UB * num_dirs, ct) <= num_cus() &&
-      kp > 0 && kp <= 32 && (int64_t)t_max * n * num_dirs * h * 4 < (1ll << 31)) {
-    const void* fn = nullptr;
-#define DS2_LFP(K)                                                                        \
-  case K:                                                                                 \
-    fn = bts == 2 ? reinterpret_cast<const void*>(lstm_fwd_persist_kernel<K, 2>)          \
-                  : reinterpret_cast<const void*>(lstm_fwd_persist_kernel<K, 1>);         \
-    break;
-    switch (kp) {
-      DS2_LFP(8) DS2_LFP(16) DS2_LFP(25) DS2_LFP(32)
-      default: break;
-    }
-#undef DS2_LFP
-    bool ok = fn != nullptr;
-    for (int b0 = 0; ok && b0 < BTW; b0 += ct) {
-      int T_ = t_max, N_ = n, H_ = h, D_ = num_dirs, UB_ = UB, BT_ = std::min(ct, BTW - b0);
-      int NB_ = b0 * GB * bts;
-      unsigned* err = ctrs + num_dirs * BT_;
-      if (hipMemsetAsync(ctrs, 0, lstm_counter_bytes(n, num_dirs), st) != hipSuccess)
-        return launch_status("ds2_lstm counters");
-      void* args[] = {&T_, &N_, &H_, &D_, &UB_, &BT_, &xproj, &wp, &b_hh_f, &b_hh_r, &lens,
-                      &h_all, &c_all, &gates, &ctrs, &err, &NB_};
-      ok = rnn_launch(fn, dim3(mapped_grid(UB * num_dirs, BT_)), dim3(GT), args,
-                                      0, st) == hipSuccess;
-      if (ok) fold_err(err, err_out, st);
-      if (!ok && b0 > 0) return launch_status("ds2_lstm_fwd chunk");
-    }
-    if (ok) return launch_status("ds2_lstm_fwd");
-    (void)hipGetLastError();   // fall back to one launch per step
+  if (persistent && (h % 4) == 0 && kp > 0 && kp <= 32) {
+    const void* fn = pick_instance(kFwdPersist[bts - 1], kp);
+    if (fn != nullptr &&
+        for_each_chunk("ds2_lstm_fwd", ho, D, BTW, ct, 0, st, &rc,
+                       [&](int b0, int bt, Handoff c) {
+                         int NB = b0 * GB * bts;
+                         void* args[] = {&T, &N, &H, &D, &UB, &bt, &xproj, &wp, &b_hh_f, &b_hh_r,
+                                         &lens, &h_all, &c_all, &gates, &c.ctrs, &c.err, &NB};
+                         return launch_fn(fn, mapped_grid(UB * D, bt), GT, args, 0, st);
+                       }))
+      return rc;   // else one launch per step
   }
-  for (int s = 0; s < t_max; ++s) {
-    switch (ksw) {
-      DS2_LFWD_CASE(8) DS2_LFWD_CASE(16) DS2_LFWD_CASE(32)
-    }
-  }
+  const int grid = mapped_grid(UB * D, BT);
+  int step = 0;
+  void* args[] = {&step, &T, &N, &H, &D, &UB, &BT, &xproj, &wp, &b_hh_f, &b_hh_r, &lens,
+                  &h_all, &c_all, &gates, &cs};
+  for (step = 0; step < t_max; ++step)
+    (void)hipLaunchKernel(step_fn, dim3(grid), dim3(GT), args, 0, st);
   return launch_status("ds2_lstm_fwd");
-}
-
-// the fp16x3 backward's counters (as the GRU's: group counters, error word, 64 flags and 64
-// XCC ids per group) and record ring, after the fp32 kernels' regions
-static inline size_t lstm_h3_ctr_bytes(int n, int num_dirs) {
-  const size_t groups = (size_t)num_dirs * ((n + GB - 1) / GB);
-  return align256((groups + 1 + groups * 128) * sizeof(unsigned));
-}
-static size_t lstm_bwd_ws_base(int n, int h, int num_dirs) {
-  const int64_t UB = (h + GU - 1) / GU;
-  const int64_t KS = h;
-  return align256((size_t)(num_dirs * UB * KS * 64) * sizeof(float)) +
-         align256((size_t)2 * n * num_dirs * h * sizeof(float)) + lstm_counter_bytes(n, num_dirs);
 }
 
 size_t ds2_lstm_bwd_workspace_size(int n, int h, int num_dirs) {
   if (n < 1 || h < 1 || num_dirs < 1) return 256;
-  const size_t r3 = h3_bwd_ring_bytes((n + GB - 1) / GB, h, num_dirs, 4);
-  const size_t r1 = lstm_h1_ring_bytes(n, h, num_dirs);
-  return lstm_bwd_ws_base(n, h, num_dirs) + lstm_h3_ctr_bytes(n, num_dirs) +
-         align256(r3 > r1 ? r3 : r1) + 256;
+  return lstm_bwd_layout(RnnShape{0, n, h, num_dirs}).total;
 }
 
 // the single-term backward (cfg4's bf16 mode) as launched: its grid, 0 when it declines
-static int lstm_h1_launch_grid(int t_max, int n, int h, int num_dirs) {
-  if (!persistent_enabled() || (h % GU) != 0) return 0;
-  if ((int64_t)t_max * n * num_dirs * 4 * h * 4 >= (1ll << 31)) return 0;
-  const int g = lstm_h1_grid(n, h, num_dirs);
+static int lstm_h1_launch_grid(const RnnShape& s) {
+  if (!persistent_enabled() || (s.h % GU) != 0 || !s.fits32(4)) return 0;
+  const int g = lstm_h1_grid(s);
   return g > 0 && g <= num_cus() ? g : 0;
+}
+
+// the fp16x3 backward's launch: 16-sample tiles per launch (consecutive launches cover the
+// batch), 0 when it declines the shape
+static int lstm_h3_tiles(const RnnShape& s) {
+  if (env_off("DS2_LSTM_H3") || !persistent_enabled() || (s.h % GU) != 0 || !s.fits32(4)) return 0;
+  const int ct = lstm_chunk_tiles(s.UB(), s.d, s.BT());
+  const int g = bwd16_grid(4, s, ct);
+  return g > 0 && g <= num_cus() ? ct : 0;
+}
+
+// workgroups one persistent backward launch holds at once (a batch larger than the chip
+// runs as consecutive launches of at most this many), 0 for the per-step kernels
+int ds2_lstm_bwd_grid(int n, int h, int num_dirs) {
+  if (n < 1 || h < 1 || (num_dirs != 1 && num_dirs != 2)) return 0;
+  // t only bounds 32-bit offsets; 1 asks about the launch shape
+  const RnnShape s = {1, n, h, num_dirs};
+  const int ct = lstm_h3_tiles(s);
+  if (ct > 0) return bwd16_grid(4, s, ct);
+  if (!persistent_enabled() || (h % 4) != 0) return 0;
+  const int bts = lstm_bwd_bts(s);
+  const int BTW = (s.BT() + bts - 1) / bts;
+  const int g = mapped_grid(s.UB() * num_dirs, lstm_chunk_tiles(s.UB(), num_dirs, BTW));
+  return g <= num_cus() ? g : 0;
 }
 
 // ds2_lstm_bwd_half falls back to ds2_lstm_bwd when the single-term launch declines at run time
@@ -1040,9 +1044,8 @@ static int lstm_h1_launch_grid(int t_max, int n, int h, int num_dirs) {
 // more workgroups, so report the larger grid: the CU guard never budgets for fewer than run
 int ds2_lstm_bwd_half_grid(int n, int h, int num_dirs) {
   if (n < 1 || h < 1 || (num_dirs != 1 && num_dirs != 2)) return 0;
-  const int g = lstm_h1_launch_grid(1, n, h, num_dirs);
-  const int f = ds2_lstm_bwd_grid(n, h, num_dirs);
-  return g > f ? g : f;
+  return std::max(lstm_h1_launch_grid(RnnShape{1, n, h, num_dirs}),
+                  ds2_lstm_bwd_grid(n, h, num_dirs));
 }
 
 ds2_status_t ds2_lstm_bwd_half(int t_max, int n, int h, int num_dirs, const float* dy, int dy_dirs,
@@ -1053,63 +1056,29 @@ ds2_status_t ds2_lstm_bwd_half(int t_max, int n, int h, int num_dirs, const floa
   if (t_max == 0 || n == 0) return DS2_OK;
   if (gates == nullptr || c_all == nullptr) return DS2_INVALID_VALUE;
   if (dy_dirs != 1 && dy_dirs != num_dirs) return DS2_INVALID_VALUE;
-  if (ws == nullptr || ws_bytes < ds2_lstm_bwd_workspace_size(n, h, num_dirs))
+  const RnnShape s = {t_max, n, h, num_dirs};
+  const LstmBwdLayout L = lstm_bwd_layout(s);
+  if (ws == nullptr || ws_bytes < L.total)
     return DS2_WORKSPACE_TOO_SMALL;
-  if (lstm_h1_launch_grid(t_max, n, h, num_dirs) > 0) {
+  if (lstm_h1_launch_grid(s) > 0) {
     hipStream_t st = as_stream(stream);
     apply_spin_limit_env();
-    char* base3 = static_cast<char*>(ws) + lstm_bwd_ws_base(n, h, num_dirs);
-    unsigned* ctrs3 = reinterpret_cast<unsigned*>(base3);
-    float* ring3 = reinterpret_cast<float*>(base3 + lstm_h3_ctr_bytes(n, num_dirs));
-    const int BT32 = (n + 31) / 32;
-    unsigned* err = ctrs3 + num_dirs * BT32;
-    if (hipMemsetAsync(ctrs3, 0, lstm_h3_ctr_bytes(n, num_dirs), st) != hipSuccess)
-      return launch_status("ds2_lstm counters");
-    if (launch_lstm_bwd_h1(t_max, n, h, num_dirs, dy, dy_dirs, w_hh_f,
-                           num_dirs == 2 ? w_hh_r : w_hh_f, c_all, gates, lens, dgates, ring3,
-                           ctrs3, err, kLstmDopPadLds, st, nullptr)) {
-      fold_err(err, err_out, st);
-      return launch_status("ds2_lstm_bwd_half");
-    }
-    (void)hipGetLastError();
+    unsigned* ctrs3 = ws_at<unsigned>(ws, L.ctrs3);
+    const Handoff ho = {ws_at<float>(ws, L.ring3), ctrs3, L.ctr3_bytes,
+                        err_word(ctrs3, s.groups(32)), err_out, nullptr, kDopPadLds};
+    const RecBwd a = {dy, dy_dirs, w_hh_f, num_dirs == 2 ? w_hh_r : w_hh_f, c_all, gates, lens,
+                      dgates, nullptr, nullptr, nullptr, nullptr};
+    ds2_status_t rc = DS2_OK;
+    if (rung("ds2_lstm_bwd_half", ho, true, 0, st, &rc,
+             [&] { return launch_lstm_bwd_h1(s, a, ho, st); }))
+      return rc;
   }
   return ds2_lstm_bwd(t_max, n, h, num_dirs, dy, dy_dirs, w_hh_f, w_hh_r, c_all, gates, lens,
                       dgates, err_out, ws, ws_bytes, stream);
 }
 
-// the fp16x3 backward's launch: 16-sample tiles per launch (consecutive launches cover the
-// batch), 0 when it declines the shape
-static int lstm_h3_tiles(int t_max, int n, int h, int num_dirs) {
-  if (!lstm_h3_on() || !persistent_enabled() || (h % GU) != 0) return 0;
-  if ((int64_t)t_max * n * num_dirs * 4 * h * 4 >= (1ll << 31)) return 0;
-  const int UB = h / GU, BT = (n + GB - 1) / GB;
-  const int ct = lstm_chunk_tiles(UB, num_dirs, BT);
-  const int g = lstm_h3_grid(h, num_dirs, ct);
-  return g > 0 && g <= num_cus() ? ct : 0;
-}
-
-#define DS2_LBWD_CASE(K)                                                                    \
-  case K:                                                                                   \
-    hipLaunchKernelGGL(lstm_bwd_step_kernel<K>, dim3(grid), dim3(GT), 0, st, s, t_max, n, h, \
-                       num_dirs, UB, BT, dy, dy_dirs, wpt, c_all, gates, lens, dgates, dcs);  \
-    break;
-
-// workgroups one persistent backward launch holds at once (a batch larger than the chip
-// runs as consecutive launches of at most this many), 0 for the per-step kernels
-int ds2_lstm_bwd_grid(int n, int h, int num_dirs) {
-  if (n < 1 || h < 1 || (num_dirs != 1 && num_dirs != 2)) return 0;
-  // t_max only bounds 32-bit offsets; 1 asks about the launch shape
-  const int ct = lstm_h3_tiles(1, n, h, num_dirs);
-  if (ct > 0) return lstm_h3_grid(h, num_dirs, ct);
-  if (!persistent_enabled() || (h % 4) != 0) return 0;
-  const int UB = (h + GU - 1) / GU, BT = (n + GB - 1) / GB;
-  int bts = lstm_bts(UB, num_dirs, BT);
-  if (bts == 2 && 4 * h > 2 * 4 * GW * 32) bts = 1;
-  const int BTW = (BT + bts - 1) / bts;
-  const int g = mapped_grid(UB * num_dirs, lstm_chunk_tiles(UB, num_dirs, BTW));
-  return g <= num_cus() ? g : 0;
-}
-
+// Ladder: the fp16x3 kernels (gru_split.hip, NG = 4; DS2_LSTM_H3=0 skips them), the LDS-staged
+// persistent kernels (H % 4 == 0), one launch per step.
 ds2_status_t ds2_lstm_bwd(int t_max, int n, int h, int num_dirs, const float* dy, int dy_dirs,
                           const float* w_hh_f, const float* w_hh_r, const float* c_all,
                           const float* gates, const int* lens, float* dgates, unsigned* err_out,
@@ -1118,49 +1087,38 @@ ds2_status_t ds2_lstm_bwd(int t_max, int n, int h, int num_dirs, const float* dy
   if (t_max == 0 || n == 0) return DS2_OK;
   if (gates == nullptr || c_all == nullptr) return DS2_INVALID_VALUE;
   if (dy_dirs != 1 && dy_dirs != num_dirs) return DS2_INVALID_VALUE;
-  if (ws == nullptr || ws_bytes < ds2_lstm_bwd_workspace_size(n, h, num_dirs))
+  const RnnShape s = {t_max, n, h, num_dirs};
+  const LstmBwdLayout L = lstm_bwd_layout(s);
+  if (ws == nullptr || ws_bytes < L.total)
     return DS2_WORKSPACE_TOO_SMALL;
   if (num_dirs == 1) w_hh_r = w_hh_f;
   hipStream_t st = as_stream(stream);
   apply_spin_limit_env();
-  const int UB = (h + GU - 1) / GU;
+  int T = t_max, N = n, H = h, D = num_dirs, UB = s.UB(), BT = s.BT(), DYD = dy_dirs;
   const int KS = h;
-  const int BT = (n + GB - 1) / GB;
   const int chunk_ks = std::min(4 * h, LKC_BWD) / 4;
-  const int ksw = lstm_pick_ksw((chunk_ks + GW - 1) / GW);
-  if (ksw < 0) return DS2_UNSUPPORTED_SHAPE;
-  float* wpt = static_cast<float*>(ws);
-  size_t off = align256((size_t)num_dirs * UB * KS * 64 * sizeof(float));
-  float* dcs = reinterpret_cast<float*>(static_cast<char*>(ws) + off);
-  off += align256((size_t)2 * n * num_dirs * h * sizeof(float));
-  unsigned* ctrs = reinterpret_cast<unsigned*>(static_cast<char*>(ws) + off);
+  const void* step_fn = pick_instance(kBwdStep, (chunk_ks + GW - 1) / GW);
+  if (step_fn == nullptr) return DS2_UNSUPPORTED_SHAPE;
+  float* wpt = ws_at<float>(ws, L.wpt);
+  float* dcs = ws_at<float>(ws, L.dcs);
+  ds2_status_t rc = DS2_OK;
   // the fp16x3 backward (gru_split.hip, NG = 4): W_hh read directly, gate gradients handed
   // off as one scaled fp16 hi / lo record per producer and step
-  const int ct3 = lstm_h3_tiles(t_max, n, h, num_dirs);
+  const int ct3 = lstm_h3_tiles(s);
   if (ct3 > 0) {
-    char* base3 = static_cast<char*>(ws) + lstm_bwd_ws_base(n, h, num_dirs);
-    unsigned* ctrs3 = reinterpret_cast<unsigned*>(base3);
-    float* ring3 = reinterpret_cast<float*>(base3 + lstm_h3_ctr_bytes(n, num_dirs));
-    bool ok = true, launched = false;
-    for (int b0 = 0; ok && b0 < BT; b0 += ct3) {
-      const int bt = std::min(ct3, BT - b0);
-      unsigned* err = ctrs3 + num_dirs * bt;
-      if (hipMemsetAsync(ctrs3, 0, lstm_h3_ctr_bytes(n, num_dirs), st) != hipSuccess)
-        return launch_status("ds2_lstm counters");
-      ok = launch_lstm_bwd_h3(t_max, n, h, num_dirs, dy, dy_dirs, w_hh_f, w_hh_r, c_all, gates,
-                              lens, dgates, ring3, ctrs3, err, kLstmDopPadLds, st, nullptr, b0, bt);
-      if (ok) fold_err(err, err_out, st);
-      if (!ok && launched) return launch_status("ds2_lstm_bwd chunk");
-      launched = launched || ok;
-    }
-    if (ok) return launch_status("ds2_lstm_bwd");
-    (void)hipGetLastError();
+    const Handoff ho3 = {ws_at<float>(ws, L.ring3), ws_at<unsigned>(ws, L.ctrs3), L.ctr3_bytes,
+                         nullptr, err_out, nullptr, kDopPadLds};
+    const RecBwd a = {dy, dy_dirs, w_hh_f, w_hh_r, c_all, gates, lens, dgates, nullptr,
+                      nullptr, nullptr, nullptr};
+    if (for_each_chunk("ds2_lstm_bwd", ho3, D, BT, ct3, 0, st, &rc,
+                       [&](int b0, int bt, Handoff c) {
+                         return launch_bwd16(4, s, a, c, st, b0, bt, nullptr);
+                       }))
+      return rc;
   }
   hipLaunchKernelGGL(pack_bwd_kernel<4>, dim3(grid_cap((int64_t)num_dirs * UB * KS * 64)),
                      dim3(256), 0, st, w_hh_f, w_hh_r, h, num_dirs, UB, KS, wpt);
-  const int grid = mapped_grid(UB * num_dirs, BT);
-  if (persistent_enabled() && (h % 4) == 0 &&
-      (int64_t)t_max * n * num_dirs * 4 * h * 4 < (1ll << 31)) {
+  if (persistent_enabled() && (h % 4) == 0 && s.fits32(4)) {
     // smallest (k-steps per wave per chunk, chunks) covering 4H gate columns
     const int opts[] = {8, 16, 25, 32, 48, 64};
     int kswc = -1, nch = -1;
@@ -1171,53 +1129,36 @@ ds2_status_t ds2_lstm_bwd(int t_max, int n, int h, int num_dirs, const float* dy
           nch = c;
           break;
         }
-    // 32-sample workgroups stage chunks of at most 1024 gate columns (32 rows in LDS);
-    // past two chunks (H > 512) the W_hh^T fragments and a chunk's in-flight loads exceed
-    // the 256 VGPRs, so the batch runs in 16-sample chunks instead
-    int bts = lstm_bts(UB, num_dirs, BT);
-    if (bts == 2 && 4 * h > 2 * 4 * GW * 32) bts = 1;
+    const int bts = lstm_bwd_bts(s);
     if (bts == 2) {
       kswc = 32;
       nch = (4 * h + 4 * GW * 32 - 1) / (4 * GW * 32);
     }
-    const void* fn = nullptr;    // the interleaved layout
-    const void* fx = nullptr;    // the same-XCD groups
-#define DS2_LBP(K, C, B)                                                          \
-  if (kswc == K && nch == C && bts == B) {                                        \
-    fn = reinterpret_cast<const void*>(lstm_bwd_persist_kernel<K, C, B, false>);  \
-    fx = reinterpret_cast<const void*>(lstm_bwd_persist_kernel<K, C, B, true>);   \
-  }
-    DS2_LBP(8, 1, 1) DS2_LBP(16, 1, 1) DS2_LBP(25, 1, 1) DS2_LBP(32, 1, 1) DS2_LBP(48, 1, 1)
-    DS2_LBP(64, 1, 1) DS2_LBP(48, 2, 1) DS2_LBP(64, 2, 1)
-    DS2_LBP(32, 1, 2) DS2_LBP(32, 2, 2)
-#undef DS2_LBP
+    const LstmBwdPersist* k = nullptr;
+    for (const LstmBwdPersist& e : kBwdPersist)
+      if (e.k == kswc && e.c == nch && e.b == bts) k = &e;
     const int BTW = (BT + bts - 1) / bts;
-    const int ct = lstm_chunk_tiles(UB, num_dirs, BTW);
-    bool ok = fn != nullptr && mapped_grid(UB * num_dirs, ct) <= num_cus();
-    for (int b0 = 0; ok && b0 < BTW; b0 += ct) {
-      int T_ = t_max, N_ = n, H_ = h, D_ = num_dirs, UB_ = UB, BT_ = std::min(ct, BTW - b0);
-      int DYD_ = dy_dirs, NB_ = b0 * GB * bts;
-      unsigned* err = ctrs + num_dirs * BT_;
-      if (hipMemsetAsync(ctrs, 0, lstm_counter_bytes(n, num_dirs), st) != hipSuccess)
-        return launch_status("ds2_lstm counters");
-      // same-XCD groups (DS2_GRU_XCD, as the GRU backward's) where they tile the XCDs
-      const bool xm = xcd_groups_on() && xgrp_fits(UB, BT_, num_dirs);
-      void* args[] = {&T_, &N_, &H_, &D_, &UB_, &BT_, &dy, &DYD_, &wpt, &c_all, &gates, &lens,
-                      &dgates, &ctrs, &err, &NB_};
-      ok = rnn_launch(xm ? fx : fn,
-                      dim3(xm ? xgrp_grid(UB, BT_, num_dirs) : mapped_grid(UB * num_dirs, BT_)),
-                      dim3(GT), args, 0, st) == hipSuccess;
-      if (ok) fold_err(err, err_out, st);
-      if (!ok && b0 > 0) return launch_status("ds2_lstm_bwd chunk");
-    }
-    if (ok) return launch_status("ds2_lstm_bwd");
-    (void)hipGetLastError();
+    const int ct = lstm_chunk_tiles(UB, D, BTW);
+    const Handoff ho = {nullptr, ws_at<unsigned>(ws, L.ctrs), L.ctr_bytes, nullptr, err_out,
+                        nullptr, 0};
+    if (k != nullptr && mapped_grid(UB * D, ct) <= num_cus() &&
+        for_each_chunk("ds2_lstm_bwd", ho, D, BTW, ct, 0, st, &rc,
+                       [&](int b0, int bt, Handoff c) {
+                         int NB = b0 * GB * bts, xm = 0;
+                         // same-XCD groups (as the GRU backward's) where they tile the XCDs
+                         const int grid = group_grid(UB, bt, D, &xm);
+                         void* args[] = {&T, &N, &H, &D, &UB, &bt, &dy, &DYD, &wpt, &c_all, &gates,
+                                         &lens, &dgates, &c.ctrs, &c.err, &NB};
+                         return launch_fn(xm ? k->fx : k->fn, grid, GT, args, 0, st);
+                       }))
+      return rc;
   }
-  for (int s = 0; s < t_max; ++s) {
-    switch (ksw) {
-      DS2_LBWD_CASE(8) DS2_LBWD_CASE(16) DS2_LBWD_CASE(32) DS2_LBWD_CASE(64)
-    }
-  }
+  const int grid = mapped_grid(UB * D, BT);
+  int step = 0;
+  void* args[] = {&step, &T, &N, &H, &D, &UB, &BT, &dy, &DYD, &wpt, &c_all, &gates, &lens,
+                  &dgates, &dcs};
+  for (step = 0; step < t_max; ++step)
+    (void)hipLaunchKernel(step_fn, dim3(grid), dim3(GT), args, 0, st);
   return launch_status("ds2_lstm_bwd");
 }
 

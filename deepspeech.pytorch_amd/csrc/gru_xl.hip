@@ -68,6 +68,38 @@ __device__ __forceinline__ bool xl_map(int G, int UBX, int& g, int& ub) {
   return g < G && ub < UBX;
 }
 
+// What only the cold paths read -- the error words a timed-out wait raises, the tensor and shape
+// the poison fill needs -- parked in LDS by thread 0 at kernel start (the barrier of
+// xl_group_local publishes it).  The step loop then holds none of it in SGPRs: at one wave per
+// SIMD the loops ran out of them, and every spill reload (v_readlane) sat on the step's serial
+// path.  (The loop's barriers and memory clobbers keep these loads where they are written.)
+// The pointers keep their global address space: a pointer loaded back from LDS is generic, its
+// atomics are FLAT, and with a FLAT access possibly outstanding the compiler turns every
+// counted vmcnt(N) wait of the step loop into vmcnt(0) (the record loads then no longer overlap
+// the products: 1.77 -> 1.82 ms per backward launch).
+typedef __attribute__((address_space(1))) unsigned xl_gu32;
+typedef __attribute__((address_space(1))) float xl_gf32;
+struct XlCold {
+  xl_gu32 *err, *err_out;
+  xl_gf32* out;    // the poison fill's tensor (h_all / dgx)
+  int N, D, H;
+  int n0, j0;      // the workgroup's first sample and unit
+};
+
+__device__ __forceinline__ void xl_raise(const XlCold& c) {
+  xl_gu32 *e = c.err, *eo = c.err_out;
+  __hip_atomic_fetch_or(e, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (eo != nullptr) __hip_atomic_fetch_or(eo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// poison_rest from the cold block: `width` floats per row in `groups` slices of H columns
+__device__ __forceinline__ void xl_poison(const XlCold& c, int s, int T, bool rev, int d,
+                                          int width_h, int groups) {
+  const int n = c.n0 + (int)(threadIdx.x >> 5);
+  poison_rest((float*)c.out, s, T, rev, c.N, c.D, n, d, c.H, c.j0 + (int)(threadIdx.x & 31),
+              width_h * c.H, groups, n < c.N);
+}
+
 // Every workgroup publishes its XCC id (+1) into its group's table and waits for the group's
 // UBX entries; true when all equal this workgroup's (every member reaches the same answer from
 // the same table).  A timeout sets the error word and answers false.  `mode` (diagnostic, read
@@ -137,13 +169,12 @@ __device__ __forceinline__ float half_wave_max(float v) {
 // other producers or for a workgroup barrier.  False, and the error words set, past the spin
 // bound (DS2_RNN_SPIN_LIMIT=0: at once).
 __device__ __forceinline__ bool xl_wave_flags_wait(const unsigned* flags, int count,
-                                                   unsigned target, unsigned* err,
-                                                   unsigned* err_out) {
+                                                   unsigned target, const XlCold& cold) {
   const int lane = threadIdx.x & 63;
   if (count == 0) return true;
   for (unsigned spins = 0;; ++spins) {
     if (spins > g_spin_limit || g_spin_limit == 0) {
-      if (lane == 0) raise_err(err, err_out);
+      if (lane == 0) xl_raise(cold);
       return false;
     }
     const unsigned v = lane < count ? __hip_atomic_load(flags + lane, __ATOMIC_RELAXED,
@@ -154,6 +185,81 @@ __device__ __forceinline__ bool xl_wave_flags_wait(const unsigned* flags, int co
   }
 }
 
+// W_hh fragments beyond the arch-VGPR budget stay in AGPRs for the whole kernel and the MFMAs
+// read them there (gfx950 takes A / B operands from either half of the register file).  The
+// compiler only ever parks a VGPR value in an AGPR as a spill and copies it back in front of
+// every use (v_accvgpr_read: ~190 per forward step, ~310 per backward step at NPW 6), so these
+// MFMAs are issued from inline asm whose operand constraints name the file: xl_agpr moves a
+// fragment there once, at kernel start.  kXlVgprW: the producers whose fragments stay VGPRs.
+constexpr int kXlVgprW = 2, kXlVgprWBwd = 1;
+__device__ __forceinline__ u32x4 xl_agpr(u32x4 v) {
+  u32x4 r;
+  asm volatile("" : "=a"(r) : "0"(v));
+  return r;
+}
+// What the compiler does not do for an asm statement: `s_nop 1` covers a VALU-written operand
+// (a fragment or tile the allocator moved just before the statement), and whoever reads the
+// accumulators next calls xl_mfma_settle first (the MFMA's result -> any other reader).  In
+// the forward that is once per step, behind the last tile: between the tiles the accumulators
+// are operands of the asm statements alone, and the compiler must not touch them there.  After
+// a change, check the assembly (scripts/xl_reg_audit.py: no v_accvgpr_*, no spill; and no
+// v_mov of an accumulator register between a step's first MFMA and the settle).
+__device__ __forceinline__ void xl_mfma_settle(f32x4 (&c)[6]) {
+  asm volatile("s_nop 15\n\ts_nop 7"
+               : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]), "+v"(c[4]), "+v"(c[5]));
+}
+// One forward tile: c[ct] += a . lo[ct], then += a . hi[ct] (each c[ct] its own chain, small
+// products first), the six chains interleaved.  WC: the fragments' register file.
+#define DS2_XL_FWD_TILE(WC)                                                                  \
+  asm volatile(                                                                              \
+      "s_nop 1\n\t"                                                                          \
+      "v_mfma_f32_16x16x32_f16 %0, %6, %7, %0\n\tv_mfma_f32_16x16x32_f16 %1, %6, %8, %1\n\t"  \
+      "v_mfma_f32_16x16x32_f16 %2, %6, %9, %2\n\tv_mfma_f32_16x16x32_f16 %3, %6, %10, %3\n\t" \
+      "v_mfma_f32_16x16x32_f16 %4, %6, %11, %4\n\tv_mfma_f32_16x16x32_f16 %5, %6, %12, %5\n\t" \
+      "v_mfma_f32_16x16x32_f16 %0, %6, %13, %0\n\tv_mfma_f32_16x16x32_f16 %1, %6, %14, %1\n\t" \
+      "v_mfma_f32_16x16x32_f16 %2, %6, %15, %2\n\tv_mfma_f32_16x16x32_f16 %3, %6, %16, %3\n\t" \
+      "v_mfma_f32_16x16x32_f16 %4, %6, %17, %4\n\tv_mfma_f32_16x16x32_f16 %5, %6, %18, %5"      \
+      : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]), "+v"(c[4]), "+v"(c[5])               \
+      : "v"(a), WC(lo[0]), WC(lo[1]), WC(lo[2]), WC(lo[3]), WC(lo[4]), WC(lo[5]), WC(hi[0]), \
+        WC(hi[1]), WC(hi[2]), WC(hi[3]), WC(hi[4]), WC(hi[5]))
+template <bool AG>
+__device__ __forceinline__ void xl_fwd_tile(f32x4 (&c)[6], u32x4 a, const u32x4 (&lo)[6],
+                                            const u32x4 (&hi)[6]) {
+  if constexpr (AG)
+    DS2_XL_FWD_TILE("a");
+  else
+    DS2_XL_FWD_TILE("v");
+}
+#undef DS2_XL_FWD_TILE
+
+// One backward record: per unit half c the two zero-C chains c[2 c] (hi fragments) and
+// c[2 c + 1] (lo) over the gates r, z, n, the four chains interleaved.  w[gate][half][hi, lo].
+// The VALU adds the chains up right behind the statement, so the MFMA-result wait states are
+// inside it (`s_nop 7` is what the compiler itself puts between this MFMA and a VALU reader).
+#define DS2_XL_BWD_REC(WC)                                                                    \
+  asm volatile(                                                                               \
+      "s_nop 1\n\t"                                                                           \
+      "v_mfma_f32_16x16x32_f16 %0, %4, %7, 0\n\tv_mfma_f32_16x16x32_f16 %1, %4, %8, 0\n\t"     \
+      "v_mfma_f32_16x16x32_f16 %2, %4, %9, 0\n\tv_mfma_f32_16x16x32_f16 %3, %4, %10, 0\n\t"    \
+      "v_mfma_f32_16x16x32_f16 %0, %5, %11, %0\n\tv_mfma_f32_16x16x32_f16 %1, %5, %12, %1\n\t" \
+      "v_mfma_f32_16x16x32_f16 %2, %5, %13, %2\n\tv_mfma_f32_16x16x32_f16 %3, %5, %14, %3\n\t" \
+      "v_mfma_f32_16x16x32_f16 %0, %6, %15, %0\n\tv_mfma_f32_16x16x32_f16 %1, %6, %16, %1\n\t" \
+      "v_mfma_f32_16x16x32_f16 %2, %6, %17, %2\n\tv_mfma_f32_16x16x32_f16 %3, %6, %18, %3\n\t" \
+      "s_nop 9"                                                                               \
+      : "=&v"(c[0]), "=&v"(c[1]), "=&v"(c[2]), "=&v"(c[3])                                    \
+      : "v"(ar), "v"(az), "v"(an), WC(w[0][0][0]), WC(w[0][0][1]), WC(w[0][1][0]),            \
+        WC(w[0][1][1]), WC(w[1][0][0]), WC(w[1][0][1]), WC(w[1][1][0]), WC(w[1][1][1]),       \
+        WC(w[2][0][0]), WC(w[2][0][1]), WC(w[2][1][0]), WC(w[2][1][1]))
+template <bool AG>
+__device__ __forceinline__ void xl_bwd_rec(f32x4 (&c)[4], u32x4 ar, u32x4 az, u32x4 an,
+                                           const u32x4 (&w)[3][2][2]) {
+  if constexpr (AG)
+    DS2_XL_BWD_REC("a");
+  else
+    DS2_XL_BWD_REC("v");
+}
+#undef DS2_XL_BWD_REC
+
 // the stacked fp16 (hi; lo) A-fragment slots of value (row m < 8, k) in a 1-KB fragment:
 // lane (k >> 3) * 16 + m (hi) / + m + 8 (lo), slot k & 7
 __device__ __forceinline__ int xl_frag_hi(int m, int k) { return (((k >> 3) << 4) + m) * 8 + (k & 7); }
@@ -163,7 +269,8 @@ __device__ __forceinline__ int xl_frag_hi(int m, int k) { return (((k >> 3) << 4
 // Wave w holds W_hh for the producers [p0, p0 + np) (k = their 32 units each): per producer and
 // column tile ct = gate * 2 + unit half, the fp16 hi / lo B fragments of W_hh's rows scaled by
 // 2^e(gate, unit) (the row's max over the whole K).  h (|h| < 1) takes the fixed scale 2^14.
-template <int NPW>
+// TRACE: the instantiation with the stamp sites (DS2_GRU_STAMPS=2); the product ones carry none
+template <int NPW, bool TRACE>
 __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void gru_fwd_xl_kernel(
     int T, int N, int H, int D, int UBX, int BTX, const float* __restrict__ xproj,
     const float* __restrict__ w_f, const float* __restrict__ w_r, const float* __restrict__ b_f,
@@ -181,6 +288,7 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
   __shared__ int slen[LB];
   __shared__ int sh_local;
   __shared__ int failed;
+  __shared__ XlCold cold;
   // W_hh fragments of a wave's last producer when it has NPW + 1 (cfg2: 25 = 6 + 6 + 6 + 7):
   // in LDS, read every step, instead of 48 more registers in every wave
   __shared__ u32x4 wx[LW * NCT * 2 * 64];
@@ -194,7 +302,10 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
   // which issues none of the step's HBM traffic (the io waves below), takes the extra one
   const int p0 = wave * (UBX / LW) + min(wave, UBX % LW);
   const int np = UBX / LW + (wave < UBX % LW ? 1 : 0);   // host guarantees np <= NPW + 1
-  if (threadIdx.x == 0) failed = 0;
+  if (threadIdx.x == 0) {
+    failed = 0;
+    cold = XlCold{(xl_gu32*)err, (xl_gu32*)err_out, (xl_gf32*)h_all, N, D, H, bt * LB, ub * LU};
+  }
   const bool local =
       xl_group_local(xl + g * 32, ub, UBX, err, err_out, &sh_local, xl + 512 + g, force_global);
   const int slot_floats = G * UBX * 256;
@@ -204,23 +315,17 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
   // per-wave timeline (DS2_GRU_STAMPS=2): [step][block][wave][6] = step start, hand-off wait
   // done, products done, io done (waves 1-3), reduction barrier done, published; lane 0 of
   // every wave (scripts/trace_gru.py)
-  const bool tracing = stamps != nullptr && lane == 0;
   auto trace_at = [&](int s, int p) __attribute__((always_inline)) {
-    if (tracing && s >= kXlTraceS0 && s < kXlTraceS0 + kXlTraceSteps)
-      stamps[(((int64_t)(s - kXlTraceS0) * gridDim.x + blockIdx.x) * LW + wave) * 6 + p] =
-          __builtin_amdgcn_s_memrealtime();
+    if constexpr (TRACE)
+      if (stamps != nullptr && lane == 0 && s >= kXlTraceS0 && s < kXlTraceS0 + kXlTraceSteps)
+        stamps[(((int64_t)(s - kXlTraceS0) * gridDim.x + blockIdx.x) * LW + wave) * 6 + p] =
+            __builtin_amdgcn_s_memrealtime();
   };
 
   // W_hh fragments: producer p, tile ct (gate gt = ct >> 1, half c = ct & 1), k slot i ->
   // W[gt H + 32 ub + 16 c + (lane & 15)][32 (p0 + p) + 8 (lane >> 4) + i]
-  Duo w[NPW][NCT];
-  auto wfr = [&](int p, int ct) __attribute__((always_inline)) {   // producer p's fragments (p == NPW: from LDS)
-    if (p < NPW) return w[p < NPW ? p : 0][ct];
-    Duo r;
-    r.hi = __builtin_bit_cast(f16x8, wx[((wave * NCT + ct) * 2 + 0) * 64 + lane]);
-    r.lo = __builtin_bit_cast(f16x8, wx[((wave * NCT + ct) * 2 + 1) * 64 + lane]);
-    return r;
-  };
+  // (producers below kXlVgprW in VGPRs, the others in AGPRs, producer NPW in LDS)
+  u32x4 whi[NPW][NCT], wlo[NPW][NCT];
   {
     const float* W = d == 0 ? w_f : w_r;
     const int q8 = 8 * (lane >> 4);
@@ -278,11 +383,13 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
         f32x4 a, b;
         frag(p, ct, a, b);
         const Duo dd = split2h(a, b, sc[ct]);
+        const u32x4 dh = __builtin_bit_cast(u32x4, dd.hi), dl = __builtin_bit_cast(u32x4, dd.lo);
         if (p < NPW) {
-          w[p < NPW ? p : 0][ct] = dd;
+          whi[p < NPW ? p : 0][ct] = p < kXlVgprW ? dh : xl_agpr(dh);
+          wlo[p < NPW ? p : 0][ct] = p < kXlVgprW ? dl : xl_agpr(dl);
         } else {
-          wx[((wave * NCT + ct) * 2 + 0) * 64 + lane] = __builtin_bit_cast(u32x4, dd.hi);
-          wx[((wave * NCT + ct) * 2 + 1) * 64 + lane] = __builtin_bit_cast(u32x4, dd.lo);
+          wx[((wave * NCT + ct) * 2 + 0) * 64 + lane] = dh;
+          wx[((wave * NCT + ct) * 2 + 1) * 64 + lane] = dl;
         }
       }
   }
@@ -380,22 +487,33 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
       const int base = (((s - 1) % LSLOTS) * slot_floats + grp_off + p0 * 256 + lane * 4) * 4;
       sleep_units(g_rnn_tune[7]);
       u32x4 hv[NPW + 1];
+      // the tile count as the step sees it: opaque, so that each `p < npl` is a scalar compare
+      // where it is used -- with np itself the compiler hoists every one of them out of the
+      // step loop as a 64-bit lane mask, and those masks were most of the SGPR spills (48 at
+      // NPW 6, reloaded by v_readlane in front of every tile)
+      int npl = np;
+      asm volatile("" : "+s"(npl));
 #pragma unroll
       for (int p = 0; p < NPW + 1; ++p)
-        hv[p] = __builtin_amdgcn_raw_buffer_load_b128(x_rs, p < np ? base + p * 1024 : 0x7ffffff0, 0, kSc1);
+        hv[p] = __builtin_amdgcn_raw_buffer_load_b128(x_rs, p < npl ? base + p * 1024 : 0x7ffffff0, 0, kSc1);
       asm volatile("" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
       // fixed order: tile p is multiplied once it and every tile before it have arrived; a
       // stale pass re-loads every tile not yet multiplied (their round trips overlap)
-      bool bad = false;   // a tile of this wave timed out: the rest are skipped
+      // Only the waits are conditional: the MFMAs of the wave's np tiles run in one straight
+      // line that is left after the last one, so each acc[ct] is a single chain in one set of
+      // registers (with each tile's MFMAs under that tile's condition the compiler copied all
+      // 24 accumulators at every tile boundary and drained the MFMA pipe there).
+      bool bad = false;   // a tile of this wave timed out: no more waits, the step is discarded
 #pragma unroll
       for (int p = 0; p < NPW + 1; ++p) {
-        if (p < np && !bad) {
+        if (p >= npl) break;
+        if (!bad) {
           for (unsigned spins = 0;
                !kAblWait && (!wave_ready(__builtin_bit_cast(f32x4, hv[p])) || g_spin_limit == 0);
                ++spins) {
             if (spins > g_spin_limit || g_spin_limit == 0) {
-              if (lane == 0) raise_err(err, err_out);
+              if (lane == 0) xl_raise(cold);
               failed = 1;
               bad = true;
               break;
@@ -404,21 +522,28 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
             asm volatile("" ::: "memory");
 #pragma unroll
             for (int q = p; q < NPW + 1; ++q)
-              if (q < np && (unsigned)(q - p) < g_rnn_tune[6])
+              if (q < npl && (unsigned)(q - p) < g_rnn_tune[6])
                 hv[q] = __builtin_amdgcn_raw_buffer_load_b128(x_rs, base + q * 1024, 0, kSc1);
           }
-          const f16x8 a = __builtin_bit_cast(f16x8, hv[p]);
+        }
+        // one chain per column tile over the producers, small products first (mma3h's order).
+        // Per-producer zero-C chains joined by the VALU (the backward's form) moved the bs-32
+        // step's bias gradients by 3 % and cost 0.6 us per step: the adds wait on each MFMA
+        if (p < kXlVgprW && p < NPW) {
+          xl_fwd_tile<false>(acc, hv[p], wlo[p < NPW ? p : 0], whi[p < NPW ? p : 0]);
+        } else if (p < NPW) {
+          xl_fwd_tile<true>(acc, hv[p], wlo[p < NPW ? p : 0], whi[p < NPW ? p : 0]);
+        } else {
+          u32x4 xh[NCT], xw[NCT];
 #pragma unroll
           for (int ct = 0; ct < NCT; ++ct) {
-            // one chain over the producers, small products first (mma3h's order).  Per-producer
-            // zero-C chains joined by the VALU (the backward's form) moved the bs-32 step's
-            // bias gradients by 3 % and cost 0.6 us per step: the adds wait on each MFMA
-            const Duo wf = wfr(p, ct);
-            acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, wf.lo, acc[ct], 0, 0, 0);
-            acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, wf.hi, acc[ct], 0, 0, 0);
+            xh[ct] = wx[((wave * NCT + ct) * 2 + 0) * 64 + lane];
+            xw[ct] = wx[((wave * NCT + ct) * 2 + 1) * 64 + lane];
           }
+          xl_fwd_tile<false>(acc, hv[p], xw, xh);
         }
       }
+      xl_mfma_settle(acc);
       trace_at(s, 2);
     }
     if (io) {
@@ -435,7 +560,7 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
         red[(wave * 16 + (lane >> 4) * 4 + i) * RC + ct * 16 + (lane & 15)] = acc[ct][i];
     __syncthreads();
     if (failed) {
-      poison_rest(h_all, s, T, d != 0, N, D, n, d, H, j, H, 1, owner);
+      xl_poison(cold, s, T, d != 0, d, 1, 1);
       return;
     }
     trace_at(s, 4);
@@ -496,7 +621,7 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 // Per-producer flags: the records as their own flags (the forward's sentinel ring over 3.1-KB
 // records, no drain and no flag) measured 5.3-5.5 vs 3.8 us per step and was removed.
 // ROWS: the instantiation that also keeps the row maxima of dgx (rowp)
-template <int NPW, bool ROWS>
+template <int NPW, bool ROWS, bool TRACE>
 __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void gru_bwd_xl_kernel(
     int T, int N, int H, int D, int UBX, int BTX, const float* __restrict__ dy, int dyd,
     const float* __restrict__ w_f, const float* __restrict__ w_r,
@@ -517,6 +642,7 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
   __shared__ int slen[LB];
   __shared__ int sh_local;
   __shared__ int flag;
+  __shared__ XlCold cold;
   __shared__ float rowmx[2 * LB];   // dgx row maxima of the last two steps (rowp)
   // W_hh^T fragments of a wave's last producer when it has NPW + 1 (as the forward's)
   __shared__ u32x4 wx[LW * 6 * 2 * 64];
@@ -531,7 +657,10 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
   const int p0 = wave * (UBX / LW) + min(wave, UBX % LW);
   const int np = UBX / LW + (wave < UBX % LW ? 1 : 0);   // host guarantees np <= NPW + 1
   const int H3 = 3 * H;
-  if (threadIdx.x == 0) flag = 1;
+  if (threadIdx.x == 0) {
+    flag = 1;
+    cold = XlCold{(xl_gu32*)err, (xl_gu32*)err_out, (xl_gf32*)dgx, N, D, H, bt * LB, ub * LU};
+  }
   const int slot_floats = G * UBX * LRB;
   const __amdgpu_buffer_rsrc_t x_rs =
       __builtin_amdgcn_make_buffer_rsrc(ring, (short)0, 2 * slot_floats * 4, 0x00020000);
@@ -544,23 +673,17 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
   // per-wave timeline (DS2_GRU_STAMPS=2): [step][block][wave][6] = step start, hand-off wait
   // done, products done, io done (waves 1-3), reduction barrier done, published; lane 0 of
   // every wave (scripts/trace_gru.py)
-  const bool tracing = stamps != nullptr && lane == 0;
   auto trace_at = [&](int s, int p) __attribute__((always_inline)) {
-    if (tracing && s >= kXlTraceS0 && s < kXlTraceS0 + kXlTraceSteps)
-      stamps[(((int64_t)(s - kXlTraceS0) * gridDim.x + blockIdx.x) * LW + wave) * 6 + p] =
-          __builtin_amdgcn_s_memrealtime();
+    if constexpr (TRACE)
+      if (stamps != nullptr && lane == 0 && s >= kXlTraceS0 && s < kXlTraceS0 + kXlTraceSteps)
+        stamps[(((int64_t)(s - kXlTraceS0) * gridDim.x + blockIdx.x) * LW + wave) * 6 + p] =
+            __builtin_amdgcn_s_memrealtime();
   };
 
   // W_hh^T fragments: producer p, gate gt, half c, k slot i ->
   //   W_hh[gt H + 32 (p0 + p) + 8 (lane >> 4) + i][32 ub + 16 c + (lane & 15)]
-  Duo w[NPW][3][2];
-  auto wfr = [&](int p, int gt, int c) __attribute__((always_inline)) {   // producer p's fragments (p == NPW: from LDS)
-    if (p < NPW) return w[p < NPW ? p : 0][gt][c];
-    Duo r;
-    r.hi = __builtin_bit_cast(f16x8, wx[((wave * 6 + gt * 2 + c) * 2 + 0) * 64 + lane]);
-    r.lo = __builtin_bit_cast(f16x8, wx[((wave * 6 + gt * 2 + c) * 2 + 1) * 64 + lane]);
-    return r;
-  };
+  // [hi, lo] last; producer 0 in VGPRs, the others in AGPRs, producer NPW in LDS
+  u32x4 w[NPW][3][2][2];
   float unscale;   // 2^-e of the owner's unit (threadIdx.x & 31)
   {
     const float* W = d == 0 ? w_f : w_r;
@@ -621,18 +744,19 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
           f32x4 a, b;
           col(p, gt, c, a, b);
           const Duo dd = split2h(a, b, sc[c]);
+          const u32x4 dh = __builtin_bit_cast(u32x4, dd.hi), dl = __builtin_bit_cast(u32x4, dd.lo);
           if (p < NPW) {
-            w[p < NPW ? p : 0][gt][c] = dd;
+            w[p < NPW ? p : 0][gt][c][0] = p < kXlVgprWBwd ? dh : xl_agpr(dh);
+            w[p < NPW ? p : 0][gt][c][1] = p < kXlVgprWBwd ? dl : xl_agpr(dl);
           } else {
-            wx[((wave * 6 + gt * 2 + c) * 2 + 0) * 64 + lane] = __builtin_bit_cast(u32x4, dd.hi);
-            wx[((wave * 6 + gt * 2 + c) * 2 + 1) * 64 + lane] = __builtin_bit_cast(u32x4, dd.lo);
+            wx[((wave * 6 + gt * 2 + c) * 2 + 0) * 64 + lane] = dh;
+            wx[((wave * 6 + gt * 2 + c) * 2 + 1) * 64 + lane] = dl;
           }
         }
   }
   const int m = threadIdx.x >> 5;
   const int u = threadIdx.x & 31;
   const int n = bt * LB + m;
-  const int j = ub * LU + u;
   const bool owner = n < N;
   if (threadIdx.x < LB) slen[threadIdx.x] = bt * LB + (int)threadIdx.x < N ? lens[bt * LB + threadIdx.x] : 0;
   __syncthreads();
@@ -748,8 +872,10 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     }
     if (s == 0) io_issue(0);
     if (s > 0) {
+      int npl = np;   // opaque per step (as the forward's): scalar compares, no hoisted lane masks
+      asm volatile("" : "+s"(npl));
       // a wave whose wait timed out clears `flag`; the workgroup leaves at the reduction barrier
-      if (!kAblWait && !xl_wave_flags_wait(flags + p0, np, (unsigned)s, err, err_out) && lane == 0)
+      if (!kAblWait && !xl_wave_flags_wait(flags + p0, npl, (unsigned)s, cold) && lane == 0)
         flag = 0;
       asm volatile("" ::: "memory");
       trace_at(s, 1);
@@ -757,7 +883,7 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
       u32x4 r0[NPW + 1], r1[NPW + 1], r2[NPW + 1];
       f32x4 rs[NPW + 1];
       auto load_rec = [&](int p) __attribute__((always_inline)) {
-        const int base = p < np ? rb + p * LRB * 4 : 0x7ffff000;
+        const int base = p < npl ? rb + p * LRB * 4 : 0x7ffff000;
         r0[p] = __builtin_amdgcn_raw_buffer_load_b128(x_rs, base + lane * 16, 0, kSc1);
         r1[p] = __builtin_amdgcn_raw_buffer_load_b128(x_rs, base + 1024 + lane * 16, 0, kSc1);
         r2[p] = __builtin_amdgcn_raw_buffer_load_b128(x_rs, base + 2048 + lane * 16, 0, kSc1);
@@ -773,22 +899,22 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
       for (int p = 0; p < NPW + 1; ++p) {
         if (p + LWP < NPW + 1) load_rec(p + LWP);
         if (p + LWP == NPW) io_issue(s);
-        if (p < np) {
-          const f16x8 ar = __builtin_bit_cast(f16x8, r0[p]);
-          const f16x8 az = __builtin_bit_cast(f16x8, r1[p]);
-          const f16x8 an = __builtin_bit_cast(f16x8, r2[p]);
+        if (p < npl) {
+          f32x4 cc[4];
+          if (p < kXlVgprWBwd && p < NPW) {
+            xl_bwd_rec<false>(cc, r0[p], r1[p], r2[p], w[p < NPW ? p : 0]);
+          } else if (p < NPW) {
+            xl_bwd_rec<true>(cc, r0[p], r1[p], r2[p], w[p < NPW ? p : 0]);
+          } else {
+            u32x4 xw[3][2][2];
 #pragma unroll
-          for (int c = 0; c < 2; ++c) {
-            const f32x4 z4 = f32x4{0.f, 0.f, 0.f, 0.f};
-            const Duo w0 = wfr(p, 0, c), w1 = wfr(p, 1, c), w2 = wfr(p, 2, c);
-            f32x4 c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ar, w0.hi, z4, 0, 0, 0);
-            f32x4 c2 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ar, w0.lo, z4, 0, 0, 0);
-            c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(az, w1.hi, c1, 0, 0, 0);
-            c2 = __builtin_amdgcn_mfma_f32_16x16x32_f16(az, w1.lo, c2, 0, 0, 0);
-            c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(an, w2.hi, c1, 0, 0, 0);
-            c2 = __builtin_amdgcn_mfma_f32_16x16x32_f16(an, w2.lo, c2, 0, 0, 0);
-            acc[c] += (c1 + c2) * rs[p];
+            for (int k = 0; k < 12; ++k)
+              xw[k >> 2][(k >> 1) & 1][k & 1] = wx[(wave * 12 + k) * 64 + lane];
+            xl_bwd_rec<false>(cc, r0[p], r1[p], r2[p], xw);
           }
+          // (c1 + c2) 2^-e per sample row, in producer order
+          acc[0] += (cc[0] + cc[1]) * rs[p];
+          acc[1] += (cc[2] + cc[3]) * rs[p];
         }
       }
       trace_at(s, 2);
@@ -801,7 +927,7 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
         red[(wave * 16 + (lane >> 4) * 4 + i) * RC + 16 * c + (lane & 15)] = acc[c][i];
     __syncthreads();
     if (flag == 0) {
-      poison_rest(dgx, s, T, d == 0, N, D, n, d, H, j, H3, 3, owner);
+      xl_poison(cold, s, T, d == 0, d, 3, 3);
       return;
     }
     const float dyv = pin[m * LU + u], g_r = pin[256 + m * LU + u], g_z = pin[512 + m * LU + u];
@@ -989,15 +1115,17 @@ int gru_xl_active(int n, int h, int num_dirs) {
 size_t gru_xl_ctr_words() { return 520; }
 
 // K = producers per wave: K - 1 in registers + one from LDS
-static const Instance kFwdXl[] = {inst(2, gru_fwd_xl_kernel<1>), inst(4, gru_fwd_xl_kernel<3>),
-                                  inst(7, gru_fwd_xl_kernel<6>)};
-static const Instance kBwdXl[] = {inst(2, gru_bwd_xl_kernel<1, false>),
-                                  inst(4, gru_bwd_xl_kernel<3, false>),
-                                  inst(7, gru_bwd_xl_kernel<6, false>)};
+// [1]: the traced instantiations, run when the caller asked for stamps (DS2_GRU_STAMPS=2)
+#define DS2_XL_TABLE(K, ...) \
+  {inst(2, K<1, __VA_ARGS__>), inst(4, K<3, __VA_ARGS__>), inst(7, K<6, __VA_ARGS__>)}
+static const Instance kFwdXl[2][3] = {DS2_XL_TABLE(gru_fwd_xl_kernel, false),
+                                      DS2_XL_TABLE(gru_fwd_xl_kernel, true)};
+static const Instance kBwdXl[2][3] = {DS2_XL_TABLE(gru_bwd_xl_kernel, false, false),
+                                      DS2_XL_TABLE(gru_bwd_xl_kernel, false, true)};
 // the same with the row-maximum partials of dgates_x
-static const Instance kBwdXlRows[] = {inst(2, gru_bwd_xl_kernel<1, true>),
-                                      inst(4, gru_bwd_xl_kernel<3, true>),
-                                      inst(7, gru_bwd_xl_kernel<6, true>)};
+static const Instance kBwdXlRows[2][3] = {DS2_XL_TABLE(gru_bwd_xl_kernel, true, false),
+                                          DS2_XL_TABLE(gru_bwd_xl_kernel, true, true)};
+#undef DS2_XL_TABLE
 
 // ring bytes: forward 4 slots of 1-KB tiles, backward 2 slots of records (both within the
 // rings ds2_gru_fwd / ds2_gru_bwd carve for the 16-unit kernels)
@@ -1028,7 +1156,7 @@ bool launch_gru_fwd_xl(RnnShape s, RecFwd a, Handoff ho, hipStream_t st) {
   apply_spin_limit_env();
   apply_rnn_tune_env();
   int UBX = s.h / LU, BTX = s.BT(LB), FG = xl_force_global();
-  const void* fn = pick_instance(kFwdXl, (UBX + LW - 1) / LW);
+  const void* fn = pick_instance(kFwdXl[ho.stamps != nullptr], (UBX + LW - 1) / LW);
   if (fn == nullptr) return false;
   if (!xl_prepare(ho.ctrs, ho.ctr_bytes, nullptr, 0, ho.ring,
                   gru_xl_ring_bytes(s.n, s.h, s.d, false), st))
@@ -1048,7 +1176,9 @@ bool launch_gru_bwd_xl(RnnShape s, RecBwd a, Handoff ho, hipStream_t st) {
   apply_rnn_tune_env();
   int UBX = s.h / LU, BTX = s.BT(LB), FG = xl_force_global();
   const int need = (UBX + LW - 1) / LW;
-  const void* fn = a.rowp != nullptr ? pick_instance(kBwdXlRows, need) : pick_instance(kBwdXl, need);
+  const int tr = ho.stamps != nullptr;
+  const void* fn =
+      a.rowp != nullptr ? pick_instance(kBwdXlRows[tr], need) : pick_instance(kBwdXl[tr], need);
   if (fn == nullptr) return false;
   if (!xl_prepare(ho.ctrs, ho.ctr_bytes, a.camax,
                   a.camax != nullptr ? (size_t)2 * s.d * 3 * s.h : 0, nullptr, 0, st))

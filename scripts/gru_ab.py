@@ -7,6 +7,39 @@ import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "deepspeech.pytorch_amd"))
+
+# `libs name=path name=path ...`: builds of the library against each other (say the parent
+# commit's and the tree's), alternating AB_ROUNDS times in one call, one fresh child process per
+# turn (DS2_LIB_PATH).  Every child runs the product calls (forward; backward with bias
+# gradients, column maxima and the row-maximum partials) at the bench shape and at the shapes
+# of tests/test_gpu_gru_xl_instances.py, times them and prints a SHA-256 per output; the parent
+# prints the per-launch times and whether every output is bit-equal across the builds.
+LIB_SHAPES = [(501, 32, 800, 2), (27, 9, 288, 2), (29, 8, 416, 1), (31, 12, 544, 2), (33, 5, 672, 1)]
+if len(sys.argv) > 1 and sys.argv[1] == "libs":
+    import json
+    import subprocess
+    libs = [a.split("=", 1) for a in sys.argv[2:]]
+    seen, equal = {}, True
+    for r in range(int(os.environ.get("AB_ROUNDS", "3"))):
+        for name, path in libs:
+            out = subprocess.run([sys.executable, os.path.abspath(__file__), "libchild"],
+                                 env=dict(os.environ, DS2_LIB_PATH=os.path.abspath(path)),
+                                 capture_output=True, text=True, timeout=600)
+            if out.returncode != 0:
+                sys.exit(f"{name}: exit {out.returncode}\n{out.stdout}\n{out.stderr}")
+            for line in out.stdout.splitlines():
+                if not line.startswith("{"):
+                    continue
+                rec = json.loads(line)
+                ref = seen.setdefault(rec["shape"], rec["sha"])
+                diff = [k for k in ref if ref[k] != rec["sha"][k]]
+                equal = equal and not diff
+                print(f"{name}#{r} {rec['shape']:>16s} fwd {rec['fwd_us']:8.1f} us  bwd "
+                      f"{rec['bwd_us']:8.1f} us  " + ("bit-equal" if not diff else f"DIFFERS {diff}"),
+                      flush=True)
+    print("ALL BIT-EQUAL" if equal else "OUTPUTS DIFFER")
+    sys.exit(0 if equal else 1)
+
 import torch  # noqa: E402
 from ds2amd import _lib, ops  # noqa: E402
 
@@ -66,6 +99,51 @@ def timed(fn, reps=5):
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) / reps
 
+
+def lib_child():
+    import hashlib
+    import json
+    sha = lambda x: hashlib.sha256(x.detach().cpu().contiguous().numpy().tobytes()).hexdigest()[:16]
+    for (t, n, h, d) in LIB_SHAPES:
+        gg = torch.Generator(device="cpu").manual_seed(1)
+        xp = (torch.randn(t, n, d, 3 * h, generator=gg) * 0.5).to(dev)
+        ww = [(torch.rand(3 * h, h, generator=gg) * 0.06 - 0.03).to(dev) for _ in range(2)]
+        bb = [(torch.rand(3 * h, generator=gg) * 0.06 - 0.03).to(dev) for _ in range(2)]
+        ln = torch.tensor([max(1, t - 3 * i) for i in range(n)], dtype=torch.int32, device=dev)
+        dyy = torch.randn(t, n, h, generator=gg).to(dev)
+        o = {k: torch.zeros(t, n, d, c * h, device=dev) for k, c in
+             (("h_all", 1), ("gates", 4), ("dgx", 3), ("dgh", 3))}
+        db = [torch.zeros(3 * h, device=dev) for _ in range(4)]
+        col = torch.zeros(2 * d * 3 * h, dtype=torch.int32, device=dev)
+        row = torch.zeros(t * n, dtype=torch.int32, device=dev)
+        wf = torch.zeros(_lib.size("ds2_gru_fwd_workspace_size", n, h, d), dtype=torch.uint8, device=dev)
+        wb = torch.zeros(_lib.size("ds2_gru_row_amax_workspace_size", t, n, h, d), dtype=torch.uint8, device=dev)
+
+        def f():
+            _lib.call("ds2_gru_fwd", t, n, h, d, xp.data_ptr(), ww[0].data_ptr(), ww[1].data_ptr(),
+                      bb[0].data_ptr(), bb[1].data_ptr(), ln.data_ptr(), o["h_all"].data_ptr(),
+                      o["gates"].data_ptr(), None, wf.data_ptr(), wf.numel(), ops._stream())
+
+        def bk():
+            _lib.call("ds2_gru_bwd_bias_amax", t, n, h, d, dyy.data_ptr(), 1, ww[0].data_ptr(),
+                      ww[1].data_ptr(), o["h_all"].data_ptr(), o["gates"].data_ptr(), ln.data_ptr(),
+                      o["dgx"].data_ptr(), o["dgh"].data_ptr(), db[0].data_ptr(), db[1].data_ptr(),
+                      db[2].data_ptr(), db[3].data_ptr(), col.data_ptr(), None, wb.data_ptr(),
+                      wb.numel(), ops._stream())
+
+        tf = timed(f)
+        tb = timed(bk)
+        _lib.call("ds2_gru_row_amax", t, n, h, d, wb.data_ptr(), wb.numel(), row.data_ptr(), ops._stream())
+        torch.cuda.synchronize()
+        hs = {k: sha(v) for k, v in o.items()}
+        hs.update(col_amax=sha(col), row_amax=sha(row), dbias=sha(torch.cat(db)))
+        print(json.dumps({"shape": f"{t}x{n}x{h}x{d}", "fwd_us": tf * 1e3, "bwd_us": tb * 1e3, "sha": hs}),
+              flush=True)
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "libchild":
+    lib_child()
+    sys.exit(0)
 
 variants = {"x6": {"DS2_GRU_X6": "1", "DS2_RNN_TUNE": ""},
             "f32": {"DS2_GRU_X6": "0", "DS2_RNN_TUNE": ""}}

@@ -3,7 +3,10 @@
 Every workgroup stamps s_memrealtime (10 ns ticks) at {step start, wait done, staged,
 mfma+red done, arrived} for 16 steps; this prints the arrival skew inside each
 (direction, batch tile) group, the latency from the group's last arrival to the
-first / median / last consumer leaving its wait, and the phase lengths."""
+first / median / last consumer leaving its wait, and the phase lengths.
+
+DS2_GRU_STAMPS=2 (set below) also selects the traced instantiations of the XCD-local kernels
+(gru_xl.hip, TRACE = true): the product ones carry no stamp sites."""
 import os
 import sys
 

@@ -11,6 +11,7 @@
 // gradients) add up 1.3 M times.  Two reduction shapes:
 //   rows   : x is [R][C] (SequenceWise BatchNorm1d, model.py:28-43,89,336)
 //            block = 64 columns x 4 row groups, grid = column blocks x row chunks
+//            (also a masked [N][C][1][1] conv block: row = sample, its one position t = 0)
 //   planes : x is [outer][C][D][T] (BatchNorm2d, model.py:210,213)
 //            block = one (outer, channel) plane slice, threads stride along T
 #include "common.h"
@@ -25,8 +26,13 @@ enum RedMode { RED_STATS = 0, RED_BWD = 1 };
 // doubles per (part, channel) partial: stats (sum x, sum x^2, -), backward
 // (sum g, sum g*x, sum x)
 constexpr int kParts = 3;
-// doubles per channel of backward coefficients: k1, k2, k3, exact mean
-constexpr int kCoef = 4;
+// doubles per channel of backward coefficients: k1, k2, k3, exact mean, invstd
+constexpr int kCoef = 5;
+// channels of at most this many values take the backward's invstd from x in fp64, not the
+// stored float: g's part outside span{1, xhat} has count - 2 degrees of freedom, and at count 2
+// all of dx is k1 (g1 - g2) / 2 * (1 - xhat^2) = ... * eps * invstd^2 ~ 1e-6, of which the
+// float's rounding (6e-8 of xhat^2 ~ 1) is percents
+constexpr int kTinyCount = 8;
 
 struct BnBwdArgs {
   const float* mean;
@@ -73,7 +79,9 @@ __global__ __launch_bounds__(256) void reduce_rows_kernel(const float* __restric
         acc1 += (double)v * v;
       } else {
         float xhat;
-        const float g = bwd_g(dy[(int64_t)r * C + col], v, col, 0, 1, a, &xhat);
+        // masked rows (a [N][C][1][1] conv block): row r is sample r, its one position t = 0
+        const float g = bwd_g(dy[(int64_t)r * C + col], v, col, 0, a.masked ? a.lens[r] : 1, a,
+                              &xhat);
         acc0 += g;
         acc1 += (double)g * v;
         acc2 += v;
@@ -136,13 +144,14 @@ __global__ __launch_bounds__(256) void reduce_rows4_kernel(const float* __restri
       } else {
         const float4 d = *reinterpret_cast<const float4*>(dy + (int64_t)r * C + col);
         const float dd[4] = {d.x, d.y, d.z, d.w};
+        const bool live = !a.masked || a.lens[r] > 0;   // masked rows: row r is sample r, t = 0
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const float xhat = (vv[e] - mu[e]) * is[e];
           float g = dd[e];
           if (a.masked) {
             const float y2 = ga[e] * xhat + be[e];
-            g = (y2 > a.lo && y2 < a.hi) ? g : 0.f;
+            g = (live && y2 > a.lo && y2 < a.hi) ? g : 0.f;
           }
           acc0[e] += g;
           acc1[e] += (double)g * vv[e];
@@ -333,22 +342,35 @@ __global__ void eval_stats_kernel(const float* __restrict__ rm, const float* __r
 //   bias gradient (see ds2_bn_backward).
 __global__ __launch_bounds__(256) void bwd_final_kernel(
     const double* __restrict__ partial, int nparts, int C, double count, BnBwdArgs a,
-    int n_outer, int D, int T, double* __restrict__ coef, float* __restrict__ dgamma,
-    float* __restrict__ dbeta, float* __restrict__ dbias) {
+    const float* __restrict__ x, float eps, int n_outer, int D, int T, double* __restrict__ coef,
+    float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ dbias) {
   int c;
   double sum[3];
   if (!sum_parts<3>(partial, nparts, C, c, sum)) return;
   const double sg = sum[0];
   const double mean = sum[2] / count;
-  const double is = (double)a.invstd[c];
+  double is = (double)a.invstd[c];
+  if (eps > 0.f && count <= (double)kTinyCount) {
+    const int64_t inner = (int64_t)D * T;
+    double ss = 0.0;
+    for (int o = 0; o < n_outer; ++o)
+      for (int64_t j = 0; j < inner; ++j) {
+        const double dv = (double)x[((int64_t)o * C + c) * inner + j] - mean;
+        ss += dv * dv;
+      }
+    is = 1.0 / sqrt(ss / count + (double)eps);
+  }
   const double sgx = is * (sum[1] - mean * sg);     // sum(g * xhat)
   const double gbar = sg / count;
   const double gxbar = sgx / count;
-  const double k1 = (double)a.gamma[c] * is;
+  // one value per channel (R = 1): g == mean(g) and xhat == 0, so dx is identically 0 -- with
+  // k1 the apply's fused k1 * g - k[1] would leave the rounding of k[1] = k1 * mean(g)
+  const double k1 = count > 1.0 ? (double)a.gamma[c] * is : 0.0;
   coef[c * kCoef + 0] = k1;
   coef[c * kCoef + 1] = k1 * gbar;
   coef[c * kCoef + 2] = k1 * gxbar;
   coef[c * kCoef + 3] = mean;
+  coef[c * kCoef + 4] = is;
   if (dgamma != nullptr) dgamma[c] = static_cast<float>(sgx);
   if (dbeta != nullptr) dbeta[c] = static_cast<float>(sg);
   if (dbias != nullptr) {
@@ -496,7 +518,7 @@ __global__ __launch_bounds__(256) void tnf_to_nft_kernel(const float* __restrict
   }
 }
 
-// backward apply over [outer][C][D][T] (rows case: D = T = 1 -> inner = 1).  grid
+// backward apply over [outer][C][D][T] (D T > 1; D = T = 1 is bwd_apply_rows_kernel).  grid
 // (ceil(T / 256), ceil(D / BA_ROWS), outer * C): a thread takes BA_ROWS rows d of one column
 // t, all loads issued before the math (one element per thread ran at ~2.8 TB/s)
 constexpr int BA_ROWS = 4;
@@ -524,7 +546,7 @@ __global__ void bwd_apply_planes_kernel(const float* __restrict__ dy, const floa
     const int64_t idx = ((int64_t)oc * D + d0 + r) * T + t;
     float xhat32;
     const float g = bwd_g(dv[r], xv[r], c, t, len, a, &xhat32);   // mask as the forward's
-    const double xhat = ((double)xv[r] - k[3]) * (double)a.invstd[c];
+    const double xhat = ((double)xv[r] - k[3]) * k[4];
     float v = static_cast<float>(k[0] * g - k[1] - k[2] * xhat);
     if (a.masked && t >= len) v = 0.f;
     dx[idx] = v;
@@ -539,8 +561,16 @@ __global__ void bwd_apply_rows_kernel(const float* __restrict__ dy, const float*
        i += (int64_t)gridDim.x * blockDim.x) {
     const int c = static_cast<int>(i % C);
     const double* k = coef + c * kCoef;
-    const double xhat = ((double)x[i] - k[3]) * (double)a.invstd[c];
-    dx[i] = static_cast<float>(k[0] * dy[i] - k[1] - k[2] * xhat);
+    const double xhat = ((double)x[i] - k[3]) * k[4];
+    float g = dy[i];
+    int len = 1;
+    if (a.masked) {   // D = T = 1 under a mask: the planes apply's mask, row = sample, t = 0
+      float xhat32;
+      len = a.lens[i / C];
+      g = bwd_g(g, x[i], c, 0, len, a, &xhat32);
+    }
+    const float v = static_cast<float>(k[0] * g - k[1] - k[2] * xhat);
+    dx[i] = len > 0 ? v : 0.f;
   }
 }
 
@@ -663,9 +693,9 @@ ds2_status_t ds2_bn_apply_mask_htanh(const float* x, int n, int c, int d, int t,
 ds2_status_t ds2_bn_backward(const float* dy, int dy_layout, const float* x, int outer, int c,
                              int d, int t, const float* mean, const float* invstd,
                              const float* gamma, const float* beta, int masked,
-                             const int* lens, float lo, float hi, float* dx, float* dgamma,
-                             float* dbeta, float* dbias_in, void* ws, size_t ws_bytes,
-                             ds2_stream_t stream) {
+                             const int* lens, float lo, float hi, float eps, float* dx,
+                             float* dgamma, float* dbeta, float* dbias_in, void* ws,
+                             size_t ws_bytes, ds2_stream_t stream) {
   if (outer < 1 || c < 1 || d < 1 || t < 1) return DS2_INVALID_VALUE;
   if (dy_layout == 1 && !masked) return DS2_INVALID_VALUE;
   if (masked && lens == nullptr) return DS2_INVALID_VALUE;
@@ -697,8 +727,8 @@ ds2_status_t ds2_bn_backward(const float* dy, int dy_layout, const float* x, int
                        st, x, g_src, c, d, t, a, partial);
   }
   hipLaunchKernelGGL(bwd_final_kernel, dim3(cdiv(c, 64)), dim3(256), 0, st, partial,
-                     (int)nparts, c, (double)outer * inner, a, outer, d, t, coef, dgamma, dbeta,
-                     dbias_in);
+                     (int)nparts, c, (double)outer * inner, a, x, eps, outer, d, t, coef, dgamma,
+                     dbeta, dbias_in);
   if (inner == 1) {
     hipLaunchKernelGGL(bwd_apply_rows_kernel, dim3(grid_cap((int64_t)outer * c, 256)), dim3(256),
                        0, st, g_src, x, (int64_t)outer, c, a, coef, dx);

@@ -137,8 +137,8 @@ ds2_status_t ds2_bn_relu_dropout_bwd(const float* dy, const float* y, const floa
   const ds2_status_t e = launch_status("ds2_bn_relu_dropout_bwd");
   if (e != DS2_OK) return e;
   return ds2_bn_backward(dz, 0, x, rows, c, 1, 1, mean, invstd, gamma, beta, 0, nullptr, 0.f, 0.f,
-                         dx, dgamma, dbeta, nullptr, static_cast<char*>(ws) + off, ws_bytes - off,
-                         stream);
+                         /*eps: not known here, the stored invstd at every count*/ 0.f, dx, dgamma,
+                         dbeta, nullptr, static_cast<char*>(ws) + off, ws_bytes - off, stream);
 }
 
 }  // extern "C"

@@ -86,8 +86,8 @@ _PROTOS = {
     "ds2_bn_apply_mask_htanh": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp,
                                          _vp, _c_f, _c_f, _vp, _c_int, _vp]),
     "ds2_bn_backward": (_c_int, [_vp, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp,
-                                 _vp, _c_int, _vp, _c_f, _c_f, _vp, _vp, _vp, _vp, _vp, _sz,
-                                 _vp]),
+                                 _vp, _c_int, _vp, _c_f, _c_f, _c_f, _vp, _vp, _vp, _vp, _vp,
+                                 _sz, _vp]),
     "ds2_gru_fwd_workspace_size": (_sz, [_c_int, _c_int, _c_int]),
     "ds2_gru_cache_floats": (_sz, [_c_int, _c_int, _c_int, _c_int]),
     "ds2_gru_fwd": (_c_int, [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

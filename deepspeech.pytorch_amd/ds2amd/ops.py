@@ -522,9 +522,10 @@ def bn_dropout_apply_amax(x2d, mean, invstd, gamma, beta, relu: bool, drop):
 
 
 def bn_backward(dy, dy_layout, x, outer, c, d, t, mean, invstd, gamma, beta, masked=False,
-                lens=None, lo=0.0, hi=20.0, want_dbias=False, bias=None):
+                lens=None, lo=0.0, hi=20.0, want_dbias=False, bias=None, eps=0.0):
     """dgamma / dbeta (/ dbias of the preceding conv) land in the parameters' gradient
-    slots when they have one (grad_like)."""
+    slots when they have one (grad_like).  eps: the forward's (channels of a few values then
+    take their invstd from x in fp64, see ds2_bn_backward); 0 if not known."""
     dx = torch.empty(outer, c, d, t, device=x.device, dtype=_F32)
     dgamma = grad_like(gamma)
     dbeta = grad_like(beta)
@@ -535,8 +536,8 @@ def bn_backward(dy, dy_layout, x, outer, c, d, t, mean, invstd, gamma, beta, mas
     ws = _ws(_lib.size("ds2_bn_workspace_size", outer, c, d * t), x.device)
     _lib.call("ds2_bn_backward", dy.data_ptr(), dy_layout, x.data_ptr(), outer, c, d, t,
               mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), int(masked),
-              _p(lens), float(lo), float(hi), dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
-              _p(dbias), ws.data_ptr(), ws.numel(), _stream())
+              _p(lens), float(lo), float(hi), float(eps), dx.data_ptr(), dgamma.data_ptr(),
+              dbeta.data_ptr(), _p(dbias), ws.data_ptr(), ws.numel(), _stream())
     return dx, dgamma, dbeta, dbias
 
 
@@ -858,20 +859,20 @@ class ConvBlockFn(torch.autograd.Function):
                   float(hi), y.data_ptr(), int(out_layout), _stream())
         ctx.save_for_backward(x, z, lens, weight, gamma, beta, mean, invstd)
         ctx.bias = bias   # only its identity (gradient slot) is used in backward
-        ctx.cfg = (stride, padding, lo, hi, out_layout, bias is not None, training)
+        ctx.cfg = (stride, padding, lo, hi, out_layout, bias is not None, training, eps)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, z, lens, weight, gamma, beta, mean, invstd = ctx.saved_tensors
-        stride, padding, lo, hi, out_layout, has_bias, training = ctx.cfg
+        stride, padding, lo, hi, out_layout, has_bias, training, eps = ctx.cfg
         if not training:
             raise _lib.Ds2Error("ConvBlockFn backward in eval mode is not supported")
         dy = dy.contiguous()
         n, c, d, t = z.shape
         dz, dgamma, dbeta, dbias = bn_backward(dy, out_layout, z, n, c, d, t, mean, invstd, gamma,
                                                beta, masked=True, lens=lens, lo=lo, hi=hi,
-                                               want_dbias=has_bias, bias=ctx.bias)
+                                               want_dbias=has_bias, bias=ctx.bias, eps=eps)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = conv2d_dgrad(dz, weight, x.shape, stride, padding)
@@ -900,6 +901,7 @@ class SeqBatchNormFn(torch.autograd.Function):
         ctx.save_for_backward(x2d, gamma, beta, mean, invstd)
         ctx.training = training
         ctx.drop = drop
+        ctx.eps = eps
         return y
 
     @staticmethod
@@ -911,7 +913,8 @@ class SeqBatchNormFn(torch.autograd.Function):
         dy = dy.contiguous()
         if ctx.drop is not None:
             dy = dropout_apply(dy, *ctx.drop)
-        dx, dgamma, dbeta, _ = bn_backward(dy, 0, x2d, r, c, 1, 1, mean, invstd, gamma, beta)
+        dx, dgamma, dbeta, _ = bn_backward(dy, 0, x2d, r, c, 1, 1, mean, invstd, gamma, beta,
+                                           eps=ctx.eps)
         return dx.view(r, c), dgamma, dbeta, None, None, None, None, None, None
 
 

@@ -335,13 +335,17 @@ ds2_status_t ds2_bn_apply_mask_htanh(const float* x, int n, int c, int d, int t,
  * out_layout above; layout 1 only with masked != 0).  Writes dx
  * ([outer][c][d][t]), dgamma, dbeta (overwritten) and, if dbias_in != NULL, the
  * gradient of the per-channel bias added before the masked BN (the conv bias;
- * exact closed form, see bn.hip).  dx may not alias dy.                      */
+ * exact closed form, see bn.hip).  dx may not alias dy.  eps: the forward's, or
+ * <= 0 if not known.  With it, channels of at most 8 values take invstd from x in
+ * fp64 and not from the float `invstd`, whose rounding is percents of dx when a
+ * channel holds 2 values (dx ~ eps invstd^2 there); larger channels and the mask
+ * decisions always use the stored floats.                                     */
 ds2_status_t ds2_bn_backward(const float* dy, int dy_layout, const float* x, int outer, int c,
                              int d, int t, const float* mean, const float* invstd,
                              const float* gamma, const float* beta, int masked,
-                             const int* lens, float lo, float hi, float* dx, float* dgamma,
-                             float* dbeta, float* dbias_in, void* ws, size_t ws_bytes,
-                             ds2_stream_t stream);
+                             const int* lens, float lo, float hi, float eps, float* dx,
+                             float* dgamma, float* dbeta, float* dbias_in, void* ws,
+                             size_t ws_bytes, ds2_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* Bidirectional GRU recurrence (torch gate order r, z, n), packed-sequence

@@ -1138,9 +1138,9 @@ def test_ctc_infeasible_and_module(dev):
 
 
 # ---------------------------------------------------------------------------- softmax / greedy
-def test_softmax_tnc(dev):
+def _softmax_tnc_case(dev, t, n, c):
     g = torch.Generator().manual_seed(1)
-    x = torch.randn(17, 5, 30, generator=g, dtype=torch.float64) * 4
+    x = torch.randn(t, n, c, generator=g, dtype=torch.float64) * 4
     xd = x.float().to(dev).requires_grad_(True)
     p = ops.SoftmaxTNCFn.apply(xd)
     ref = F.softmax(x.transpose(0, 1), -1)
@@ -1150,6 +1150,62 @@ def test_softmax_tnc(dev):
     xr = x.clone().requires_grad_(True)
     F.softmax(xr.transpose(0, 1), -1).backward(dp)
     _close(xd.grad, xr.grad, 1e-5, "softmax bwd")
+    # accumulate=1 adds the same gradient onto what the destination holds
+    dst0 = torch.randn(t, n, c, generator=g, dtype=torch.float64)
+    dst = dst0.float().to(dev)
+    _lib.call("ds2_softmax_tnc_bwd", p.detach().data_ptr(), dp.float().to(dev).data_ptr(), t, n,
+              c, dst.data_ptr(), 1, ops._stream())
+    _close(dst, dst0.float().double() + xr.grad, 1e-5, "softmax bwd accumulate")
+
+
+def test_softmax_tnc(dev):
+    _softmax_tnc_case(dev, 17, 5, 30)
+
+
+@pytest.mark.parametrize("t,n,c", [(1, 1, 1), (3, 1, 64), (7, 3, 29), (5, 2, 63)])
+def test_softmax_tnc_shapes(dev, t, n, c):
+    """One wave per (t, n) row, lanes over C, 4 rows per block: one lane, all 64 lanes, 63, and
+    row counts 1, 3, 21, 10 that leave the last block part-filled (17 x 5 x 30 is
+    test_softmax_tnc); same bounds, and the backward's accumulate flag."""
+    _softmax_tnc_case(dev, t, n, c)
+
+
+def test_softmax_tnc_extreme_logits(dev):
+    """Logits spanning +-1e4 with some entries at -inf (never a whole row): probabilities
+    finite, summing to 1 within 1e-6, exactly 0 where the logit is -inf, and within 1e-6 of
+    float64."""
+    t, n, c = 7, 3, 29
+    g = torch.Generator().manual_seed(2)
+    x = (torch.rand(t, n, c, generator=g) * 2 - 1) * 1e4
+    x[..., 0] = torch.linspace(-1e4, 1e4, t * n).view(t, n)     # the span is reached in full
+    gone = torch.rand(t, n, c, generator=g) < 0.2
+    gone[..., 1:3] = False                                       # never a whole row
+    x[gone] = float("-inf")
+    # near-ties at the top of a row, so that more than one probability is non-zero
+    others = x.clone()
+    others[..., 2] = float("-inf")
+    x[..., 2] = others.amax(-1) - torch.rand(t, n, generator=g)
+    p = ops.softmax_tnc(x.to(dev)).cpu()
+    ref = F.softmax(x.double().transpose(0, 1), -1)
+    assert torch.isfinite(p).all().item()
+    assert (p.double().sum(-1) - 1).abs().max().item() <= 1e-6
+    assert not p[gone.transpose(0, 1)].any().item()
+    assert ((p > 0).sum(-1) >= 2).all().item()
+    _close(p, ref, 1e-6, "softmax extreme")
+
+
+def test_softmax_tnc_rejects_wide_rows(dev):
+    """c = 65 (more classes than a wave has lanes) is DS2_UNSUPPORTED_SHAPE from both entry
+    points, before any launch."""
+    lib = _lib.load()
+    t, n, c = 3, 2, 65
+    x = torch.zeros(t, n, c, device=dev)
+    p, d = torch.zeros(n, t, c, device=dev), torch.zeros(t, n, c, device=dev)
+    assert lib.ds2_softmax_tnc(x.data_ptr(), t, n, c, p.data_ptr(), ops._stream()) == 2
+    assert lib.ds2_softmax_tnc_bwd(p.data_ptr(), p.data_ptr(), t, n, c, d.data_ptr(), 0,
+                                   ops._stream()) == 2
+    assert lib.ds2_softmax_tnc_bwd(p.data_ptr(), p.data_ptr(), t, n, c, d.data_ptr(), 1,
+                                   ops._stream()) == 2
 
 
 def test_greedy_decode_bit_exact(dev, golden_dir):

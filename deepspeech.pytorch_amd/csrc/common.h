@@ -11,6 +11,7 @@
 #include <stddef.h>
 
 #include "../../include/ds2hip.h"
+#include "../../include/ds2hip_test.h"   // the DS2_RUNG_* values of RnnLaunchRec
 
 namespace ds2 {
 
@@ -33,6 +34,27 @@ inline ds2_status_t launch_status(const char* where) {
     return DS2_HIP_ERROR;
   }
   return DS2_OK;
+}
+
+// What the recurrent entry point last called on this thread launched (ds2_test_rnn_last_launch,
+// include/ds2hip_test.h; rung = its DS2_RUNG_* value).  Host only and thread-local as the
+// error string: rnn_rec_reset at the entry point, rnn_rec_launch after every launch that
+// went out -- the first one sets the fields, each one counts.
+struct RnnLaunchRec {
+  int rung, k, c, bts, launches, grid, same_xcd;
+};
+RnnLaunchRec& rnn_rec();
+inline void rnn_rec_reset() { rnn_rec() = RnnLaunchRec{0, 0, 0, 0, 0, 0, 0}; }
+inline void rnn_rec_launch(int rung, int k, int c, int bts, int grid, int same_xcd) {
+  RnnLaunchRec& r = rnn_rec();
+  if (r.launches++ == 0) {
+    r.rung = rung;
+    r.k = k;
+    r.c = c;
+    r.bts = bts;
+    r.grid = grid;
+    r.same_xcd = same_xcd;
+  }
 }
 
 inline int cdiv(int64_t a, int64_t b) { return static_cast<int>((a + b - 1) / b); }

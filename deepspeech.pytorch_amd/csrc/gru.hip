@@ -1203,6 +1203,7 @@ ds2_status_t ds2_gru_fwd(int t_max, int n, int h, int num_dirs, const float* xpr
                          const float* b_hh_r, const int* lens, float* h_all, float* gates,
                          unsigned* err_out, void* ws, size_t ws_bytes, ds2_stream_t stream) {
   if (t_max < 0 || n < 0 || h < 1 || (num_dirs != 1 && num_dirs != 2)) return DS2_INVALID_VALUE;
+  rnn_rec_reset();
   if (h > KC_FWD) return DS2_UNSUPPORTED_SHAPE;
   if (t_max == 0 || n == 0) return DS2_OK;
   const RnnShape s = {t_max, n, h, num_dirs};
@@ -1217,8 +1218,8 @@ ds2_status_t ds2_gru_fwd(int t_max, int n, int h, int num_dirs, const float* xpr
   apply_rnn_tune_env();
   int T = t_max, N = n, H = h, D = num_dirs, UB = s.UB(), BT = s.BT();
   const int KS = (h + 3) / 4;
-  const void* step_fn = pick_instance(kFwdStep, (KS + GW - 1) / GW);
-  if (step_fn == nullptr) return DS2_UNSUPPORTED_SHAPE;
+  const Instance step_fn = pick_instance(kFwdStep, (KS + GW - 1) / GW);
+  if (step_fn.fn == nullptr) return DS2_UNSUPPORTED_SHAPE;
   float* wp = ws_at<float>(ws, L.wp);
   const int grid = mapped_grid(UB * num_dirs, BT);
   const bool persistent = persistent_enabled() && grid <= num_cus() && s.fits32(1);
@@ -1236,9 +1237,10 @@ ds2_status_t ds2_gru_fwd(int t_max, int n, int h, int num_dirs, const float* xpr
     // the dynamic LDS keeps one workgroup per CU (every workgroup gets a whole CU's SIMDs)
     void* args[] = {&T, &N, &H, &D, &UB, &BT, &xproj, &w_hh_f, &w_hh_r, &b_hh_f,
                     &b_hh_r, &lens, &h_all, &gates, &ho.ring, &ho.ctrs, &ho.err, &ho.stamps};
-    const void* fn = pick_instance(kFwdDop, (UB + GW - 1) / GW);
-    if (rung("ds2_gru_fwd", ho, false, 0, st, &rc,
-             [&] { return launch_fn(fn, grid, GT, args, kDopPadLds, st); }))
+    const Instance fn = pick_instance(kFwdDop, (UB + GW - 1) / GW);
+    if (rung("ds2_gru_fwd", ho, false, 0, st, &rc, [&] {
+          return launch_fn(fn, DS2_RUNG_DOP, 1, 0, grid, GT, args, kDopPadLds, st);
+        }))
       return rc;
   }
   hipLaunchKernelGGL(pack_fwd_kernel<3>, dim3(grid_cap((int64_t)num_dirs * UB * KS * 192)),
@@ -1248,17 +1250,17 @@ ds2_status_t ds2_gru_fwd(int t_max, int n, int h, int num_dirs, const float* xpr
     int trace = stamp_mode() == 2 ? 1 : 0;
     void* args[] = {&T, &N, &H, &D, &UB, &BT, &xproj, &wp, &b_hh_f, &b_hh_r, &lens,
                     &h_all, &gates, &ho.ctrs, &ho.err, &ho.stamps, &trace};
-    const void* fn = pick_instance(kFwdPersist, persist_ksw((KS + GW - 1) / GW, KC_FWD));
-    if (rung("ds2_gru_fwd", ho, true, 0, st, &rc,
-             [&] { return launch_fn(fn, grid, GT, args, 0, st); }))
+    const Instance fn = pick_instance(kFwdPersist, persist_ksw((KS + GW - 1) / GW, KC_FWD));
+    if (rung("ds2_gru_fwd", ho, true, 0, st, &rc, [&] {
+          return launch_fn(fn, DS2_RUNG_LDS_PERSIST, 1, 0, grid, GT, args, 0, st);
+        }))
       return rc;   // else one launch per step
   }
 
   int step = 0;
   void* args[] = {&step, &T, &N, &H, &D, &UB, &BT, &xproj, &wp, &b_hh_f, &b_hh_r, &lens,
                   &h_all, &gates};
-  for (step = 0; step < t_max; ++step)
-    (void)hipLaunchKernel(step_fn, dim3(grid), dim3(GT), args, 0, st);
+  for (step = 0; step < t_max; ++step) launch_step(step_fn, grid, GT, args, st);
   return launch_status("ds2_gru_fwd");
 }
 
@@ -1338,8 +1340,8 @@ static ds2_status_t gru_bwd_run(const RnnShape& s, RecBwd a, unsigned* err_out, 
   int T = s.t, N = s.n, H = s.h, D = s.d, UB = s.UB(), BT = s.BT();
   const int KS = (3 * s.h + 3) / 4;
   const int chunk_ks = (std::min(3 * s.h, KC_BWD) + 3) / 4;
-  const void* step_fn = pick_instance(kBwdStep, (chunk_ks + GW - 1) / GW + 1);
-  if (step_fn == nullptr) return DS2_UNSUPPORTED_SHAPE;
+  const Instance step_fn = pick_instance(kBwdStep, (chunk_ks + GW - 1) / GW + 1);
+  if (step_fn.fn == nullptr) return DS2_UNSUPPORTED_SHAPE;
   float* wpt = ws_at<float>(ws, L.wpt);
   float* dhs = ws_at<float>(ws, L.dhs);
   const int grid = mapped_grid(UB * D, BT);
@@ -1361,11 +1363,12 @@ static ds2_status_t gru_bwd_run(const RnnShape& s, RecBwd a, unsigned* err_out, 
     void* args[] = {&T, &N, &H, &D, &UB, &BT, &a.dy, &a.dy_dirs, &a.w_hh_f, &a.w_hh_r, &a.state,
                     &a.gates, &a.lens, &a.dgx, &a.dgh, &ho.ring, &ho.ctrs, &ho.err, &ho.stamps,
                     &a.dbp};
-    const void* fn = pick_instance(kBwdDop, (3 * UB + GW - 1) / GW);
+    const Instance fn = pick_instance(kBwdDop, (3 * UB + GW - 1) / GW);
     if (rung("ds2_gru_bwd", ho, true, 0, st, &rc,
              [&] { return launch_bwd16(3, s, a, ho, st, 0, BT, &done.camax); }) ||
-        rung("ds2_gru_bwd", ho, false, 0, st, &rc,
-             [&] { return launch_fn(fn, grid, GT, args, kDopPadLds, st); })) {
+        rung("ds2_gru_bwd", ho, false, 0, st, &rc, [&] {
+          return launch_fn(fn, DS2_RUNG_DOP, 1, 0, grid, GT, args, kDopPadLds, st);
+        })) {
       done.summed = a.dbp != nullptr;   // both sum the bias partials themselves
       return rc;
     }
@@ -1375,17 +1378,17 @@ static ds2_status_t gru_bwd_run(const RnnShape& s, RecBwd a, unsigned* err_out, 
   if (persistent && 3 * H <= KC_BWD && (H % 4) == 0) {
     void* args[] = {&T, &N, &H, &D, &UB, &BT, &a.dy, &a.dy_dirs, &wpt, &a.state, &a.gates,
                     &a.lens, &a.dgx, &a.dgh, &ho.ctrs, &ho.err, &ho.stamps};
-    const void* fn = pick_instance(kBwdPersist, persist_ksw((KS + GW - 1) / GW, KC_BWD));
-    if (rung("ds2_gru_bwd", ho, true, 0, st, &rc,
-             [&] { return launch_fn(fn, grid, GT, args, 0, st); }))
+    const Instance fn = pick_instance(kBwdPersist, persist_ksw((KS + GW - 1) / GW, KC_BWD));
+    if (rung("ds2_gru_bwd", ho, true, 0, st, &rc, [&] {
+          return launch_fn(fn, DS2_RUNG_LDS_PERSIST, 1, 0, grid, GT, args, 0, st);
+        }))
       return rc;
   }
 
   int step = 0;
   void* args[] = {&step, &T, &N, &H, &D, &UB, &BT, &a.dy, &a.dy_dirs, &wpt, &a.state, &a.gates,
                   &a.lens, &a.dgx, &a.dgh, &dhs};
-  for (step = 0; step < s.t; ++step)
-    (void)hipLaunchKernel(step_fn, dim3(grid), dim3(GT), args, 0, st);
+  for (step = 0; step < s.t; ++step) launch_step(step_fn, grid, GT, args, st);
   return launch_status("ds2_gru_bwd");
 }
 
@@ -1402,6 +1405,10 @@ static ds2_status_t gru_bwd_bias_impl(int t_max, int n, int h, int num_dirs, con
   if (t_max < 0 || n < 0 || h < 1 || (num_dirs != 1 && num_dirs != 2)) return DS2_INVALID_VALUE;
   if (gates == nullptr) return DS2_INVALID_VALUE;
   if (dy_dirs != 1 && dy_dirs != num_dirs) return DS2_INVALID_VALUE;
+  // a kernel without the fused maxima is followed by ds2_amax's column pass (float4 columns):
+  // decline before anything is launched, not after the recurrence ran
+  if (camax != nullptr && (num_dirs * 3 * h) % 4 != 0) return DS2_UNSUPPORTED_SHAPE;
+  rnn_rec_reset();
   const bool want_db = db_ih_f != nullptr;
   if (want_db && (db_hh_f == nullptr || (num_dirs == 2 && (db_ih_r == nullptr || db_hh_r == nullptr))))
     return DS2_INVALID_VALUE;
@@ -1509,6 +1516,7 @@ ds2_status_t ds2_rnn_fwd_ws(int t_max, int n, int h, int num_dirs, const float* 
                             const float* b_hh_r, const int* lens, float* h_all, unsigned* err_out,
                             void* ws, size_t ws_bytes, ds2_stream_t stream) {
   if (t_max < 0 || n < 0 || h < 1 || (num_dirs != 1 && num_dirs != 2)) return DS2_INVALID_VALUE;
+  rnn_rec_reset();
   if (t_max == 0 || n == 0) return DS2_OK;
   if (xproj == nullptr || w_hh_f == nullptr || b_hh_f == nullptr || lens == nullptr ||
       h_all == nullptr || (num_dirs == 2 && (w_hh_r == nullptr || b_hh_r == nullptr)))
@@ -1550,6 +1558,10 @@ ds2_status_t ds2_rnn_bwd_ws(int t_max, int n, int h, int num_dirs, const float* 
                             void* ws, size_t ws_bytes, ds2_stream_t stream) {
   if (t_max < 0 || n < 0 || h < 1 || (num_dirs != 1 && num_dirs != 2)) return DS2_INVALID_VALUE;
   if (dy_dirs != 1 && dy_dirs != num_dirs) return DS2_INVALID_VALUE;
+  // the per-step fallback takes the maxima from ds2_amax's column pass (float4 columns): decline
+  // before anything is launched, not after the recurrence ran
+  if (col_amax != nullptr && (num_dirs * h) % 4 != 0) return DS2_UNSUPPORTED_SHAPE;
+  rnn_rec_reset();
   if (ws == nullptr || ws_bytes < ds2_rnn_bwd_workspace_size(n, h, num_dirs))
     return DS2_WORKSPACE_TOO_SMALL;
   hipStream_t st = as_stream(stream);

@@ -1489,9 +1489,10 @@ static const Instance kLstmBwdH1[] = {
 // keeps map_work's interleaved layout, bit-identical results).  The grid queries and the
 // launches both come through here.  fn == nullptr: declined.
 struct Pick16 {
-  const void* fn;
+  Instance e;   // fn == nullptr: declined
   int grid, same_xcd;
   bool h3;   // an fp16x3 backward: it also leaves the column maxima (camax)
+  int rung;  // of the launch record
 };
 
 // the GRU kernels are on by default; DS2_GRU_X6=0 selects the fp32-MFMA kernels (gru.hip: the
@@ -1501,26 +1502,31 @@ static bool declines16(int ng, int h) {
 }
 
 static Pick16 pick_fwd16(int ng, const RnnShape& s) {
-  Pick16 p = {nullptr, -1, 0, false};
+  Pick16 p = {{0, nullptr}, -1, 0, false, DS2_RUNG_H3_16};
   if (declines16(ng, s.h) || (ng != 1 && ng != 3)) return p;
   const int need = ((s.UB() + 1) / 2 + XW - 1) / XW;
-  p.fn = ng == 1                 ? pick_instance(kRnnFwd, need)
-         : env_off("DS2_GRU_H3") ? pick_instance(kGruFwdX6, need)
-                                 : pick_instance(kGruFwdH3, need);
-  if (p.fn != nullptr) p.grid = group_grid(s.UB(), s.BT(), s.d, &p.same_xcd);
+  const bool x6 = ng == 3 && env_off("DS2_GRU_H3");
+  p.e = ng == 1 ? pick_instance(kRnnFwd, need)
+        : x6    ? pick_instance(kGruFwdX6, need)
+                : pick_instance(kGruFwdH3, need);
+  if (x6) p.rung = DS2_RUNG_X6_16;
+  if (p.e.fn != nullptr) p.grid = group_grid(s.UB(), s.BT(), s.d, &p.same_xcd);
   return p;
 }
 
 static Pick16 pick_bwd16(int ng, const RnnShape& s, int bt_launch) {
-  Pick16 p = {nullptr, -1, 0, false};
+  Pick16 p = {{0, nullptr}, -1, 0, false, DS2_RUNG_H3_16};
   if (declines16(ng, s.h)) return p;
   const int UB = s.UB(), need = (UB + BW - 1) / BW;
-  p.fn = ng == 1   ? pick_instance(kRnnBwd, need)
-         : ng == 4 ? pick_instance(kLstmBwd, need)
-         : env_off("DS2_GRU_H3_BWD") ? nullptr : pick_instance(kGruBwdH3, need);
-  p.h3 = p.fn != nullptr;
-  if (p.fn == nullptr && ng == 3) p.fn = pick_instance(kGruBwdX6, ((3 * UB + 1) / 2 + BW - 1) / BW);
-  if (p.fn != nullptr) p.grid = group_grid(UB, bt_launch, s.d, &p.same_xcd);
+  if (ng == 1) p.e = pick_instance(kRnnBwd, need);
+  else if (ng == 4) p.e = pick_instance(kLstmBwd, need);
+  else if (!env_off("DS2_GRU_H3_BWD")) p.e = pick_instance(kGruBwdH3, need);
+  p.h3 = p.e.fn != nullptr;
+  if (p.e.fn == nullptr && ng == 3) {
+    p.e = pick_instance(kGruBwdX6, ((3 * UB + 1) / 2 + BW - 1) / BW);
+    p.rung = DS2_RUNG_X6_16;
+  }
+  if (p.e.fn != nullptr) p.grid = group_grid(UB, bt_launch, s.d, &p.same_xcd);
   return p;
 }
 
@@ -1535,13 +1541,14 @@ static void apply_knobs() {
 
 bool launch_fwd16(int ng, RnnShape s, RecFwd a, Handoff ho, hipStream_t st) {
   Pick16 p = pick_fwd16(ng, s);
-  if (p.fn == nullptr) return false;
+  if (p.e.fn == nullptr) return false;
   apply_knobs();
   int UB = s.UB(), BT = s.BT();
   void* args[] = {&s.t, &s.n, &s.h, &s.d, &UB, &BT, &a.xproj, &a.w_hh_f, &a.w_hh_r, &a.b_hh_f,
                   &a.b_hh_r, &a.lens, &a.h_all, &a.gates, &ho.ring, &ho.ctrs, &ho.err,
                   &ho.stamps, &p.same_xcd};
-  return rnn_launch(p.fn, dim3(p.grid), dim3(XT), args, ho.lds_pad, st) == hipSuccess;
+  return launch_rec(p.e.fn, Ran{p.rung, p.e.k, 0, 1, p.same_xcd}, dim3(p.grid), dim3(XT), args,
+                    ho.lds_pad, st);
 }
 
 // a.camax (nullable) is zeroed by the caller; ring and counters are sized for bt_launch groups
@@ -1551,13 +1558,14 @@ bool launch_bwd16(int ng, RnnShape s, RecBwd a, Handoff ho, hipStream_t st, int 
                   int bt_launch, bool* camax_fused) {
   if (camax_fused != nullptr) *camax_fused = false;
   Pick16 p = pick_bwd16(ng, s, bt_launch);
-  if (p.fn == nullptr) return false;
+  if (p.e.fn == nullptr) return false;
   apply_knobs();
   int UB = s.UB(), NB = tile0 * GB;
   void* args[] = {&s.t, &s.n, &s.h, &s.d, &UB, &bt_launch, &a.dy, &a.dy_dirs, &a.w_hh_f,
                   &a.w_hh_r, &a.state, &a.gates, &a.lens, &a.dgx, &a.dgh, &ho.ring, &ho.ctrs,
                   &ho.err, &ho.stamps, &a.dbp, &p.same_xcd, &a.camax, &NB};
-  const bool ok = rnn_launch(p.fn, dim3(p.grid), dim3(BW * 64), args, ho.lds_pad, st) == hipSuccess;
+  const bool ok = launch_rec(p.e.fn, Ran{p.rung, p.e.k, 0, 1, p.same_xcd}, dim3(p.grid),
+                             dim3(BW * 64), args, ho.lds_pad, st);
   if (ok && p.h3 && a.camax != nullptr && camax_fused != nullptr) *camax_fused = true;
   return ok;
 }
@@ -1573,10 +1581,10 @@ size_t h3_bwd_ring_bytes(int n_tiles, int h, int num_dirs, int ng) {
 // tiles.  Its kernel takes a shorter argument list (no dgh, stamps, dbp or tile offset), so it
 // keeps a launcher of its own.
 static Pick16 pick_h1(const RnnShape& s) {
-  Pick16 p = {nullptr, -1, 0, false};
+  Pick16 p = {{0, nullptr}, -1, 0, false, DS2_RUNG_SINGLE_TERM};
   if ((s.h % GU) != 0) return p;
-  p.fn = pick_instance(kLstmBwdH1, (s.UB() + BW - 1) / BW);
-  if (p.fn != nullptr) p.grid = group_grid(s.UB(), s.BT(L1B), s.d, &p.same_xcd);
+  p.e = pick_instance(kLstmBwdH1, (s.UB() + BW - 1) / BW);
+  if (p.e.fn != nullptr) p.grid = group_grid(s.UB(), s.BT(L1B), s.d, &p.same_xcd);
   return p;
 }
 
@@ -1589,13 +1597,14 @@ size_t lstm_h1_ring_bytes(int n, int h, int num_dirs) {
 
 bool launch_lstm_bwd_h1(RnnShape s, RecBwd a, Handoff ho, hipStream_t st) {
   Pick16 p = pick_h1(s);
-  if (p.fn == nullptr) return false;
+  if (p.e.fn == nullptr) return false;
   apply_knobs();
   int UB = s.UB(), BT = s.BT(L1B);
   void* args[] = {&s.t, &s.n, &s.h, &s.d, &UB, &BT, &a.dy, &a.dy_dirs, &a.w_hh_f, &a.w_hh_r,
                   &a.state, &a.gates, &a.lens, &a.dgx, &ho.ring, &ho.ctrs, &ho.err, &p.same_xcd,
                   &a.camax};
-  return rnn_launch(p.fn, dim3(p.grid), dim3(BW * 64), args, ho.lds_pad, st) == hipSuccess;
+  return launch_rec(p.e.fn, Ran{p.rung, p.e.k, 0, L1B / GB, p.same_xcd}, dim3(p.grid),
+                    dim3(BW * 64), args, ho.lds_pad, st);
 }
 
 }  // namespace ds2

@@ -1156,8 +1156,8 @@ bool launch_gru_fwd_xl(RnnShape s, RecFwd a, Handoff ho, hipStream_t st) {
   apply_spin_limit_env();
   apply_rnn_tune_env();
   int UBX = s.h / LU, BTX = s.BT(LB), FG = xl_force_global();
-  const void* fn = pick_instance(kFwdXl[ho.stamps != nullptr], (UBX + LW - 1) / LW);
-  if (fn == nullptr) return false;
+  const Instance fn = pick_instance(kFwdXl[ho.stamps != nullptr], (UBX + LW - 1) / LW);
+  if (fn.fn == nullptr) return false;
   if (!xl_prepare(ho.ctrs, ho.ctr_bytes, nullptr, 0, ho.ring,
                   gru_xl_ring_bytes(s.n, s.h, s.d, false), st))
     return false;
@@ -1165,7 +1165,8 @@ bool launch_gru_fwd_xl(RnnShape s, RecFwd a, Handoff ho, hipStream_t st) {
   void* args[] = {&s.t, &s.n, &s.h, &s.d, &UBX, &BTX, &a.xproj, &a.w_hh_f, &a.w_hh_r, &a.b_hh_f,
                   &a.b_hh_r, &a.lens, &a.h_all, &a.gates, &ho.ring, &xl, &ho.err, &ho.err_out,
                   &ho.stamps, &FG};
-  return rnn_launch(fn, dim3(8 * UBX), dim3(LT), args, ho.lds_pad, st) == hipSuccess;
+  return launch_rec(fn.fn, Ran{DS2_RUNG_XCD_LOCAL, fn.k, 0, 0, 1}, dim3(8 * UBX), dim3(LT), args,
+                    ho.lds_pad, st);
 }
 
 // a.dbp: [ceil(n / 8)][D][4][H] partials (nullable); a.camax as launch_bwd16's, but zeroed by
@@ -1177,9 +1178,9 @@ bool launch_gru_bwd_xl(RnnShape s, RecBwd a, Handoff ho, hipStream_t st) {
   int UBX = s.h / LU, BTX = s.BT(LB), FG = xl_force_global();
   const int need = (UBX + LW - 1) / LW;
   const int tr = ho.stamps != nullptr;
-  const void* fn =
+  const Instance fn =
       a.rowp != nullptr ? pick_instance(kBwdXlRows[tr], need) : pick_instance(kBwdXl[tr], need);
-  if (fn == nullptr) return false;
+  if (fn.fn == nullptr) return false;
   if (!xl_prepare(ho.ctrs, ho.ctr_bytes, a.camax,
                   a.camax != nullptr ? (size_t)2 * s.d * 3 * s.h : 0, nullptr, 0, st))
     return false;
@@ -1187,7 +1188,8 @@ bool launch_gru_bwd_xl(RnnShape s, RecBwd a, Handoff ho, hipStream_t st) {
   void* args[] = {&s.t, &s.n, &s.h, &s.d, &UBX, &BTX, &a.dy, &a.dy_dirs, &a.w_hh_f, &a.w_hh_r,
                   &a.state, &a.gates, &a.lens, &a.dgx, &a.dgh, &ho.ring, &xl, &ho.err,
                   &ho.err_out, &ho.stamps, &a.dbp, &a.camax, &a.rowp, &FG};
-  return rnn_launch(fn, dim3(8 * UBX), dim3(LT), args, ho.lds_pad, st) == hipSuccess;
+  return launch_rec(fn.fn, Ran{DS2_RUNG_XCD_LOCAL, fn.k, 0, 0, 1}, dim3(8 * UBX), dim3(LT), args,
+                    ho.lds_pad, st);
 }
 
 // the row-maximum partials of launch_gru_bwd_xl: bytes, and their reduction to out[t_max n]

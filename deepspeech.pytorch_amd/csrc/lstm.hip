@@ -936,6 +936,7 @@ ds2_status_t ds2_lstm_fwd(int t_max, int n, int h, int num_dirs, const float* xp
                           float* gates, unsigned* err_out, void* ws, size_t ws_bytes,
                           ds2_stream_t stream) {
   if (t_max < 0 || n < 0 || h < 1 || (num_dirs != 1 && num_dirs != 2)) return DS2_INVALID_VALUE;
+  rnn_rec_reset();
   if (h > LKC_FWD) return DS2_UNSUPPORTED_SHAPE;
   if (t_max == 0 || n == 0) return DS2_OK;
   const RnnShape s = {t_max, n, h, num_dirs};
@@ -949,8 +950,8 @@ ds2_status_t ds2_lstm_fwd(int t_max, int n, int h, int num_dirs, const float* xp
   apply_spin_limit_env();
   int T = t_max, N = n, H = h, D = num_dirs, UB = s.UB(), BT = s.BT();
   const int KS = (h + 3) / 4;
-  const void* step_fn = pick_instance(kFwdStep, (KS + GW - 1) / GW);
-  if (step_fn == nullptr) return DS2_UNSUPPORTED_SHAPE;
+  const Instance step_fn = pick_instance(kFwdStep, (KS + GW - 1) / GW);
+  if (step_fn.fn == nullptr) return DS2_UNSUPPORTED_SHAPE;
   float* wp = ws_at<float>(ws, L.wp);
   float* cs = ws_at<float>(ws, L.cs);
   const Handoff ho = {ws_at<float>(ws, L.ring), ws_at<unsigned>(ws, L.ctrs), L.ctr_bytes,
@@ -964,9 +965,10 @@ ds2_status_t ds2_lstm_fwd(int t_max, int n, int h, int num_dirs, const float* xp
   // wave rounded up to an instantiated 1, 2, 4 or 8 (extra blocks are predicated off)
   if (persistent && (h % GU) == 0 && UB <= 8 * GW) {
     const int nbw = (UB + GW - 1) / GW;
-    const void* fn = pick_instance(kFwdDop[env_off("DS2_LSTM_H3") ? 0 : 1][bts - 1], nbw);
+    const int h3 = env_off("DS2_LSTM_H3") ? 0 : 1;
+    const Instance fn = pick_instance(kFwdDop[h3][bts - 1], nbw);
     const size_t ring_fill = nbw > 4 ? 0 : L.ring_bytes;   // the sentinel ring (HM = 1)
-    if (fn != nullptr &&
+    if (fn.fn != nullptr &&
         for_each_chunk("ds2_lstm_fwd", ho, D, BTW, ct, ring_fill, st, &rc,
                        [&](int b0, int bt, Handoff c) {
                          int NB = b0 * GB * bts, XG = 0;
@@ -975,7 +977,8 @@ ds2_status_t ds2_lstm_fwd(int t_max, int n, int h, int num_dirs, const float* xp
                          void* args[] = {&T, &N, &H, &D, &UB, &bt, &xproj, &w_hh_f, &w_hh_r,
                                          &b_hh_f, &b_hh_r, &lens, &h_all, &c_all, &gates, &c.ring,
                                          &c.ctrs, &c.err, &NB, &XG};
-                         return launch_fn(fn, grid, GT, args, kDopPadLds, st);
+                         return launch_fn(fn, h3 ? DS2_RUNG_DOP_H3 : DS2_RUNG_DOP, bts, XG, grid,
+                                          GT, args, kDopPadLds, st);
                        }))
       return rc;
   }
@@ -983,14 +986,15 @@ ds2_status_t ds2_lstm_fwd(int t_max, int n, int h, int num_dirs, const float* xp
                      dim3(256), 0, st, w_hh_f, w_hh_r, h, num_dirs, UB, KS, wp);
   const int kp = persist_ksw((KS + GW - 1) / GW, LKC_FWD);
   if (persistent && (h % 4) == 0 && kp > 0 && kp <= 32) {
-    const void* fn = pick_instance(kFwdPersist[bts - 1], kp);
-    if (fn != nullptr &&
+    const Instance fn = pick_instance(kFwdPersist[bts - 1], kp);
+    if (fn.fn != nullptr &&
         for_each_chunk("ds2_lstm_fwd", ho, D, BTW, ct, 0, st, &rc,
                        [&](int b0, int bt, Handoff c) {
                          int NB = b0 * GB * bts;
                          void* args[] = {&T, &N, &H, &D, &UB, &bt, &xproj, &wp, &b_hh_f, &b_hh_r,
                                          &lens, &h_all, &c_all, &gates, &c.ctrs, &c.err, &NB};
-                         return launch_fn(fn, mapped_grid(UB * D, bt), GT, args, 0, st);
+                         return launch_fn(fn, DS2_RUNG_LDS_PERSIST, bts, 0,
+                                          mapped_grid(UB * D, bt), GT, args, 0, st);
                        }))
       return rc;   // else one launch per step
   }
@@ -998,8 +1002,7 @@ ds2_status_t ds2_lstm_fwd(int t_max, int n, int h, int num_dirs, const float* xp
   int step = 0;
   void* args[] = {&step, &T, &N, &H, &D, &UB, &BT, &xproj, &wp, &b_hh_f, &b_hh_r, &lens,
                   &h_all, &c_all, &gates, &cs};
-  for (step = 0; step < t_max; ++step)
-    (void)hipLaunchKernel(step_fn, dim3(grid), dim3(GT), args, 0, st);
+  for (step = 0; step < t_max; ++step) launch_step(step_fn, grid, GT, args, st);
   return launch_status("ds2_lstm_fwd");
 }
 
@@ -1053,6 +1056,7 @@ ds2_status_t ds2_lstm_bwd_half(int t_max, int n, int h, int num_dirs, const floa
                                const float* gates, const int* lens, float* dgates,
                                unsigned* err_out, void* ws, size_t ws_bytes, ds2_stream_t stream) {
   if (t_max < 0 || n < 0 || h < 1 || (num_dirs != 1 && num_dirs != 2)) return DS2_INVALID_VALUE;
+  rnn_rec_reset();
   if (t_max == 0 || n == 0) return DS2_OK;
   if (gates == nullptr || c_all == nullptr) return DS2_INVALID_VALUE;
   if (dy_dirs != 1 && dy_dirs != num_dirs) return DS2_INVALID_VALUE;
@@ -1084,6 +1088,7 @@ ds2_status_t ds2_lstm_bwd(int t_max, int n, int h, int num_dirs, const float* dy
                           const float* gates, const int* lens, float* dgates, unsigned* err_out,
                           void* ws, size_t ws_bytes, ds2_stream_t stream) {
   if (t_max < 0 || n < 0 || h < 1 || (num_dirs != 1 && num_dirs != 2)) return DS2_INVALID_VALUE;
+  rnn_rec_reset();
   if (t_max == 0 || n == 0) return DS2_OK;
   if (gates == nullptr || c_all == nullptr) return DS2_INVALID_VALUE;
   if (dy_dirs != 1 && dy_dirs != num_dirs) return DS2_INVALID_VALUE;
@@ -1097,8 +1102,8 @@ ds2_status_t ds2_lstm_bwd(int t_max, int n, int h, int num_dirs, const float* dy
   int T = t_max, N = n, H = h, D = num_dirs, UB = s.UB(), BT = s.BT(), DYD = dy_dirs;
   const int KS = h;
   const int chunk_ks = std::min(4 * h, LKC_BWD) / 4;
-  const void* step_fn = pick_instance(kBwdStep, (chunk_ks + GW - 1) / GW);
-  if (step_fn == nullptr) return DS2_UNSUPPORTED_SHAPE;
+  const Instance step_fn = pick_instance(kBwdStep, (chunk_ks + GW - 1) / GW);
+  if (step_fn.fn == nullptr) return DS2_UNSUPPORTED_SHAPE;
   float* wpt = ws_at<float>(ws, L.wpt);
   float* dcs = ws_at<float>(ws, L.dcs);
   ds2_status_t rc = DS2_OK;
@@ -1149,7 +1154,9 @@ ds2_status_t ds2_lstm_bwd(int t_max, int n, int h, int num_dirs, const float* dy
                          const int grid = group_grid(UB, bt, D, &xm);
                          void* args[] = {&T, &N, &H, &D, &UB, &bt, &dy, &DYD, &wpt, &c_all, &gates,
                                          &lens, &dgates, &c.ctrs, &c.err, &NB};
-                         return launch_fn(xm ? k->fx : k->fn, grid, GT, args, 0, st);
+                         return launch_rec(xm ? k->fx : k->fn,
+                                           Ran{DS2_RUNG_LDS_PERSIST, k->k, k->c, bts, xm},
+                                           dim3(grid), dim3(GT), args, 0, st);
                        }))
       return rc;
   }
@@ -1157,8 +1164,7 @@ ds2_status_t ds2_lstm_bwd(int t_max, int n, int h, int num_dirs, const float* dy
   int step = 0;
   void* args[] = {&step, &T, &N, &H, &D, &UB, &BT, &dy, &DYD, &wpt, &c_all, &gates, &lens,
                   &dgates, &dcs};
-  for (step = 0; step < t_max; ++step)
-    (void)hipLaunchKernel(step_fn, dim3(grid), dim3(GT), args, 0, st);
+  for (step = 0; step < t_max; ++step) launch_step(step_fn, grid, GT, args, st);
   return launch_status("ds2_lstm_bwd");
 }
 

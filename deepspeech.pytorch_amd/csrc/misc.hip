@@ -17,6 +17,9 @@ void set_last_error_text(const char* where, const char* what) {
   snprintf(g_last_error, sizeof(g_last_error), "%s: %s", where, what);
 }
 
+static thread_local RnnLaunchRec g_rnn_rec = {0, 0, 0, 0, 0, 0, 0};
+RnnLaunchRec& rnn_rec() { return g_rnn_rec; }
+
 static inline int grid_for(int64_t work, int block) {
   int64_t g = (work + block - 1) / block;
   if (g > 2048) g = 2048;
@@ -431,6 +434,14 @@ const char* ds2_status_string(ds2_status_t s) {
 }
 
 const char* ds2_last_error(void) { return g_last_error; }
+
+ds2_status_t ds2_test_rnn_last_launch(int* out) {
+  if (out == nullptr) return DS2_INVALID_VALUE;
+  const RnnLaunchRec r = rnn_rec();
+  const int v[7] = {r.rung, r.k, r.c, r.bts, r.launches, r.grid, r.same_xcd};
+  for (int i = 0; i < 7; ++i) out[i] = v[i];
+  return DS2_OK;
+}
 
 const char* ds2_version(void) { return "libds2hip 0.1.0 gfx950"; }
 

@@ -136,6 +136,7 @@ ds2_status_t ds2_rnn_fwd(int t_max, int n, int h, int num_dirs, const float* xpr
                          const float* b_hh_r, const int* lens, float* h_all,
                          ds2_stream_t stream) {
   if (t_max < 0 || n < 0 || h < 1 || (num_dirs != 1 && num_dirs != 2)) return DS2_INVALID_VALUE;
+  rnn_rec_reset();
   if (t_max == 0 || n == 0) return DS2_OK;
   if (xproj == nullptr || w_hh_f == nullptr || b_hh_f == nullptr || lens == nullptr ||
       h_all == nullptr || (num_dirs == 2 && (w_hh_r == nullptr || b_hh_r == nullptr)))
@@ -146,9 +147,11 @@ ds2_status_t ds2_rnn_fwd(int t_max, int n, int h, int num_dirs, const float* xpr
   }
   const dim3 grid(cdiv(h, RN_U), cdiv(n, RN_M), num_dirs);
   hipStream_t st = as_stream(stream);
-  for (int s = 0; s < t_max; ++s)
+  for (int s = 0; s < t_max; ++s) {
     hipLaunchKernelGGL(rnn_fwd_step_kernel, grid, dim3(RN_T), 0, st, s, t_max, n, h, num_dirs,
                        xproj, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lens, h_all);
+    rnn_rec_launch(DS2_RUNG_PER_STEP, 0, 0, 1, (int)(grid.x * grid.y * grid.z), 0);
+  }
   return launch_status("ds2_rnn_fwd");
 }
 
@@ -157,6 +160,7 @@ ds2_status_t ds2_rnn_bwd(int t_max, int n, int h, int num_dirs, const float* dy,
                          const int* lens, float* dgates, ds2_stream_t stream) {
   if (t_max < 0 || n < 0 || h < 1 || (num_dirs != 1 && num_dirs != 2)) return DS2_INVALID_VALUE;
   if (dy_dirs != 1 && dy_dirs != num_dirs) return DS2_INVALID_VALUE;
+  rnn_rec_reset();
   if (t_max == 0 || n == 0) return DS2_OK;
   if (dy == nullptr || w_hh_f == nullptr || h_all == nullptr || lens == nullptr ||
       dgates == nullptr || (num_dirs == 2 && w_hh_r == nullptr))
@@ -164,9 +168,11 @@ ds2_status_t ds2_rnn_bwd(int t_max, int n, int h, int num_dirs, const float* dy,
   if (num_dirs == 1) w_hh_r = w_hh_f;
   const dim3 grid(cdiv(h, RN_U), cdiv(n, RN_M), num_dirs);
   hipStream_t st = as_stream(stream);
-  for (int s = 0; s < t_max; ++s)
+  for (int s = 0; s < t_max; ++s) {
     hipLaunchKernelGGL(rnn_bwd_step_kernel, grid, dim3(RN_T), 0, st, s, t_max, n, h, num_dirs, dy,
                        dy_dirs, w_hh_f, w_hh_r, h_all, lens, dgates);
+    rnn_rec_launch(DS2_RUNG_PER_STEP, 0, 0, 1, (int)(grid.x * grid.y * grid.z), 0);
+  }
   return launch_status("ds2_rnn_bwd");
 }
 

@@ -60,11 +60,11 @@ struct Instance {
 template <typename F>
 static inline Instance inst(int k, F* f) { return Instance{k, reinterpret_cast<const void*>(f)}; }
 template <size_t N>
-static inline const void* pick_instance(const Instance (&table)[N], int need) {
-  if (need < 1) return nullptr;
-  for (const Instance& e : table)
-    if (need <= e.k) return e.fn;
-  return nullptr;
+static inline Instance pick_instance(const Instance (&table)[N], int need) {
+  if (need >= 1)
+    for (const Instance& e : table)
+      if (need <= e.k) return e;
+  return Instance{0, nullptr};
 }
 
 // --- workspace carve-up --------------------------------------------------------------------
@@ -122,10 +122,29 @@ struct Handoff {
   size_t lds_pad;
 };
 
+// What a launch is to the launch record (ds2_test_rnn_last_launch): the ladder's rung, the
+// table entry's key (k; c: kBwdPersist's chunks), 16-sample tiles per workgroup, same-XCD flag
+struct Ran {
+  int rung, k, c, bts, same_xcd;
+};
+// every recurrence launch of the ladders goes through here: the record is written where the
+// launch went out, by the code that chose the kernel
+static inline bool launch_rec(const void* fn, const Ran& r, dim3 grid, dim3 block, void** args,
+                              size_t lds, hipStream_t st) {
+  if (fn == nullptr || rnn_launch(fn, grid, block, args, lds, st) != hipSuccess) return false;
+  rnn_rec_launch(r.rung, r.k, r.c, r.bts, (int)(grid.x * grid.y * grid.z), r.same_xcd);
+  return true;
+}
 // a kernel picked from a table, launched as the persistent kernels are (rnn_launch)
-static inline bool launch_fn(const void* fn, int grid, int block, void** args, size_t lds,
-                             hipStream_t st) {
-  return fn != nullptr && rnn_launch(fn, dim3(grid), dim3(block), args, lds, st) == hipSuccess;
+static inline bool launch_fn(const Instance& e, int rung, int bts, int same_xcd, int grid,
+                             int block, void** args, size_t lds, hipStream_t st) {
+  return launch_rec(e.fn, Ran{rung, e.k, 0, bts, same_xcd}, dim3(grid), dim3(block), args, lds, st);
+}
+// one launch of a per-step kernel (plain launch, no LDS pad); failures surface in launch_status
+static inline void launch_step(const Instance& e, int grid, int block, void** args,
+                               hipStream_t st) {
+  if (hipLaunchKernel(e.fn, dim3(grid), dim3(block), args, 0, st) == hipSuccess)
+    rnn_rec_launch(DS2_RUNG_PER_STEP, e.k, 0, 1, grid, 0);
 }
 
 // --- the fallback ladders ------------------------------------------------------------------

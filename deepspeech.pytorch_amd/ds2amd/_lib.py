@@ -118,6 +118,7 @@ _PROTOS = {
                                    _c_i64, _c_f, _vp, _c_i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ds2_test_ring_traffic": (_c_int, [_vp, _c_i64, _c_int, _vp, _c_int, ctypes.c_double, _vp]),
     "ds2_test_beam_stamps": (_c_int, [_vp]),
+    "ds2_test_rnn_last_launch": (_c_int, [_vp]),
     "ds2_gru_bwd": (_c_int, [_c_int, _c_int, _c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp,
                              _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ds2_gru_bwd_bias": (_c_int, [_c_int, _c_int, _c_int, _c_int, _vp, _c_int, _vp, _vp, _vp,

@@ -10,6 +10,8 @@ from __future__ import annotations
 
 from typing import Optional, Tuple
 
+import collections
+import ctypes
 import os
 import numpy as np
 import torch
@@ -84,6 +86,23 @@ def check_rnn_status(device=None, reset: bool = True) -> None:
     msg = rnn_status_error(v)
     if msg is not None:
         raise _lib.Ds2Error(msg)
+
+
+# Test hook (ds2hip_test.h): what the recurrent entry point last called on THIS thread launched.
+# rung is a row of DESIGN.md's ladder table; k (and c, kBwdPersist's chunks) the key of the
+# instance-table entry that ran; bts the 16-sample tiles per workgroup; launches the batch chunks
+# (t for the per-step kernels); grid and same_xcd those of the first launch.
+RNN_RUNGS = ("none", "xcd_local", "h3_16", "x6_16", "dop", "dop_h3", "lds_persist",
+             "single_term", "per_step")
+RnnLaunch = collections.namedtuple("RnnLaunch", "rung k c bts launches grid same_xcd")
+
+
+def rnn_last_launch() -> RnnLaunch:
+    """The launch record of the calling thread.  autograd runs a LayerFn's backward on its own
+    worker thread: read the backward's record from there (a hook on the input's gradient)."""
+    out = (ctypes.c_int * 7)()
+    _lib.call("ds2_test_rnn_last_launch", ctypes.addressof(out))
+    return RnnLaunch(RNN_RUNGS[out[0]], *list(out)[1:])
 
 
 # ----------------------------------------------------------------------------
@@ -1256,7 +1275,8 @@ class GRULayerFn(torch.autograd.Function):
         dgh = torch.empty(t, n, nd, h3, device=dev, dtype=_F32)
         w_hh_f = weights[1]
         w_hh_r = weights[5] if nd == 2 else None
-        h3_scales = h3_enabled() and not bf16
+        # (the maxima need float4 columns, as ops.amax: else the GEMMs run without given scales)
+        h3_scales = h3_enabled() and not bf16 and (nd * h3) % 4 == 0
         want_rows = h3_scales and ctx.needs_input_grad[0]
         # with the dX GEMM's row scales wanted, room for the recurrence's row-maximum partials
         ws = _ws(_lib.size("ds2_gru_row_amax_workspace_size", t, n, h, nd) if want_rows
@@ -1328,8 +1348,9 @@ class RNNLayerFn(torch.autograd.Function):
         dg = torch.empty(t, n, nd, h, device=dev, dtype=_F32)
         ws = _ws(_lib.size("ds2_rnn_bwd_workspace_size", n, h, nd), dev)
         _guard_cooperative("rnn", n, h, nd)
+        # (the maxima need float4 columns, as ops.amax: else the GEMMs run without given scales)
         col_amax = (torch.empty(nd * h, dtype=_I32, device=dev)
-                    if h3_enabled() and not bf16 else None)
+                    if h3_enabled() and not bf16 and (nd * h) % 4 == 0 else None)
         _lib.call("ds2_rnn_bwd_ws", t, n, h, nd, dy.data_ptr(), dy_dirs, weights[1].data_ptr(),
                   _p(weights[5] if nd == 2 else None), h_all.data_ptr(), lens.data_ptr(),
                   dg.data_ptr(), _p(col_amax), rnn_status_word(dev).data_ptr(), ws.data_ptr(),

@@ -402,7 +402,9 @@ ds2_status_t ds2_gru_bwd_bias(int t_max, int n, int h, int num_dirs, const float
 /* ds2_gru_bwd_bias plus the column maxima of the gate gradients for the fp16x3 GEMMs that
  * follow (ds2_sgemm_amax_ws: dW_ih, dW_hh): col_amax[0, D 3H) = max over rows of |dgates_x|,
  * [D 3H, 2 D 3H) = the same of dgates_h, as float bits (ds2_amax's format).  The fp16x3
- * recurrence keeps them as it goes; any other kernel is followed by a column pass. */
+ * recurrence keeps them as it goes; any other kernel is followed by a column pass, so D 3H
+ * must be a multiple of 4 as for ds2_amax (DS2_UNSUPPORTED_SHAPE otherwise, nothing launched:
+ * call ds2_gru_bwd_bias). */
 ds2_status_t ds2_gru_bwd_bias_amax(int t_max, int n, int h, int num_dirs, const float* dy,
                                    int dy_dirs, const float* w_hh_f, const float* w_hh_r,
                                    const float* h_all, const float* gates, const int* lens,
@@ -595,7 +597,9 @@ ds2_status_t ds2_rnn_bwd(int t_max, int n, int h, int num_dirs, const float* dy,
  * one-gate fp16x3 instantiations of the GRU kernels, csrc/gru_split.hip), with the per-step
  * kernels above as the fallback for shapes they decline (H % 16 != 0, a grid past the CUs)
  * and DS2_RNN_PERSISTENT=0.  err_out as for ds2_gru_fwd.  col_amax (nullable): [D H] column
- * maxima of |dgates| as float bits (ds2_amax's format) for the fp16x3 weight-gradient GEMMs.
+ * maxima of |dgates| as float bits (ds2_amax's format) for the fp16x3 weight-gradient GEMMs;
+ * D H must then be a multiple of 4 as for ds2_amax (DS2_UNSUPPORTED_SHAPE otherwise, nothing
+ * launched: pass NULL).
  * ds2_rnn_bwd_grid: workgroups the persistent backward holds at once (0: per-step kernels). */
 size_t ds2_rnn_fwd_workspace_size(int n, int h, int num_dirs);
 ds2_status_t ds2_rnn_fwd_ws(int t_max, int n, int h, int num_dirs, const float* xproj,

@@ -44,6 +44,34 @@ ds2_status_t ds2_test_ring_traffic(const float* bucket, int64_t count, int world
  * boundaries of a frame, then s_memrealtime at its start); buf = NULL turns it off.       */
 ds2_status_t ds2_test_beam_stamps(unsigned long long* buf);
 
+/* ------------------------------------------------------------------------ */
+/* ds2_test_rnn_last_launch: which kernel the recurrent entry point last called ON THIS THREAD
+ * launched (ds2_gru_fwd, ds2_gru_bwd*, ds2_rnn_fwd[_ws], ds2_rnn_bwd[_ws], ds2_lstm_fwd,
+ * ds2_lstm_bwd, ds2_lstm_bwd_half).  Host only: the record is reset at the entry point and
+ * written where a recurrence launch went out, by the dispatch itself -- nothing recomputes
+ * the choice.  out[7] =
+ *   [0] rung: a DS2_RUNG_* value, a row of DESIGN.md's ladder table (NONE: nothing launched)
+ *   [1] k: the instance key K of the table entry that ran (inst(K, ...); kBwdPersist's k;
+ *       0 for the per-step tanh RNN kernels, which have no table)
+ *   [2] c: kBwdPersist's chunk count, 0 elsewhere
+ *   [3] bts: 16-sample tiles per workgroup (the single-term backward's 32-sample tiles: 2;
+ *       the XCD-local kernels' 8-sample tiles: 0)
+ *   [4] launches: recurrence launches that went out (batch chunks; t_max for per-step)
+ *   [5] grid: workgroups of the first launch (x * y * z)
+ *   [6] same_xcd: the same-XCD flag passed to the first launch (XCD-local: 1)           */
+enum {
+  DS2_RUNG_NONE = 0,
+  DS2_RUNG_XCD_LOCAL = 1,    /* gru_xl.hip */
+  DS2_RUNG_H3_16 = 2,        /* 16-unit fp16x3 (GRU, one-gate RNN, four-gate LSTM backward) */
+  DS2_RUNG_X6_16 = 3,        /* 16-unit bf16x6 (GRU) */
+  DS2_RUNG_DOP = 4,          /* direct-operand: fp32 MFMA (GRU; LSTM forward, DS2_LSTM_H3=0) */
+  DS2_RUNG_DOP_H3 = 5,       /* direct-operand fp16x3 (LSTM forward) */
+  DS2_RUNG_LDS_PERSIST = 6,  /* LDS-staged persistent */
+  DS2_RUNG_SINGLE_TERM = 7,  /* single-term fp16 LSTM backward (ds2_lstm_bwd_half) */
+  DS2_RUNG_PER_STEP = 8      /* one launch per step */
+};
+ds2_status_t ds2_test_rnn_last_launch(int* out);
+
 #ifdef __cplusplus
 }
 #endif

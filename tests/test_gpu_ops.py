@@ -961,7 +961,8 @@ def test_lstm_persistent_equals_per_step(dev, h, n, monkeypatch):
 
 
 @pytest.mark.parametrize("n,t,h,bidir", [(64, 60, 1024, True), (40, 37, 256, False), (7, 9, 48, True),
-                                         (5, 8, 40, True)])
+                                         (5, 8, 40, True),
+                                         (33, 9, 400, True)])   # kLstmBwdH1<4> (H 272..512)
 def test_lstm_bwd_half_vs_fp32(dev, n, t, h, bidir):
     """ds2_lstm_bwd_half (cfg4's bf16 mode: the backward recurrence's W_hh^T product on one
     fp16 term per operand, 32-sample workgroups, one launch for batch 64) against ds2_lstm_bwd
@@ -996,6 +997,9 @@ def test_lstm_bwd_half_vs_fp32(dev, n, t, h, bidir):
         torch.cuda.synchronize()
         out[fn] = dg.cpu()
     ops.check_rnn_status(dev)
+    if h % 16 == 0:   # the single-term kernel itself ran: kLstmBwdH1<ceil(H / 128)> of 1, 2, 4, 8
+        ran = ops.rnn_last_launch()
+        assert (ran.rung, ran.k) == ("single_term", {48: 1, 256: 2, 400: 4, 1024: 8}[h]), ran
     ref, got = out["ds2_lstm_bwd"], out["ds2_lstm_bwd_half"]
     assert torch.isfinite(got).all()
     for i in range(n):   # rows past a sample's length are zero on both sides

@@ -13,6 +13,7 @@
 // Greedy: one wave per utterance; argmax (first maximum) per frame, then a
 // ballot/mbcnt compaction of the frames that survive blank/repeat removal
 // (ref decoder.py:165-197).
+#include <type_traits>
 #include "common.h"
 #include "../../include/ds2hip_test.h"
 
@@ -349,6 +350,14 @@ __global__ void greedy_kernel(const float* __restrict__ probs, int n, int t_max,
 // keep every candidate (k = entry * C + char < 4096) in the wave's registers
 constexpr int BEAM_SMALL = 32, BEAM_SMALL_C = 64;
 constexpr int BEAM_LARGE = 128, BEAM_LARGE_C = 32;
+// a third for beams of 33..128 over vocabularies of 33..64 (the reference's Cyrillic label
+// set at its default beam): up to 8192 candidates, so the candidate index takes 13 bits of
+// the key, a winner's pb / pnb are read back from its key and its entry's blank candidate
+// instead of being stored per candidate, and more than 4096 candidates are selected per
+// half (beam_select_half) and merged -- see DESIGN.md, "beams up to 128 over 33..64 labels"
+constexpr int BEAM_WIDE = 128, BEAM_WIDE_C = 64;
+constexpr int BEAM_WIDE_TCH = 64;   // its staging chunk
+constexpr int BEAM_LDS_PER_CU = 160 * 1024;
 // frames of probabilities staged in LDS at a time: a global load consumed inside the frame
 // loop would make the waitcnt pass wait (vmcnt(0)) for the previous frame's trie stores
 constexpr int BEAM_TCH = 128;
@@ -383,7 +392,7 @@ __device__ __forceinline__ unsigned long long beam_pack(float s, int key) {
 // selected keys are compacted into sk[] (LDS) and each is ranked by counting the selected
 // keys above it, so sel_k receives the winners' candidate indices in rank order (the order
 // of beam_better: score, then char, then index).  Returns the number selected.
-template <int NJ>
+template <int NJ, unsigned KMASK = 4095u>
 __device__ __forceinline__ int beam_select(const unsigned long long* ukey, int tot, int beam,
                                            int* sel_k, unsigned long long* sk, int lane,
                                            unsigned long long lb) {
@@ -426,7 +435,7 @@ __device__ __forceinline__ int beam_select(const unsigned long long* ukey, int t
         rank += kj > kr ? 1 : 0;
       }
       if (lane < ns && rank < beam)
-        sel_k[rank] = static_cast<int>((0xFFFFFFFFu - klo) & 4095u);
+        sel_k[rank] = static_cast<int>((0xFFFFFFFFu - klo) & KMASK);
       return beam;
     }
   }
@@ -458,7 +467,61 @@ __device__ __forceinline__ int beam_select(const unsigned long long* ukey, int t
     const unsigned long long kr = sk[r];
     int rank = 0;
     for (int j = 0; j < nsel; ++j) rank += sk[j] > kr ? 1 : 0;
-    sel_k[rank] = static_cast<int>((0xFFFFFFFFu - static_cast<unsigned>(kr)) & 4095u);
+    sel_k[rank] = static_cast<int>((0xFFFFFFFFu - static_cast<unsigned>(kr)) & KMASK);
+  }
+  return nsel;
+}
+
+// the inverse of beam_pack's score word (-0 comes back as +0)
+__device__ __forceinline__ float beam_unpack_score(unsigned long long key) {
+  const unsigned b = static_cast<unsigned>(key >> 32);
+  return __uint_as_float((b & 0x80000000u) ? (b & 0x7FFFFFFFu) : ~b);
+}
+
+// first stage of a selection over more candidates than one wave's registers hold: of the tot
+// keys at ukey[0, tot) (lane l holds keys l, l + 64, ... in NJ registers) keep those that can
+// be among the best `beam` of a superset -- the keys >= lb (lb as in beam_select: at least
+// `beam` keys of the superset are >= it; 0 = none) if at most `beam` of them, else the best
+// `beam` by beam_select's radix descent -- compacted into out[0, return value), unordered.
+// The best `beam` of the superset are the best `beam` of the union of its parts' outputs.
+template <int NJ>
+__device__ __forceinline__ int beam_select_half(const unsigned long long* ukey, int tot, int beam,
+                                                unsigned long long* out, int lane,
+                                                unsigned long long lb) {
+  unsigned long long ru[NJ];
+#pragma unroll
+  for (int jj = 0; jj < NJ; ++jj) {
+    const int k = lane + 64 * jj;
+    ru[jj] = k < tot ? ukey[k] : 0ull;
+  }
+  auto count_ge = [&](unsigned long long c) {
+    int n = 0;
+#pragma unroll
+    for (int jj = 0; jj < NJ; ++jj) n += __popcll(__ballot(ru[jj] >= c));
+    return n;
+  };
+  unsigned long long thr = lb != 0ull ? lb : 1ull;
+  if (count_ge(thr) > beam) {
+    unsigned long long t = 0ull;
+    for (int bit = 63; bit >= 0; --bit) {
+      const unsigned long long c = t | (1ull << bit);
+      const int n = count_ge(c);
+      if (n >= beam) {
+        t = c;
+        if (n == beam) break;
+      }
+    }
+    thr = t;   // the beam-th largest key or above it: exactly `beam` (unique) keys are >= thr
+  }
+  int nsel = 0;
+#pragma unroll
+  for (int jj = 0; jj < NJ; ++jj) {
+    const bool sel = ru[jj] >= thr;
+    const unsigned long long m = __ballot(sel);
+    if (sel)
+      out[nsel + __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(m >> 32),
+                                           __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(m), 0))] = ru[jj];
+    nsel += __popcll(m);
   }
   return nsel;
 }
@@ -697,6 +760,13 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(
     int64_t node_cap, int* __restrict__ out_ids, int* __restrict__ out_ts, int* __restrict__ out_lens,
     float* __restrict__ out_scores, BeamLm L) {
   constexpr int EPL = (BM + 63) / 64;   // beam entries per lane
+  // more candidates than 12 key bits and one wave's registers hold (the wide instantiation)
+  constexpr bool WIDE = BM * CM > 4096;
+  static_assert(BM * CM <= 8192 && CM <= 64, "candidate index: 13 bits, char + 1: 7 bits");
+  constexpr int KSTRIDE = WIDE ? 8192 : 4096;          // key = (char + 1) * KSTRIDE + k
+  constexpr unsigned KMASK = KSTRIDE - 1;
+  constexpr int TCH = WIDE ? BEAM_WIDE_TCH : BEAM_TCH;   // frames staged at a time
+  using rl_t = std::conditional_t<WIDE, unsigned short, int>;   // a candidate index
   // LM state per beam entry: trie state, the order-1 preceding words, the cached
   // alpha-scaled LM score of the entry's current word (used by a space extension and by
   // the final scoring); per frame the char an entry's dictionary reset consumes and its
@@ -720,9 +790,14 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(
   __shared__ int b_len[2][BM];   // prefix length (the node's depth): one back-tracking walk
   __shared__ float score[BM];
   __shared__ unsigned long long cmask[BM];   // chars of the entry's in-beam children
-  __shared__ float cpb[BM * CM], cpnb[BM * CM];
+  // every candidate's pb / pnb; the wide instantiation has no room for them and rebuilds a
+  // winner's pair: a blank candidate's is its entry's bl_pb / bl_pnb, an extension's is
+  // (-inf, its score), the score being the key's high word
+  constexpr int NCP = WIDE ? 1 : BM * CM;
+  __shared__ float cpb[NCP], cpnb[NCP];
   __shared__ unsigned long long ukey[BM * CM];   // beam_pack(score, key) per candidate k
   __shared__ unsigned long long sk_sel[BM > 64 ? BM : 64];   // the selected keys (beam_select)
+  __shared__ unsigned long long sk_half[WIDE ? 2 * BM : 1];  // the two halves' (beam_select_half)
   __shared__ float bl_sc[BM], bl_pb[BM], bl_pnb[BM];   // the blank candidate of each entry
   __shared__ int sel_k[BM];
   __shared__ int s_nb, s_nodes, s_nr;
@@ -730,9 +805,18 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(
   // pruned-but-alive children (their char frames are updated after the scoring loop); the
   // entries of the old beam that stay
   __shared__ unsigned long long b_km[BM];
-  __shared__ int rlist[BM * CM];
+  __shared__ rl_t rlist[BM * CM];
   __shared__ int kept[BM];
-  __shared__ float pch[BEAM_TCH * CM];
+  __shared__ float pch[TCH * CM];
+  static_assert(sizeof(b_dst) + sizeof(b_hist) + sizeof(b_lms) + sizeof(cstar) + sizeof(vmask) +
+                    sizeof(lp) + sizeof(allowed) + sizeof(order) + sizeof(b_node) +
+                    sizeof(b_last) + sizeof(b_pb) + sizeof(b_pnb) + sizeof(b_par) +
+                    sizeof(b_lpc) + sizeof(b_len) + sizeof(score) + sizeof(cmask) + sizeof(cpb) +
+                    sizeof(cpnb) + sizeof(ukey) + sizeof(sk_sel) + sizeof(sk_half) +
+                    sizeof(bl_sc) + sizeof(bl_pb) + sizeof(bl_pnb) + sizeof(sel_k) +
+                    3 * sizeof(int) + sizeof(b_km) + sizeof(rlist) + sizeof(kept) + sizeof(pch) <=
+                    BEAM_LDS_PER_CU,
+                "ctc_beam_kernel: static LDS over the budget (a CU has 160 KiB)");
 
   const int n = blockIdx.x;
   const int lane = threadIdx.x;
@@ -777,11 +861,11 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(
     BEAM_STAMP(0)
     if (stamps != nullptr && t < BEAM_NSTAMP_T && lane == 0)
       stamps[t * BEAM_NSTAMP_P + 8] = __builtin_amdgcn_s_memrealtime();
-    const int tc = t % BEAM_TCH;
-    if (tc == 0) {   // stage the next BEAM_TCH frames (all loads of a lane in flight at once)
-      const int nf = min(BEAM_TCH, size - t);
+    const int tc = t % TCH;
+    if (tc == 0) {   // stage the next TCH frames (all loads of a lane in flight at once)
+      const int nf = min(TCH, size - t);
 #pragma unroll 8
-      for (int e = lane; e < BEAM_TCH * C; e += 64) {
+      for (int e = lane; e < TCH * C; e += 64) {
         const int f = e / C;
         const int c = e - f * C;
         pch[f * CM + c] = f < nf ? pn[(int64_t)(t + f) * stride_t + c] : 0.f;
@@ -1016,10 +1100,13 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(
           const float pnb = isb ? blnp[u] : (ext ? pe : -INFINITY);
           const float sc = isb ? bls[u] : (ext ? pe : -INFINITY);
           if (cv && i < nb) {
-            cpb[k] = pb;
-            cpnb[k] = pnb;
-            ukey[k] = beam_pack(sc, ((isb ? last[u] : c) + 1) * 4096 + k);
-            if (ext && ((kmi[u] >> c) & 1ull)) rlist[atomicAdd(&s_nr, 1)] = k;   // revival attempt
+            if constexpr (!WIDE) {
+              cpb[k] = pb;
+              cpnb[k] = pnb;
+            }
+            ukey[k] = beam_pack(sc, ((isb ? last[u] : c) + 1) * KSTRIDE + k);
+            if (ext && ((kmi[u] >> c) & 1ull))
+              rlist[atomicAdd(&s_nr, 1)] = static_cast<rl_t>(k);   // revival attempt
           }
         }
       }
@@ -1047,12 +1134,32 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(
     // >= it); 0 (none) while the beam is not full or some entry has no blank candidate
     const unsigned long long lb = (nb >= beam && blmin > -INFINITY)
                                       ? (beam_pack(blmin, 0) & 0xFFFFFFFF00000000ull) : 0ull;
-    const int nsel = jd <= 2    ? beam_select<2>(ukey, tot, beam, sel_k, sk_sel, lane, lb)
-                     : jd <= 4  ? beam_select<4>(ukey, tot, beam, sel_k, sk_sel, lane, lb)
-                     : jd <= 6  ? beam_select<6>(ukey, tot, beam, sel_k, sk_sel, lane, lb)
-                     : jd <= 8  ? beam_select<8>(ukey, tot, beam, sel_k, sk_sel, lane, lb)
-                     : jd <= 16 ? beam_select<16>(ukey, tot, beam, sel_k, sk_sel, lane, lb)
-                                : beam_select<SD>(ukey, tot, beam, sel_k, sk_sel, lane, lb);
+    int nsel;
+    if constexpr (!WIDE) {
+      nsel = jd <= 2    ? beam_select<2>(ukey, tot, beam, sel_k, sk_sel, lane, lb)
+             : jd <= 4  ? beam_select<4>(ukey, tot, beam, sel_k, sk_sel, lane, lb)
+             : jd <= 6  ? beam_select<6>(ukey, tot, beam, sel_k, sk_sel, lane, lb)
+             : jd <= 8  ? beam_select<8>(ukey, tot, beam, sel_k, sk_sel, lane, lb)
+             : jd <= 16 ? beam_select<16>(ukey, tot, beam, sel_k, sk_sel, lane, lb)
+                        : beam_select<SD>(ukey, tot, beam, sel_k, sk_sel, lane, lb);
+    } else if (jd <= SD / 2) {
+      // up to 4096 candidates (100 entries x 36 labels are 3600): one selection, as above
+      nsel = jd <= 2    ? beam_select<2, KMASK>(ukey, tot, beam, sel_k, sk_sel, lane, lb)
+             : jd <= 4  ? beam_select<4, KMASK>(ukey, tot, beam, sel_k, sk_sel, lane, lb)
+             : jd <= 8  ? beam_select<8, KMASK>(ukey, tot, beam, sel_k, sk_sel, lane, lb)
+             : jd <= 16 ? beam_select<16, KMASK>(ukey, tot, beam, sel_k, sk_sel, lane, lb)
+             : jd <= 32 ? beam_select<32, KMASK>(ukey, tot, beam, sel_k, sk_sel, lane, lb)
+                        : beam_select<SD / 2, KMASK>(ukey, tot, beam, sel_k, sk_sel, lane, lb);
+    } else {
+      // more: SD keys per lane are twice the registers.  Each half of the candidates gives up
+      // its best `beam` (or just its keys >= lb when those are fewer), and the best `beam` of
+      // the two lists -- which hold the best `beam` of all -- are selected and ranked
+      constexpr int HALF = 64 * (SD / 2);
+      const int n0 = beam_select_half<SD / 2>(ukey, HALF, beam, sk_half, lane, lb);
+      const int n1 = beam_select_half<SD / 2>(ukey + HALF, tot - HALF, beam, sk_half + n0, lane, lb);
+      __syncthreads();
+      nsel = beam_select<2 * BM / 64, KMASK>(sk_half, n0 + n1, beam, sel_k, sk_sel, lane, lb);
+    }
     __syncthreads();
     BEAM_STAMP(5)
     // ---- new beam: lane r builds entries r, r + 64, ...; new prefixes get trie nodes in
@@ -1153,8 +1260,13 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(
             b_lpc[nxt][e] = lp[c];
             b_len[nxt][e] = b_len[cur][i] + 1;
           }
-          b_pb[nxt][e] = cpb[k];
-          b_pnb[nxt][e] = cpnb[k];
+          if constexpr (!WIDE) {
+            b_pb[nxt][e] = cpb[k];
+            b_pnb[nxt][e] = cpnb[k];
+          } else {
+            b_pb[nxt][e] = ext ? -INFINITY : bl_pb[i];
+            b_pnb[nxt][e] = ext ? beam_unpack_score(ukey[k]) : bl_pnb[i];
+          }
         }
         run += __popcll(em);
       }
@@ -1515,7 +1627,9 @@ static ds2_status_t beam_decode(const float* probs, int n, int t_max, int c, int
       top_paths < 1 || top_paths > beam_width || cutoff_top_n < 1)
     return DS2_INVALID_VALUE;
   const bool small = c <= BEAM_SMALL_C && beam_width <= BEAM_SMALL;
-  if (!small && (c > BEAM_LARGE_C || beam_width > BEAM_LARGE)) return DS2_UNSUPPORTED_SHAPE;
+  const bool large = !small && c <= BEAM_LARGE_C && beam_width <= BEAM_LARGE;
+  if (!small && !large && (c > BEAM_WIDE_C || beam_width > BEAM_WIDE))
+    return DS2_UNSUPPORTED_SHAPE;
   if (n == 0) return DS2_OK;
   if (ws == nullptr || ws_bytes < ds2_ctc_beam_workspace_size(n, t_max, beam_width))
     return DS2_WORKSPACE_TOO_SMALL;
@@ -1534,10 +1648,12 @@ static ds2_status_t beam_decode(const float* probs, int n, int t_max, int c, int
   if (lm != nullptr) L = *lm;
   L.stamps = g_beam_stamps;
   auto kern = lm != nullptr
-                  ? (small ? ctc_beam_kernel<BEAM_SMALL, BEAM_SMALL_C, true>
-                           : ctc_beam_kernel<BEAM_LARGE, BEAM_LARGE_C, true>)
-                  : (small ? ctc_beam_kernel<BEAM_SMALL, BEAM_SMALL_C, false>
-                           : ctc_beam_kernel<BEAM_LARGE, BEAM_LARGE_C, false>);
+                  ? (small   ? ctc_beam_kernel<BEAM_SMALL, BEAM_SMALL_C, true>
+                     : large ? ctc_beam_kernel<BEAM_LARGE, BEAM_LARGE_C, true>
+                             : ctc_beam_kernel<BEAM_WIDE, BEAM_WIDE_C, true>)
+                  : (small   ? ctc_beam_kernel<BEAM_SMALL, BEAM_SMALL_C, false>
+                     : large ? ctc_beam_kernel<BEAM_LARGE, BEAM_LARGE_C, false>
+                             : ctc_beam_kernel<BEAM_WIDE, BEAM_WIDE_C, false>);
   hipLaunchKernelGGL(kern, dim3(n), dim3(64), 0, as_stream(stream), probs, t_max, c,
                      stride_n, stride_t, sizes, blank, beam_width, cutoff_top_n, cutoff_prob,
                      top_paths, par, chr, tst, lpc, ncnt, nfc, nns, nkm, cap, out_ids, out_offsets, out_lens,

@@ -79,6 +79,10 @@ class BeamCTCDecoder(Decoder):
     the n-gram model like ctcdecode's KenLM Scorer (alpha: LM weight, beta: word bonus;
     ds2amd/lm.py builds the device tables once); without an LM ctcdecode ignores
     alpha/beta and so does this.
+
+    Limits: ``beam_width <= 128`` and ``len(labels) <= 64`` (the reference's default beam of
+    100 over its Cyrillic label set of 36 is inside them); beyond either the constructor
+    raises ``ValueError``.
     """
 
     def __init__(self, labels, lm_path=None, alpha=0, beta=0, cutoff_top_n=40, cutoff_prob=1.0,
@@ -88,12 +92,11 @@ class BeamCTCDecoder(Decoder):
         if lm_path is not None:
             from .lm import ArpaScorer
             self.scorer = ArpaScorer(lm_path, labels, alpha, beta)
-        # the device search keeps every candidate in one wave's registers:
-        # beam_width <= 128 over <= 32 labels (the reference default 100 over 29), or
-        # beam_width <= 32 over <= 64 labels
-        if beam_width > (128 if len(labels) <= 32 else 32) or len(labels) > 64:
-            raise ValueError("ds2amd.BeamCTCDecoder: beam_width <= 128 with <= 32 labels, "
-                             "or beam_width <= 32 with <= 64 labels")
+        # the device search is one wave per utterance over u64 char masks: beam_width <= 128
+        # and <= 64 labels (three kernel instances: beams <= 32, <= 32 labels, and both above)
+        if beam_width > 128 or len(labels) > 64:
+            raise ValueError("ds2amd.BeamCTCDecoder: beam_width <= 128 and at most 64 labels "
+                             f"(got beam_width={beam_width}, {len(labels)} labels)")
         self.beam_width = int(beam_width)
         self.cutoff_top_n = int(cutoff_top_n)
         self.cutoff_prob = float(cutoff_prob)

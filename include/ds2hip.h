@@ -519,8 +519,10 @@ ds2_status_t ds2_greedy_decode(const float* probs, int n, int t_max, int c, int6
  * prefixes (best first): out_ids / out_offsets [n][top_paths][t_max] (char ids and
  * the frame of each char), out_lens [n][top_paths], out_scores [n][top_paths]
  * (log prob).  cutoff_top_n / cutoff_prob prune the vocabulary per frame as
- * ctcdecode does.  beam_width <= 32 with c <= 64, or beam_width <= 128 with
- * c <= 32 (the reference default beam_width = 100 over its 29 labels).        */
+ * ctcdecode does.  beam_width <= 128 and c <= 64 (three kernel instances:
+ * beam_width <= 32 with c <= 64; beam_width <= 128 with c <= 32, the reference
+ * default beam_width = 100 over 29 labels; and 33..128 over 33..64, its Cyrillic
+ * label set of 36); anything beyond is DS2_UNSUPPORTED_SHAPE.                 */
 /* Batched CER / WER edit distances (data/utils.py:47-57 get_cer_wer, decoder.py
  * Decoder.cer / .wer) over id sequences: a = decoded ids [n][a_stride] with a_lens,
  * b = reference ids flat with b_offsets / b_lens.  out[4*i .. 4*i+3] = {word

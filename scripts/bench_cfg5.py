@@ -6,9 +6,15 @@ cutoff_top_n 40: the reference's opts.py defaults; no LM) -> host strings
 (ds2amd.transcribe.transcribe_batch on device arrays).  Greedy decoding is timed beside it.
 
 usage: python scripts/bench_cfg5.py [--batch N] [--seconds S] [--beam W] [--iters K] [--stamps]
+                                    [--labels N]
 
 --stamps: also run one beam decode with the kernel's per-phase clock stamps on (utterance 0,
 frames 1..255; ds2_test_beam_stamps) and print the mean time of each phase of a frame.
+
+--labels N: pad bench.LABELS with distinct extra characters to N labels (at most 64) and give
+the model's output layer N classes, e.g. 36 for the reference's Cyrillic label set -- beams
+above 32 over more than 32 labels take the beam search's wide kernel instance.  Default: the
+labels of bench.py.
 """
 import argparse
 import json
@@ -34,13 +40,22 @@ def main():
     ap.add_argument("--lm", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..",
                                                  "tests", "golden", "tiny_lm.arpa"),
                     help="ARPA model for the beam_lm line (default: the committed 3-gram fixture)")
+    ap.add_argument("--labels", type=int, default=None,
+                    help="number of labels (default: bench.LABELS as they are)")
     args = ap.parse_args()
+    labels = bench.LABELS
+    if args.labels is not None:
+        pad = [chr(c) for c in list(range(0x30, 0x3A)) + list(range(0x430, 0x450))
+               if chr(c) not in labels]
+        if not len(labels) <= args.labels <= min(64, len(labels) + len(pad)):
+            ap.error(f"--labels: {len(labels)}..{min(64, len(labels) + len(pad))}")
+        labels = labels + ''.join(pad[:args.labels - len(labels)])
     from ds2amd import model as dsm, ops
     from ds2amd.data_loader import SpectrogramParser
     from ds2amd.decoder import BeamCTCDecoder, GreedyDecoder
     dev = torch.device("cuda", 0)
     torch.manual_seed(123456)
-    m = dsm.DeepSpeech(rnn_type='gru', labels=bench.LABELS, rnn_hidden_size=800, nb_layers=5,
+    m = dsm.DeepSpeech(rnn_type='gru', labels=labels, rnn_hidden_size=800, nb_layers=5,
                        audio_conf=bench.CONF, bidirectional=True).to(dev).eval()
     parser = SpectrogramParser(bench.CONF, normalize='max_frame', device=dev)
     n_fft, hop, win, taps = parser._consts(16000)
@@ -49,10 +64,10 @@ def main():
     pcm = torch.rand(args.batch, n_samp, generator=g).mul_(2).sub_(1).to(dev)
     ns = torch.full((args.batch,), n_samp, dtype=torch.int32, device=dev)
     frames = 1 + n_samp // hop
-    beam = BeamCTCDecoder(bench.LABELS, beam_width=args.beam, cutoff_top_n=40)
-    beam_lm = BeamCTCDecoder(bench.LABELS, lm_path=args.lm, alpha=0.8, beta=1.0,
+    beam = BeamCTCDecoder(labels, beam_width=args.beam, cutoff_top_n=40)
+    beam_lm = BeamCTCDecoder(labels, lm_path=args.lm, alpha=0.8, beta=1.0,
                              beam_width=args.beam, cutoff_top_n=40)
-    greedy = GreedyDecoder(bench.LABELS)
+    greedy = GreedyDecoder(labels)
 
     def run(decoder):
         with torch.no_grad():
@@ -74,6 +89,8 @@ def main():
         out[f"{name}_ms_per_batch"] = round(dt * 1e3, 2)
         out[f"{name}_sample"] = strings[0][0][:40]
     out["beam_width"] = args.beam
+    if args.labels is not None:
+        out["labels"] = len(labels)
     # the decoders alone on one forward's output: device part (kernel + allocations, synced)
     # and the whole decode (+ the copy back and the strings / offsets on the host)
     with torch.no_grad():

@@ -78,6 +78,114 @@ __global__ __launch_bounds__(WAV_T) void wave_aug_kernel(
   for (int64_t i = tid; i < out_stride; i += WAV_T) y[i] = i < len ? src[i] : 0.f;
 }
 
+// ---------------------------------------------------------------------------------------
+// ds2_pcm_decode: the int16 -> float32 arithmetic of load_audio_norm (data/audio_loader.py:4-27,
+// scipy wav read + normalise by max |x| + channel selection) on the packed `data` chunks of a
+// batch of wav files, so the host uploads 2 bytes per sample and no padding.
+//   desc [n][4] int64 = {first int16 element, frames, channels, selector (-1 = mean)}
+// Phase 1 (pcm_peak_kernel): abs_max per utterance = max over every sample of every channel of
+// np.abs on int16, which wraps: |-32768| = -32768.  Kept as abs_max + 32768 in an unsigned
+// word (0 = the smallest value, what the memset leaves) under atomicMax.
+// Phase 2 (pcm_scale_kernel): iff abs_max > 0 a sample is (float)((double)s * (1.0 /
+// (double)abs_max)): numpy's `sound *= 1 / abs_max` multiplies the float32 array by a float64
+// scalar in double and rounds once.  The mean over channels is ndarray.mean(axis=1) in float32:
+// a sequential sum for 2..7 channels, numpy's 8-way pairwise tree for 8, one IEEE division.
+// Every operation is spelled with the _rn intrinsics: no contraction into an fma.
+constexpr int PCM_T = 256;
+constexpr int PCM_VEC = 8;        // int16 per 16-byte load
+constexpr int PCM_PER_THREAD = 4; // outputs per thread in phase 2
+constexpr int PCM_MAX_CH = 8;
+
+// np.abs on int16: the result is wrapped back into int16
+__device__ __forceinline__ int pcm_abs16(int s) {
+  return static_cast<int>(static_cast<int16_t>(s < 0 ? -s : s));
+}
+
+__global__ __launch_bounds__(PCM_T) void pcm_peak_kernel(const int16_t* __restrict__ pcm,
+                                                         const int64_t* __restrict__ desc, int bpu,
+                                                         unsigned* __restrict__ peak) {
+  __shared__ int red[PCM_T / kWave];
+  const int b = blockIdx.x / bpu, chunk = blockIdx.x % bpu;
+  const int tid = threadIdx.x;
+  const int64_t* d = desc + (int64_t)b * 4;
+  const int64_t total = d[1] * d[2];
+  if (total == 0) return;                      // uniform over the block
+  const int16_t* x = pcm + d[0];
+  // x is 2-byte aligned and no more (an odd sample count before it): scalar head up to the
+  // first 16-byte boundary, 16-byte loads from there, scalar tail
+  int64_t head = (int64_t)((16 - (reinterpret_cast<uintptr_t>(x) & 15)) & 15) >> 1;
+  if (head > total) head = total;
+  const int64_t nvec = (total - head) / PCM_VEC;
+  const int64_t tail0 = head + nvec * PCM_VEC;
+  int m = -32768;
+  const int4* xv = reinterpret_cast<const int4*>(x + head);
+  for (int64_t v = (int64_t)chunk * PCM_T + tid; v < nvec; v += (int64_t)bpu * PCM_T) {
+    const int4 q = xv[v];
+    const int w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      m = max(m, pcm_abs16(static_cast<int16_t>(w[j] & 0xffff)));
+      m = max(m, pcm_abs16(w[j] >> 16));       // arithmetic shift: the sign-extended high half
+    }
+  }
+  if (chunk == 0) {
+    for (int64_t i = tid; i < head; i += PCM_T) m = max(m, pcm_abs16(x[i]));
+    for (int64_t i = tail0 + tid; i < total; i += PCM_T) m = max(m, pcm_abs16(x[i]));
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) m = max(m, __shfl_xor(m, off, 64));
+  if ((tid & 63) == 0) red[tid >> 6] = m;
+  __syncthreads();
+  if (tid == 0) {
+#pragma unroll
+    for (int w = 1; w < PCM_T / kWave; ++w) m = max(m, red[w]);
+    atomicMax(peak + b, static_cast<unsigned>(m + 32768));
+  }
+}
+
+__global__ __launch_bounds__(PCM_T) void pcm_scale_kernel(const int16_t* __restrict__ pcm,
+                                                          const int64_t* __restrict__ desc,
+                                                          const unsigned* __restrict__ peak,
+                                                          float* __restrict__ out,
+                                                          int64_t out_stride, int cpr) {
+  const int b = blockIdx.x / cpr, chunk = blockIdx.x % cpr;
+  const int64_t* d = desc + (int64_t)b * 4;
+  const int64_t frames = d[1];
+  const int ch = static_cast<int>(d[2]), sel = static_cast<int>(d[3]);
+  const int16_t* x = pcm + d[0];
+  const int abs_max = static_cast<int>(peak[b]) - 32768;
+  const bool scaled = abs_max > 0;
+  const double scale = scaled ? 1.0 / (double)abs_max : 1.0;
+  float* y = out + (int64_t)b * out_stride;
+  auto val = [&](int16_t s) -> float {
+    return scaled ? __double2float_rn(__dmul_rn((double)s, scale)) : (float)s;
+  };
+#pragma unroll
+  for (int k = 0; k < PCM_PER_THREAD; ++k) {
+    const int64_t i = ((int64_t)chunk * PCM_PER_THREAD + k) * PCM_T + threadIdx.x;
+    if (i >= out_stride) break;
+    float v = 0.f;
+    if (i < frames) {
+      const int16_t* s = x + i * ch;
+      if (ch == 1) {
+        v = val(s[0]);
+      } else if (sel >= 0) {
+        v = val(s[sel]);
+      } else if (ch == PCM_MAX_CH) {
+        // numpy's pairwise sum over 8 contiguous values
+        v = __fadd_rn(__fadd_rn(__fadd_rn(val(s[0]), val(s[1])), __fadd_rn(val(s[2]), val(s[3]))),
+                      __fadd_rn(__fadd_rn(val(s[4]), val(s[5])), __fadd_rn(val(s[6]), val(s[7]))));
+        v = __fdiv_rn(v, (float)ch);
+      } else {
+        v = val(s[0]);
+        for (int c = 1; c < ch; ++c) v = __fadd_rn(v, val(s[c]));
+        v = __fdiv_rn(v, (float)ch);
+      }
+    }
+    y[i] = v;
+  }
+}
+
 }  // namespace ds2
 
 using namespace ds2;
@@ -103,6 +211,52 @@ ds2_status_t ds2_wave_aug(const float* in, int64_t in_stride, const int* in_lens
                      in_lens, op_i, op_f, max_ops, noise, noise_stride, static_cast<float*>(ws),
                      cap, out, out_stride, out_lens, err);
   return launch_status("ds2_wave_aug");
+}
+
+size_t ds2_pcm_decode_workspace_size(int n) {
+  return n > 0 ? (size_t)n * sizeof(unsigned) + 256 : 256;
+}
+
+ds2_status_t ds2_pcm_decode(const int16_t* pcm, int64_t pcm_elems, const int64_t* desc_host,
+                            const int64_t* desc, int n, float* out, int64_t out_stride, void* ws,
+                            size_t ws_bytes, ds2_stream_t stream) {
+  if (n < 0 || pcm_elems < 0 || out_stride < 0) return DS2_INVALID_VALUE;
+  if (n == 0) return DS2_OK;
+  if (desc_host == nullptr || desc == nullptr || out == nullptr) return DS2_INVALID_VALUE;
+  if (n > (1 << 20)) return DS2_UNSUPPORTED_SHAPE;
+  int64_t max_total = 0;
+  for (int b = 0; b < n; ++b) {
+    const int64_t off = desc_host[4 * b], frames = desc_host[4 * b + 1];
+    const int64_t ch = desc_host[4 * b + 2], sel = desc_host[4 * b + 3];
+    if (off < 0 || frames < 0 || ch < 1 || ch > PCM_MAX_CH || sel < -1 || sel >= ch)
+      return DS2_INVALID_VALUE;
+    if (frames > out_stride || off > pcm_elems || frames > (pcm_elems - off) / ch)
+      return DS2_INVALID_VALUE;
+    max_total = frames * ch > max_total ? frames * ch : max_total;
+  }
+  if (max_total > 0 && (pcm == nullptr || (reinterpret_cast<uintptr_t>(pcm) & 1)))
+    return DS2_INVALID_VALUE;
+  if (ws == nullptr || ws_bytes < ds2_pcm_decode_workspace_size(n)) return DS2_WORKSPACE_TOO_SMALL;
+  if (out_stride == 0) return DS2_OK;
+  const int64_t cpr64 = (out_stride + PCM_T * PCM_PER_THREAD - 1) / (PCM_T * PCM_PER_THREAD);
+  if (cpr64 * n > 0x7fffffffLL) return DS2_UNSUPPORTED_SHAPE;
+  hipStream_t st = as_stream(stream);
+  unsigned* peak = static_cast<unsigned*>(ws);
+  hipError_t e = hipMemsetAsync(peak, 0, (size_t)n * sizeof(unsigned), st);
+  if (e != hipSuccess) {
+    set_last_error("ds2_pcm_decode", e);
+    return DS2_HIP_ERROR;
+  }
+  if (max_total > 0) {
+    // several blocks per utterance: 8192 samples per block and pass, at most 64 blocks
+    int bpu = cdiv(max_total, (int64_t)PCM_T * PCM_VEC * 4);
+    bpu = bpu < 1 ? 1 : (bpu > 64 ? 64 : bpu);
+    hipLaunchKernelGGL(pcm_peak_kernel, dim3((unsigned)n * bpu), dim3(PCM_T), 0, st, pcm, desc,
+                       bpu, peak);
+  }
+  hipLaunchKernelGGL(pcm_scale_kernel, dim3((unsigned)(cpr64 * n)), dim3(PCM_T), 0, st, pcm, desc,
+                     peak, out, out_stride, (int)cpr64);
+  return launch_status("ds2_pcm_decode");
 }
 
 }  // extern "C"

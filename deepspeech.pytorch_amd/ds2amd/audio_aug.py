@@ -22,6 +22,7 @@ device PCM buffer the STFT kernel reads.
 """
 from __future__ import annotations
 
+import os
 import random
 from typing import List, Optional, Sequence
 
@@ -34,6 +35,24 @@ SHIFT, DISTORT, NOISE = 1, 2, 3          # replayed by ds2_wave_aug
 STRETCH, PITCH, RESAMPLE = 4, 5, 6       # ds2_time_stretch / ds2_resample (before the above)
 HEAVY = (STRETCH, PITCH, RESAMPLE)
 MAX_DURATION_AUG = 10          # seconds (data_loader_aug.py:49)
+MAX_RAW_CHANNELS = 8           # ds2_pcm_decode's limit (its mean follows numpy's up to 8)
+
+
+def _norm_host(sound, channel):
+    """The arithmetic of data_loader.load_audio_norm past the wav read (ref
+    data/audio_loader.py:6-27), for Wave.samples of a raw Wave."""
+    abs_max = np.abs(sound).max()
+    sound = sound.astype('float32')
+    if abs_max > 0:
+        sound *= 1 / abs_max
+    if len(sound.shape) > 1:
+        if sound.shape[1] == 1:
+            sound = sound.squeeze()
+        elif channel == -1:
+            sound = sound.mean(axis=1)
+        else:
+            sound = sound[:, channel]
+    return sound
 
 
 class Wave(object):
@@ -42,9 +61,51 @@ class Wave(object):
     reference's array would have, so the transforms' length checks read the same."""
 
     def __init__(self, samples):
-        self.samples = np.ascontiguousarray(np.asarray(samples, dtype=np.float32).reshape(-1))
-        self.length = int(self.samples.shape[0])
+        self._samples = np.ascontiguousarray(np.asarray(samples, dtype=np.float32).reshape(-1))
+        self.raw = None
+        self.channel = -1
+        self.n_in = int(self._samples.shape[0])     # samples as loaded, before any record
+        self.length = self.n_in
         self.records = []      # (kind, a, b, alpha, noise float64 slice or None)
+
+    @classmethod
+    def from_raw(cls, raw, channel=-1):
+        """The raw form: the int16 samples of a wav file as scipy reads them, [frames] or
+        [frames, channels] with at most MAX_RAW_CHANNELS channels, and the channel selector
+        of load_audio_norm (-1 = mean).  Nothing is converted on the host: the transforms
+        read only ``length``, and the batch is decoded on the device (ds2_pcm_decode);
+        ``samples`` computes the float form on first use."""
+        raw = np.asarray(raw)
+        if raw.dtype != np.int16 or raw.ndim not in (1, 2):
+            raise ValueError(f"Wave.from_raw: int16 [frames] or [frames, channels], got "
+                             f"{raw.dtype} {raw.shape}")
+        ch = 1 if raw.ndim == 1 else int(raw.shape[1])
+        if not 1 <= ch <= MAX_RAW_CHANNELS:
+            raise ValueError(f"Wave.from_raw: {ch} channels (1..{MAX_RAW_CHANNELS})")
+        if ch > 1 and channel != -1 and not -ch <= channel < ch:
+            raise IndexError(f"index {channel} is out of bounds for axis 1 with size {ch}")
+        w = cls.__new__(cls)
+        w._samples = None
+        w.raw = np.ascontiguousarray(raw)
+        # a mono file ignores the selector (load_audio_norm squeezes it)
+        w.channel = -1 if ch == 1 or channel == -1 else int(channel) % ch
+        w.n_in = int(raw.shape[0])
+        w.length = w.n_in
+        w.records = []
+        return w
+
+    @property
+    def samples(self):
+        if self._samples is None:
+            self._samples = np.ascontiguousarray(
+                _norm_host(self.raw, self.channel).reshape(-1))
+        return self._samples
+
+    @samples.setter
+    def samples(self, value):
+        self._samples = value
+        self.raw = None
+        self.n_in = int(value.shape[0])
 
     @property
     def shape(self):
@@ -244,6 +305,78 @@ def heavy_length(kind, a, b, alpha, length):
     return length
 
 
+class _Staging(object):
+    """Pinned host buffers for the packed int16 upload.  A buffer is handed out again only
+    once the event recorded behind its copy has completed; until then another one is made."""
+
+    def __init__(self):
+        self._bufs = []        # [pinned uint8 tensor, event or None]
+
+    def take(self, nbytes):
+        for slot in self._bufs:
+            buf, ev = slot
+            if buf.numel() >= nbytes and (ev is None or ev.query()):
+                slot[1] = None
+                return slot
+        cap = 1 << max(16, int(nbytes - 1).bit_length())
+        slot = [torch.empty(cap, dtype=torch.uint8).pin_memory(), None]
+        self._bufs.append(slot)
+        return slot
+
+    @staticmethod
+    def release(slot):
+        ev = torch.cuda.Event()
+        ev.record()
+        slot[1] = ev
+
+
+_STAGING = _Staging()
+
+
+def pcm_decode_enabled() -> bool:
+    """DS2_PCM_DECODE=0 keeps the host float conversion and the padded fp32 upload."""
+    return os.environ.get("DS2_PCM_DECODE", "1") != "0"
+
+
+def pack_raw(waves: Sequence[Wave], buf: np.ndarray = None):
+    """The upload image of a batch of raw Waves: [desc int64 [n][4]] [pad to 16 B] [the int16
+    samples back to back], desc = ds2_pcm_decode's {first element, frames, channels,
+    selector}.  -> (desc, header bytes, total bytes), written into ``buf`` (uint8) if given."""
+    n = len(waves)
+    desc = np.zeros((n, 4), dtype=np.int64)
+    off = 0
+    for b, w in enumerate(waves):
+        ch = 1 if w.raw.ndim == 1 else w.raw.shape[1]
+        desc[b] = (off, w.raw.shape[0], ch, w.channel)
+        off += w.raw.size
+    hdr = (n * 32 + 15) // 16 * 16
+    total = hdr + 2 * off
+    if buf is not None:
+        buf[:n * 32].view(np.int64)[:] = desc.reshape(-1)
+        pcm = buf[hdr:total].view(np.int16)
+        for b, w in enumerate(waves):
+            pcm[desc[b, 0]:desc[b, 0] + w.raw.size] = w.raw.reshape(-1)
+    return desc, hdr, total
+
+
+def upload_raw(waves: Sequence[Wave], out_stride: int, device):
+    """[N, out_stride] fp32 device matrix of a batch whose every utterance is raw: one pinned
+    staging buffer, one non-blocking copy of 2 bytes per sample, ds2_pcm_decode.  None when
+    an utterance holds float samples or DS2_PCM_DECODE=0: the caller's host path."""
+    if not (pcm_decode_enabled() and waves
+            and all(isinstance(w, Wave) and w.raw is not None for w in waves)):
+        return None
+    _, _, total = pack_raw(waves)
+    slot = _STAGING.take(total)
+    desc, hdr, total = pack_raw(waves, slot[0].numpy())
+    dev = torch.empty(total, dtype=torch.uint8, device=device)
+    dev.copy_(slot[0][:total], non_blocking=True)
+    _STAGING.release(slot)
+    n = len(waves)
+    return ops.pcm_decode(dev[hdr:].view(torch.int16), desc, out_stride,
+                          desc_dev=dev[:n * 32].view(torch.int64))
+
+
 def apply_waves(waves: Sequence[Wave], device) -> tuple:
     """Replay the records of a batch on the device: -> (pcm [N, S_max] fp32 device,
     lengths list).  The librosa effects (resample, time stretch, pitch shift) lead an
@@ -262,12 +395,14 @@ def apply_waves(waves: Sequence[Wave], device) -> tuple:
                                       "transform (the reference's pipelines never do this)")
         heavy.append(w.records[:k])
         light.append(w.records[k:])
-    s_in = max(w.samples.shape[0] for w in waves)
-    pcm = np.zeros((n, max(s_in, 1)), dtype=np.float32)
-    for b, w in enumerate(waves):
-        pcm[b, :w.samples.shape[0]] = w.samples
-    pcm_d = torch.from_numpy(pcm).to(device)
-    base = [w.samples.shape[0] for w in waves]
+    s_in = max(w.n_in for w in waves)
+    pcm_d = upload_raw(waves, max(s_in, 1), device)
+    if pcm_d is None:
+        pcm = np.zeros((n, max(s_in, 1)), dtype=np.float32)
+        for b, w in enumerate(waves):
+            pcm[b, :w.samples.shape[0]] = w.samples
+        pcm_d = torch.from_numpy(pcm).to(device)
+    base = [w.n_in for w in waves]
     for h in range(max((len(r) for r in heavy), default=0)):
         outs = {}
         for kind in HEAVY:

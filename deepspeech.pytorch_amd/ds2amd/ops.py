@@ -725,6 +725,37 @@ def wave_aug(pcm: torch.Tensor, in_lens: torch.Tensor, op_i: torch.Tensor, op_f:
     return out
 
 
+def pcm_decode(packed: torch.Tensor, desc, out_stride: int,
+               desc_dev: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """load_audio_norm's int16 -> float32, peak normalisation and channel selection for a
+    batch, on the device (ds2_pcm_decode).  packed: int16 device tensor, the interleaved
+    samples of N wav files back to back; desc: host int64 [N, 4] rows {first element, frames,
+    channels, selector (-1 = mean)}; desc_dev: the same words already on the device (uploaded
+    here when None); out: where to write (allocated when None; need not be zeroed).
+    -> [N, out_stride] fp32, zero past each row's frames."""
+    packed = _need(packed, "pcm_decode.packed", torch.int16)
+    desc = np.ascontiguousarray(np.asarray(desc, dtype=np.int64).reshape(-1, 4))
+    n = int(desc.shape[0])
+    dev = packed.device
+    if desc_dev is None:
+        desc_dev = torch.from_numpy(desc).to(dev)
+    desc_dev = _need(desc_dev, "pcm_decode.desc_dev", torch.int64)
+    if desc_dev.numel() != desc.size:
+        raise _lib.Ds2Error("pcm_decode: desc_dev does not have desc's shape")
+    if out is None:
+        out = torch.empty(n, max(int(out_stride), 0), device=dev, dtype=_F32)
+    elif (not out.is_cuda or out.dtype != _F32 or not out.is_contiguous()
+          or out.numel() < n * max(int(out_stride), 0)):
+        raise _lib.Ds2Error("pcm_decode: out must be a contiguous fp32 device tensor of "
+                            "N * out_stride elements")
+    ws = _ws(_lib.size("ds2_pcm_decode_workspace_size", n), dev)
+    _lib.call("ds2_pcm_decode", packed.data_ptr(), packed.numel(), desc.ctypes.data,
+              desc_dev.data_ptr(), n, out.data_ptr(), int(out_stride), ws.data_ptr(), ws.numel(),
+              _stream())
+    return out
+
+
 # librosa / resampy effects (csrc/effects.hip): ChangeAudioSpeed, PitchShift, resampling
 FX_N_FFT, FX_HOP = 2048, 512
 

@@ -320,6 +320,66 @@ class Trainer:
             return v
         return loss.detach()
 
+    # ---- validation -------------------------------------------------------------------
+    def evaluate(self, loader, decoder=None):
+        """check_model_quality (ref train.py:333-400) over ``loader``'s collate tuples, on
+        the device: eval-mode forward without grad, CTC loss / N (costs only, no gradient
+        buffer), +-inf read as 1000, the reference's running ``val_loss_sum`` lines, greedy
+        decode (or the best beam of ``decoder``, a BeamCTCDecoder) and the WER / CER sums
+        of get_cer_wer through ds2_edit_distance.  -> dict(val_loss, wer, cer, num_words,
+        num_chars), wer and cer in per cent.  The model's mode is restored; no plotting, no
+        curriculum update."""
+        was_training = self.model.training
+        self.model.eval()
+        acc = torch.zeros(4, dtype=torch.float64, device=self.device)
+        val_loss_sum, num_losses = 0.0, 0
+        try:
+            with torch.no_grad():
+                for data in loader:
+                    inputs, targets, _, input_percentages, target_sizes = data
+                    input_sizes = input_percentages.mul_(int(inputs.size(3))).int()  # :339 quirk
+                    inputs = inputs.to(self.device, non_blocking=True)
+                    self.sync.before_forward()
+                    logits, probs, output_sizes = self.model(inputs, input_sizes)
+                    tg_d = targets.to(self.device, torch.int32)
+                    ts_h = target_sizes.cpu().int()
+                    ts_d = ts_h.to(self.device)
+                    costs, _ = ops.ctc_loss_raw(
+                        logits.transpose(0, 1).contiguous(), tg_d,
+                        output_sizes.to(self.device, torch.int32), ts_d,
+                        int(ts_h.max()) if ts_h.numel() else 0, want_grad=False)
+                    loss = costs.sum() / inputs.size(0)
+                    if dist.is_initialized():
+                        loss = reduce_tensor(loss, self.world)
+                    loss_value = float(loss.item())
+                    if loss_value in (float('inf'), float('-inf')):
+                        self.warnings["inf_loss"] += 1
+                        if self.verbose:
+                            print("WARNING: received an inf loss, setting loss value to 1000")
+                        loss_value = 1000.0
+                    val_loss_sum = val_loss_sum * 0.998 + loss_value * 0.002     # :363
+                    val_loss_sum += loss_value
+                    num_losses += 1
+                    if decoder is None:
+                        ids, _, counts = self.decoder.decode_ids(probs, output_sizes)
+                        space = self.decoder.space_index
+                    else:
+                        ids, _, lens, _ = decoder.decode_raw(probs, output_sizes)
+                        ids, counts = ids[:, 0].contiguous(), lens[:, 0].clamp(min=0).contiguous()
+                        space = decoder.space_index
+                    d, err = ops.edit_distance_raw(ids, counts, tg_d, ts_d, space)
+                    if int(err.item()) != 0:
+                        raise _lib.Ds2Error("evaluate: a transcript beyond ds2_edit_distance's "
+                                            "2048 ids / 1024 words")
+                    acc += d.sum(0, dtype=torch.float64)
+        finally:
+            self.model.train(was_training)
+        wer_sum, cer_sum, num_words, num_chars = (float(v) for v in acc.tolist())
+        return dict(val_loss=val_loss_sum / num_losses if num_losses else float('nan'),
+                    wer=100 * wer_sum / num_words if num_words else float('nan'),
+                    cer=100 * cer_sum / num_chars if num_chars else float('nan'),
+                    num_words=num_words, num_chars=num_chars)
+
     def _score(self, ids, counts, targets, target_sizes):
         """get_cer_wer over the batch (train.py:575-587) on the device: ds2_edit_distance
         on the compact greedy ids vs the flat targets."""

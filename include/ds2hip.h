@@ -111,6 +111,24 @@ ds2_status_t ds2_resample(const float* x, int64_t x_stride, const int* in_lens, 
                           const double* ratio, const int* n_valid, const double* win, int nwin,
                           int num_table, float* out, int64_t out_stride, void* ws,
                           size_t ws_bytes, ds2_stream_t stream);
+/* load_audio (ref data/audio_loader.py:4-27, called at data_loader_aug.py:664,681): the
+ * int16 -> float32 conversion, the division by max |x| and the channel selection of a batch of
+ * wav files, from their raw samples.  pcm: pcm_elems int16 (2-byte aligned), the interleaved
+ * `data` chunks of n files back to back.  desc [n][4] int64 = {first int16 element, frames,
+ * channels (1..8), selector (-1 = mean over channels, else a channel index)}, given twice: desc_host
+ * in host memory, validated here before any HIP call (the one host read of this header), and
+ * desc, the same words in device memory, which the kernels read.  out [n][out_stride] fp32: row
+ * b = the mono signal in [0, frames_b), zeros up to out_stride, all written here.  Bit for bit
+ * numpy's arithmetic: abs_max = max of np.abs over every channel in int16 (|-32768| wraps to
+ * -32768); iff abs_max > 0 a sample is (float)((double)s * (1.0 / (double)abs_max)); the mean is
+ * the float32 ndarray.mean(axis=1) (sequential sum, 8-way pairwise at 8 channels, one division).
+ * n == 0: DS2_OK, nothing launched; frames == 0: a row of zeros; negative sizes, channels
+ * outside 1..8, a selector outside [-1, channels), out_stride < max frames, samples past
+ * pcm_elems and NULL pointers: DS2_INVALID_VALUE.  Two launches on `stream`, no sync.       */
+size_t ds2_pcm_decode_workspace_size(int n);
+ds2_status_t ds2_pcm_decode(const int16_t* pcm, int64_t pcm_elems, const int64_t* desc_host,
+                            const int64_t* desc, int n, float* out, int64_t out_stride, void* ws,
+                            size_t ws_bytes, ds2_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* Dense fp32 GEMM on MFMA (v_mfma_f32_16x16x4_f32 / 32x32x2_f32), strided-batched, row-major.

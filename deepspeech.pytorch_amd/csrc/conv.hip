@@ -1,28 +1,29 @@
-// Conv2d (NCHW, fp32) as implicit GEMM on v_mfma_f32_32x32x2_f32.
-// ref model.py:208-215: conv1 W[32,1,41,11] s(2,2) p(20,5); conv2 W[32,32,21,11]
-// s(2,1) p(10,5); MaskConv (model.py:63-79) zeroes output columns w >= len.
+// Conv2d (NCHW, fp32): the extern "C" entry points and the fp32 kernel families, all on
+// v_mfma_f32_32x32x2_f32.  ref model.py:208-215: conv1 W[32,1,41,11] s(2,2) p(20,5); conv2
+// W[32,32,21,11] s(2,1) p(10,5); MaskConv (model.py:63-79) zeroes output columns w >= len.
 //
-//   fwd  : Y[co][p]  = sum_k W[co][k] * X[k][p]          p = (n, ho, wo) tile of one output row
-//   dgrad: DX[ci][q] = sum_k W'[ci][k] * DY[k][q]         q = (n, hi, wi) tile of one input row,
-//          k = (co, kh, kw) restricted to the kh of matching stride parity
-//   wgrad: DW[co][k] = sum_p DY[co][p] * X[k][p]          split over samples, slab reduce
-//
-// All three stage a [16][32] A tile and a [16][256 or 128] B tile k-major in LDS
-// (conflict-free fragment reads), double-buffered through registers: the
-// gathers of K-step i+1 are in flight while the MFMAs of step i run.
-#include "common.h"
-
-#include <cstdlib>
+// An entry point makes the dims, takes the direction's plan (conv_host.h), checks the caller's
+// workspace against it and switches on the plan's rung.  The bf16x6 / fp16x3 rungs launch from
+// conv_split.hip; here are
+//   * the implicit GEMM, which takes every shape, with the slab reduction and the bias
+//     gradient of every wgrad rung:
+//       fwd  : Y[co][p]  = sum_k W[co][k] * X[k][p]        p = (n, ho, wo) tile of one output row
+//       dgrad: DX[ci][q] = sum_k W'[ci][k] * DY[k][q]       q = (n, hi, wi) tile of one input row,
+//              k = (co, kh, kw) restricted to the kh of matching stride parity
+//       wgrad: DW[co][k] = sum_p DY[co][p] * X[k][p]        split over samples, slab reduce
+//     All three stage a [16][32] A tile and a [16][256 or 128] B tile k-major in LDS
+//     (conflict-free fragment reads), double-buffered through registers: the gathers of
+//     K-step i+1 are in flight while the MFMAs of step i run;
+//   * the LDS-patch direct convolution (conv_patch_kernel), the LDS-tile weight gradient
+//     (conv_wgrad_patch_kernel: conv1's) and the one-input-channel forward
+//     (conv1_patch_fwd_kernel: conv1's).
+#include "conv_host.h"
 
 namespace ds2 {
 
 constexpr int CBK = 16;       // K per stage
 constexpr int CBN = 256;      // positions per workgroup (fwd / dgrad)
 constexpr int CBNW = 128;     // k-columns per workgroup (wgrad)
-
-struct ConvDims {
-  int n, ci, hi, wi, co, kh, kw, sh, sw, ph, pw, ho, wo;
-};
 
 // ---------------------------------------------------------------------------
 // forward. grid (ceil(Wo/256), Ho, N * ceil(Co/32)); block 256 (4 waves, each
@@ -380,20 +381,6 @@ __global__ __launch_bounds__(BG_T) void bias_grad_kernel(const float* __restrict
   }
 }
 
-// XCD-aware decode of a 3-D grid launched as gx*gy*gz 1-D blocks: the blocks one XCD
-// is dealt (ids congruent mod 8) get a contiguous run of (x fastest, y, z) tiles, so
-// tiles that share input rows / samples share that XCD's L2.  Speed only.
-__device__ __forceinline__ void xcd_tile(int gx, int gy, int& bx, int& by, int& bz) {
-  const int nwg = gridDim.x;
-  const int o = blockIdx.x;
-  const int q = nwg >> 3, r = nwg & 7;
-  const int xcd = o & 7;
-  const int id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (o >> 3);
-  bx = id % gx;
-  by = (id / gx) % gy;
-  bz = id / (gx * gy);
-}
-
 // ---------------------------------------------------------------------------
 // Direct convolution from an LDS input patch (width stride 1): forward and dgrad.
 //
@@ -413,12 +400,6 @@ __device__ __forceinline__ void xcd_tile(int gx, int gy, int& bx, int& by, int& 
 //          (hi + ph) % sh == q; loop over co, taps = the kh of that class
 //          (reversed) x the kw (reversed), input = dy row
 //          (hi + ph - kh) / sh, col = wi + pw - kw
-constexpr int PT_ROWS = 4;          // output rows per workgroup (one per wave)
-constexpr int PT_COLS = 128;        // output columns per workgroup
-constexpr int PT_PITCH = 144;       // patch row pitch (>= PT_COLS + kw - 1)
-constexpr int PT_PROWS = 28;        // max patch rows incl. one zero row
-constexpr int PT_TMAX = 232;        // max taps (padded to even)
-constexpr int PT_WP = 33;           // tap-row pitch of the weight tile (conflict-free)
 constexpr int PT_PREG = (PT_PROWS * (PT_PITCH - 6) + 255) / 256;
 constexpr int PT_WREG4 = (PT_TMAX * PT_WP / 4 + 255) / 256;
 
@@ -435,20 +416,6 @@ struct PatchGeom {
   int r_step;     // output-row step between waves (1 fwd, sh dgrad)
 };
 
-__host__ __device__ inline int class_taps(const ConvDims& g, int q) {
-  return q < g.kh ? (g.kh - 1 - q) / g.sh + 1 : 0;
-}
-
-// weight-image geometry shared by host and device: tap rows padded to even, 33-float rows,
-// tiles padded to 16 bytes
-__host__ __device__ inline int wimg_tstride(const ConvDims& g, bool dgrad) {
-  const int a = dgrad ? class_taps(g, 0) : g.kh;   // class 0 has the most taps
-  return ((a * g.kw) + 1) & ~1;
-}
-__host__ __device__ inline int64_t wimg_tile(int tstride) {
-  return ((int64_t)tstride * PT_WP + 3) & ~(int64_t)3;
-}
-
 template <bool DGRAD>
 __device__ __forceinline__ PatchGeom patch_geom(const ConvDims& g, int ty, int wo0) {
   PatchGeom p;
@@ -464,8 +431,7 @@ __device__ __forceinline__ PatchGeom patch_geom(const ConvDims& g, int ty, int w
     // decode (class q, tile) from ty: classes in order, ceil(count_q / PT_ROWS) tiles each
     int q = 0, t = ty, hq = 0;
     for (q = 0; q < g.sh; ++q) {
-      hq = ((q - g.ph) % g.sh + g.sh) % g.sh;
-      const int cnt = hq < g.hi ? (g.hi - 1 - hq) / g.sh + 1 : 0;
+      const int cnt = class_rows(g, q, &hq);
       const int tiles = (cnt + PT_ROWS - 1) / PT_ROWS;
       if (t < tiles) break;
       t -= tiles;
@@ -525,13 +491,6 @@ __global__ void conv_wimg_kernel(const float* __restrict__ w, ConvDims g, int ts
     img[i] = v;
   }
 }
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t conv_rsrc(const float* p, int64_t elems) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p), (short)0,
-                                           static_cast<int>(elems * 4), 0x00020000);
-}
-
-typedef unsigned int cu32x4 __attribute__((ext_vector_type(4)));
 
 template <bool DGRAD>
 __global__ __launch_bounds__(256) void conv_patch_kernel(const float* __restrict__ in,
@@ -707,8 +666,6 @@ __global__ __launch_bounds__(256) void conv_patch_kernel(const float* __restrict
 // those positions touch are staged once in LDS; a lane's tap is fixed, so every
 // B read is the lane's tap offset plus the position offset.  Partials per
 // (n, band) are reduced in a fixed order by wgrad_reduce_kernel (deterministic).
-constexpr int WG_RW = 2;            // output rows per chunk
-constexpr int WG_CW = 128;          // output columns per chunk
 constexpr int WG_DYP = 33;          // dy tile row pitch
 
 template <int NT, int XS, int SW>
@@ -871,11 +828,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_patch_kernel(const float* __re
 // MFMAs.  The implicit-GEMM conv_fwd_kernel gathered every tap of every position from global
 // memory instead (16 scattered loads + index arithmetic per thread per 16 taps).
 // Wave w: output row w >> 1, columns (w & 1) * 64 + [0, 64) as two 32-column tiles.
-constexpr int C1_RW = 4;
-constexpr int C1_WC = 128;
-constexpr int C1_T = 512;
-constexpr int C1_PATCH = 12560;      // floats: ((C1_RW - 1) sh + kh) x ((C1_WC - 1) sw + kw2)
-constexpr int C1_KROWS = 492;        // filter-bank rows kh x kw2 (conv1: 41 x 12)
 constexpr int C1_PREG = (C1_PATCH + C1_T - 1) / C1_T;
 constexpr int C1_WREG = (32 * C1_KROWS + C1_T - 1) / C1_T;
 static_assert(2 * C1_PATCH * 4 + C1_KROWS * 32 * 4 <= 160 * 1024, "conv1 patch kernel LDS");
@@ -1027,1684 +979,6 @@ __global__ __launch_bounds__(C1_T, 1) void conv1_patch_fwd_kernel(
   }
 }
 
-// ---------------------------------------------------------------------------
-// bf16x6 direct convolution, forward (width stride 1 or 2) and dgrad (width stride 1), on the
-// bf16 matrix cores at
-// fp32 accuracy: every fp32 operand value is split into hi / mid / lo bf16 terms and a
-// product is formed from the six terms that carry fp32 weight (gemm.hip sxgemm_kernel), on
-// v_mfma_f32_32x32x16_bf16: M = 32 output channels, N = 32 output columns, K = 16 taps.
-//
-// K order: tap rows a in runs of 8 (a-group g) x kernel columns b in pairs (p): lane half
-// h of the MFMA takes b = 2p + h and a = 8g .. 8g + 7, so its 8 k values are 8 consecutive
-// input ROWS of one input column -- contiguous in a column-major LDS patch (16-B aligned,
-// one ds_read_b128 per plane), and 8 consecutive a of one (m, b) in the weight image.
-// Taps past the kernel (a >= rows of taps, b >= kw) have zero weight.  More than 24 tap rows
-// (conv1's 41) run as chunks of 16 rows, each staged like a loop channel of its own (RC
-// chunks per channel); width stride 2 reads patch column 2 (output column) + b.
-//   fwd  : out y[n][co][ho][wo], loop channels ci, input row ho*sh - ph + a, col wo - pw + b
-//   dgrad: out dx[n][ci][hi][wi] for hi of stride class q, loop channels co, taps of the
-//          class reversed (dy row (hi + ph - q)/sh - (A_q - 1) + a, col wi + pw - kw + 1 + b)
-// Workgroup: one output row x 256 columns x 32 output channels; 8 waves = 4 column
-// quarters (64 columns, 2 MFMA tiles) x 2 halves of the k-steps, whose partial sums meet in
-// LDS once at the end.  Per loop channel the input patch (KA rows x 256 + 2 NBP - 1
-// columns) is split and stored column-major (pitch P = 8 x odd bf16: conflict-free
-// fragment reads) and the channel's pre-split weight image [3][32][COP] is copied in; the
-// next channel's global loads fly during the MFMAs.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef cu32x4 u32x4;
-typedef __bf16 cbf16x2 __attribute__((ext_vector_type(2)));
-typedef float cf32x2 __attribute__((ext_vector_type(2)));
-
-// two fp32 -> (hi, mid, lo) bf16 pairs: one v_cvt_pk_bf16_f32 (RNE) per term pair, the
-// residuals exact in fp32 (bit-identical to per-element casts, half the instructions)
-__device__ __forceinline__ void cx_split2(float x0, float x1, unsigned& h, unsigned& m,
-                                          unsigned& l) {
-  h = __builtin_bit_cast(unsigned, __builtin_convertvector(cf32x2{x0, x1}, cbf16x2));
-  const float r0 = x0 - __builtin_bit_cast(float, h << 16);
-  const float r1 = x1 - __builtin_bit_cast(float, h & 0xffff0000u);
-  m = __builtin_bit_cast(unsigned, __builtin_convertvector(cf32x2{r0, r1}, cbf16x2));
-  const float q0 = r0 - __builtin_bit_cast(float, m << 16);
-  const float q1 = r1 - __builtin_bit_cast(float, m & 0xffff0000u);
-  l = __builtin_bit_cast(unsigned, __builtin_convertvector(cf32x2{q0, q1}, cbf16x2));
-}
-
-// 8 fp32 -> hi / mid / lo rows of 16 B at s + at, + plane, + 2 plane
-__device__ __forceinline__ void cx_split_store8(unsigned short* __restrict__ s, int plane, int at,
-                                                const float* v) {
-  u32x4 h, m, l;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    unsigned a, b, c;
-    cx_split2(v[2 * e], v[2 * e + 1], a, b, c);
-    h[e] = a;
-    m[e] = b;
-    l[e] = c;
-  }
-  *reinterpret_cast<u32x4*>(s + at) = h;
-  *reinterpret_cast<u32x4*>(s + plane + at) = m;
-  *reinterpret_cast<u32x4*>(s + 2 * plane + at) = l;
-}
-
-// fp16x3: 8 fp32 values times the power of two sc -> fp16 hi / lo rows of 16 B
-// at s + at, + plane (RNE casts; the residual is exact in fp32)
-typedef _Float16 cf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 cf16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void cx_split_store8h(unsigned short* __restrict__ s, int plane, int at,
-                                                 const float* v, float sc) {
-  u32x4 h, l;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const cf32x2 x = cf32x2{v[2 * e], v[2 * e + 1]} * sc;
-    const cf16x2 hh = __builtin_convertvector(x, cf16x2);
-    const cf16x2 ll = __builtin_convertvector(x - __builtin_convertvector(hh, cf32x2), cf16x2);
-    h[e] = __builtin_bit_cast(unsigned, hh);
-    l[e] = __builtin_bit_cast(unsigned, ll);
-  }
-  *reinterpret_cast<u32x4*>(s + at) = h;
-  *reinterpret_cast<u32x4*>(s + plane + at) = l;
-}
-
-// NPL 3: bf16 hi / mid / lo planes; NPL 2: fp16 hi / lo planes of v sc
-template <int NPL>
-__device__ __forceinline__ void cx_store8(unsigned short* __restrict__ s, int plane, int at,
-                                          const float* v, float sc) {
-  if constexpr (NPL == 2) cx_split_store8h(s, plane, at, v, sc);
-  else cx_split_store8(s, plane, at, v);
-}
-
-// acc += a.b over one 32 x 32 x 16 fragment pair: bf16x6 (6 products, small terms first) or
-// fp16x3 (lo.hi + hi.lo + hi.hi)
-template <int NPL>
-__device__ __forceinline__ f32x16 cx_mma(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x16 c) {
-  if constexpr (NPL == 2) {
-    typedef cf16x8 H;
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(H, a[1]), __builtin_bit_cast(H, b[0]), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(H, a[0]), __builtin_bit_cast(H, b[1]), c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(H, a[0]), __builtin_bit_cast(H, b[0]), c, 0, 0, 0);
-  } else {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
-  }
-}
-
-// acc += a.b, fp16x3 with the small products in their own chain: big += hi.hi, small +=
-// lo.hi + hi.lo.  The matrix cores floor (truncate toward -inf) each addend's bits below
-// ~2^-31 of the largest operand of the instruction, C included (scripts/mfma_rounding.hip,
-// profiles/r5n_mfma_rounding.txt).  Chained with hi.hi and a large C, every lo.hi product
-// lost its low bits to that floor: a small NEGATIVE bias per product that sums of the outputs
-// (the conv block's BatchNorm parameter gradients: 1.3 M nearly cancelling terms) amplify.  In
-// their own chain the small products keep every bit (their C stays ~2^-11 of the big one's);
-// the two sums meet by a VALU add (RNE).
-__device__ __forceinline__ void cx_mma_h3s(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x16& big,
-                                           f32x16& small) {
-  typedef cf16x8 H;
-  small = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(H, a[1]), __builtin_bit_cast(H, b[0]), small, 0, 0, 0);
-  small = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(H, a[0]), __builtin_bit_cast(H, b[1]), small, 0, 0, 0);
-  big = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(H, a[0]), __builtin_bit_cast(H, b[0]), big, 0, 0, 0);
-}
-
-// a weight-image value's fp16x3 / bf16x6 terms (NPL planes, `per` apart from img[base])
-template <int NPL>
-__device__ __forceinline__ void cx_wimg_put(unsigned short* __restrict__ img, int64_t base,
-                                            int64_t per, float v, float sc) {
-  if constexpr (NPL == 2) {
-    const float x = v * sc;
-    const _Float16 hb = (_Float16)x;
-    img[base] = __builtin_bit_cast(unsigned short, hb);
-    img[base + per] = __builtin_bit_cast(unsigned short, (_Float16)(x - (float)hb));
-  } else {
-    const __bf16 hb = (__bf16)v;
-    const float r1 = v - (float)hb;
-    const __bf16 mbf = (__bf16)r1;
-    const __bf16 lb = (__bf16)(r1 - (float)mbf);
-    img[base] = __builtin_bit_cast(unsigned short, hb);
-    img[base + per] = __builtin_bit_cast(unsigned short, mbf);
-    img[base + 2 * per] = __builtin_bit_cast(unsigned short, lb);
-  }
-}
-
-// fp16x3 scales of an implicit-GEMM convolution: m_exp[m] = h3_exp(max |w| over the taps and
-// loop channels of output row m) (fwd: m = co; dgrad: m = ci), one workgroup per m
-template <bool DGRAD>
-__global__ void conv_h3_wexp_kernel(const float* __restrict__ w, ConvDims g, int* __restrict__ m_exp) {
-  __shared__ float red[4];
-  const int m = blockIdx.x;
-  const int KHW = g.kh * g.kw;
-  const int L = DGRAD ? g.co : g.ci;
-  float mx = 0.f;
-  for (int i = threadIdx.x; i < L * KHW; i += blockDim.x) {
-    const int l = i / KHW, t = i - l * KHW;
-    const float v = DGRAD ? w[((int64_t)l * g.ci + m) * KHW + t] : w[((int64_t)m * g.ci + l) * KHW + t];
-    mx = fmaxf(mx, fabsf(v));
-  }
-  mx = wave_max(mx);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int i = 1; i < (int)(blockDim.x >> 6); ++i) mx = fmaxf(mx, red[i]);
-    m_exp[m] = h3_exp(__float_as_uint(mx));
-  }
-}
-
-// per-sample max |x| of an [n][per] tensor (float bits, unsigned atomic max; out zeroed first):
-// grid (chunks, n), 256 threads, 16-B loads where the sample's base is 16-B aligned
-__global__ void conv_h3_samax_kernel(const float* __restrict__ x, int64_t per,
-                                     unsigned* __restrict__ out) {
-  __shared__ float red[4];
-  const int n = blockIdx.y;
-  const float* xs = x + (int64_t)n * per;
-  // chunks of a multiple of 4 elements, so that 16-B aligned samples take the float4 path
-  const int64_t chunk = (((per + gridDim.x - 1) / gridDim.x) + 3) & ~(int64_t)3;
-  const int64_t b = (int64_t)blockIdx.x * chunk;
-  const int64_t e = b + chunk < per ? b + chunk : per;
-  if (b >= e) return;   // block-uniform: past the sample's end after the rounding up
-  float mx = 0.f;
-  if ((reinterpret_cast<uintptr_t>(xs + b) & 15) == 0) {
-    const int64_t e4 = b + ((e - b) & ~(int64_t)3);
-    // unrolled: 8 loads in flight per thread (one at a time ran at ~2.5 TB/s)
-#pragma unroll 8
-    for (int64_t i = b + 4 * threadIdx.x; i < e4; i += 4 * blockDim.x) {
-      const float4 v = *reinterpret_cast<const float4*>(xs + i);
-      mx = fmaxf(mx, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
-    }
-    for (int64_t i = e4 + threadIdx.x; i < e; i += blockDim.x) mx = fmaxf(mx, fabsf(xs[i]));
-  } else {
-#pragma unroll 8
-    for (int64_t i = b + threadIdx.x; i < e; i += blockDim.x) mx = fmaxf(mx, fabsf(xs[i]));
-  }
-  mx = wave_max(mx);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int i = 1; i < (int)(blockDim.x >> 6); ++i) mx = fmaxf(mx, red[i]);
-    if (b < e) atomicMax(out + n, __float_as_uint(mx));
-  }
-}
-
-// per-channel max |t| of an [N][C][plane] tensor (float bits, unsigned atomic max; out zeroed
-// first): grid (chunks, C), 256 threads striding the channel's N x plane elements
-__global__ void conv_h3_chamax_kernel(const float* __restrict__ t, int N, int C, int64_t plane,
-                                      unsigned* __restrict__ out) {
-  __shared__ float red[4];
-  const int ch = blockIdx.y;
-  const int64_t total = (int64_t)N * plane;
-  const int64_t chunk = (total + gridDim.x - 1) / gridDim.x;
-  const int64_t b = (int64_t)blockIdx.x * chunk;
-  const int64_t e = b + chunk < total ? b + chunk : total;
-  float mx = 0.f;
-  // the chunk walked sample by sample: inside one sample the channel's plane is contiguous,
-  // so the loop is a plain strided sweep with 8 loads in flight per thread
-  for (int64_t i = b; i < e;) {
-    const int64_t n = i / plane;
-    const int64_t seg = (n + 1) * plane < e ? (n + 1) * plane : e;
-    const float* base = t + (n * C + ch) * plane - n * plane;   // base[k]: element k
-#pragma unroll 8
-    for (int64_t k = i + threadIdx.x; k < seg; k += blockDim.x) mx = fmaxf(mx, fabsf(base[k]));
-    i = seg;
-  }
-  mx = wave_max(mx);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int k = 1; k < (int)(blockDim.x >> 6); ++k) mx = fmaxf(mx, red[k]);
-    if (b < e && mx > 0.f) atomicMax(out + ch, __float_as_uint(mx));
-  }
-}
-
-constexpr int CX_T = 512;
-constexpr int CX_COLS = 256;
-constexpr int CX_PATCH = 3 * 522 * 24;   // bf16: 3 planes x columns x pitch (max)
-constexpr int CX_PATCH1 = 3 * 267 * 40;  // the same for width stride 1 without row chunks
-constexpr int CX_PATCH_DB = 2 * 3 * 267 * 24;   // double-buffered (conv2 fwd: pitch 24)
-constexpr int CX_WIMG = 3 * 32 * 296;    // bf16: 3 planes x 32 channels x COP (max)
-constexpr int CX_PU = 3;                 // patch staging units per thread (max; template PU)
-constexpr int CX_WQ = 7;                 // 16-B weight-image chunks per thread
-
-struct CxGeom {
-  int KA;     // tap rows (of one chunk) padded to 8
-  int NBP;    // kernel-column pairs
-  int P;      // patch column pitch (bf16)
-  int COP;    // weight-image channel pitch (bf16)
-  int PCOL;   // patch columns
-  int RC;     // tap-row chunks per loop channel
-};
-
-__host__ __device__ constexpr int cx_pitch8odd(int v) {   // smallest 8 * odd >= v
-  return 8 * (((v + 7) / 8) % 2 == 0 ? (v + 7) / 8 + 1 : (v + 7) / 8);
-}
-
-// The geometry cx_geom gives an instantiation with compile-time a-groups / column pairs and
-// width stride 1 without row chunks (conv2 fwd / dgrad): with it a compile-time constant,
-// every fragment read is one per-lane base + an immediate offset (no address registers or
-// VALU per k-step).
-template <int NGA, int NBP>
-struct CxConst {
-  static constexpr int KA = 8 * NGA;
-  static constexpr int P = cx_pitch8odd(KA);
-  static constexpr int COP = cx_pitch8odd(2 * NBP * KA + 1);
-  static constexpr int PCOL = (256 - 1) + 2 * NBP;
-};
-
-__host__ __device__ inline CxGeom cx_geom(const ConvDims& g, bool dgrad) {
-  CxGeom c;
-  const int a = dgrad ? class_taps(g, 0) : g.kh;
-  c.KA = a <= 24 ? (a + 7) / 8 * 8 : 16;
-  c.RC = (a + c.KA - 1) / c.KA;
-  c.NBP = (g.kw + 1) / 2;
-  c.P = cx_pitch8odd(c.KA);        // 8 x odd bf16: conflict-free 16-B fragment reads
-  c.COP = cx_pitch8odd(2 * c.NBP * c.KA + 1);
-  c.PCOL = (CX_COLS - 1) * (dgrad ? 1 : g.sw) + 2 * c.NBP;
-  return c;
-}
-
-// split-weight image: [class][mb][loop channel][plane][32][COP] bf16 (NPL 3) or fp16 (NPL 2)
-// NPL 2: fp16 hi / lo planes of w 2^m_exp[m] (fp16x3)
-template <bool DGRAD, int NPL = 3>
-__global__ void conv_x6_wimg_kernel(const float* __restrict__ w, ConvDims g, CxGeom c,
-                                    unsigned short* __restrict__ img,
-                                    const int* __restrict__ m_exp, int flip_odd = 0) {
-  const int M = DGRAD ? g.ci : g.co;
-  const int L = (DGRAD ? g.co : g.ci) * c.RC;          // (channel, tap-row chunk) pairs
-  const int mbn = (M + 31) / 32;
-  const int classes = DGRAD ? g.sh : 1;
-  const int64_t per = (int64_t)32 * c.COP;             // one plane of one (class, mb, l)
-  const int64_t total = (int64_t)classes * mbn * L * per;
-  const int KHW = g.kh * g.kw;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    int64_t r = i;
-    const int e = static_cast<int>(r % per); r /= per;
-    const int l = static_cast<int>(r % L); r /= L;
-    const int mb = static_cast<int>(r % mbn); r /= mbn;
-    const int q = static_cast<int>(r);
-    const int mm = e / c.COP, rem = e - mm * c.COP;
-    const int b = rem / c.KA, al = rem - b * c.KA;
-    const int m = mb * 32 + mm;
-    const int ch = l / c.RC, a = (l - ch * c.RC) * c.KA + al;
-    float v = 0.f;
-    if (rem < 2 * c.NBP * c.KA && m < M && b < g.kw) {
-      if (!DGRAD) {
-        if (a < g.kh) v = w[((int64_t)m * g.ci + ch) * KHW + a * g.kw + b];
-      } else {
-        const int aq = class_taps(g, q);
-        if (a < aq) v = w[((int64_t)ch * g.ci + m) * KHW + (q + g.sh * (aq - 1 - a)) * g.kw + (g.kw - 1 - b)];
-      }
-      // k-step st = (tap-row group, column pair); the second half of the k-steps (the kk = 1
-      // waves' share) is stored negated: see conv_x6_kernel's epilogue.  flip_odd 1: the odd
-      // loop channels instead; 2: nothing negated (conv_h3_fwd2r_kernel)
-      const int st = (al >> 3) * c.NBP + (b >> 1), nks = (c.KA / 8) * c.NBP;
-      if (flip_odd == 0 ? st >= (nks + 1) / 2 : (flip_odd == 1 && (l & 1) != 0)) v = -v;
-    }
-    const float sc = NPL == 2 && m < M ? h3_scale(m_exp[m]) : 1.f;
-    cx_wimg_put<NPL>(img, ((((int64_t)q * mbn + mb) * L + l) * NPL) * per + e, per, v, sc);
-  }
-}
-
-// NGA, NBP > 0: compile-time a-groups / column pairs (fully unrolled k loop for the model's
-// conv2: fwd 3 x 6, dgrad 2 x 6; conv1 fwd 2 x 6); 0: read from c at run time.  PU: patch
-// staging units per thread (2, or 3 for conv1's 522-column stride-2 patch).  SW: width stride
-// (0: run time); RCH: tap-row chunks (c.RC) possible.  The width-stride-1 unchunked form
-// (conv2) keeps its smaller LDS patch and compile-time addressing.
-// DB: the input patch double-buffered (conv2 fwd): the next channel's patch is split and
-// stored into the other buffer in the middle of this channel's k-steps (its loads were issued
-// at the channel's start), so only the weight image copy stays between the two barriers.
-// NPL 2: fp16x3 -- the patch is staged as fp16 hi / lo of x 2^e_n (e_n from the sample's
-// max |x|, n_amax[n]), the image holds w 2^m_exp[m], three products per fragment pair, and the
-// epilogue multiplies by 2^-(m_exp[m] + e_n) (exact) before the bias.
-template <bool DGRAD, int NGA, int NBP_, int PU, int SW, bool RCH, bool DB = false, int NPL = 3>
-__global__ __launch_bounds__(CX_T, 1) void conv_x6_kernel(const float* __restrict__ in,
-                                                          const unsigned short* __restrict__ img,
-                                                          const float* __restrict__ bias,
-                                                          float* __restrict__ out, ConvDims g,
-                                                          const int* __restrict__ out_lens,
-                                                          CxGeom c, int gx, int gy,
-                                                          const int* __restrict__ m_exp,
-                                                          const unsigned* __restrict__ n_amax) {
-  __shared__ __attribute__((aligned(16))) unsigned short
-      ps[DB ? CX_PATCH_DB : ((SW == 1 && !RCH) ? CX_PATCH1 : CX_PATCH)];
-  __shared__ __attribute__((aligned(16))) unsigned short ws[CX_WIMG];
-  const int M = DGRAD ? g.ci : g.co;
-  const int L = DGRAD ? g.co : g.ci;
-  const int in_h = DGRAD ? g.ho : g.hi;
-  const int in_w = DGRAD ? g.wo : g.wi;
-  const int out_h = DGRAD ? g.hi : g.ho;
-  const int out_w = DGRAD ? g.wi : g.wo;
-  const int mbn = (M + 31) / 32;
-  int bx, by, bz;
-  xcd_tile(gx, gy, bx, by, bz);
-  const int n = bz / mbn;
-  const int mb = bz - n * mbn;
-  const int m0 = mb * 32;
-  const int c0 = bx * CX_COLS;
-  // output row and the first input row of its taps
-  int orow, prow0, q = 0, A;
-  if (!DGRAD) {
-    orow = by;
-    prow0 = orow * g.sh - g.ph;
-    A = g.kh;
-  } else {
-    int t = by, hq = 0;
-    for (q = 0; q < g.sh; ++q) {
-      hq = ((q - g.ph) % g.sh + g.sh) % g.sh;
-      const int cnt = hq < g.hi ? (g.hi - 1 - hq) / g.sh + 1 : 0;
-      if (t < cnt) break;
-      t -= cnt;
-    }
-    A = class_taps(g, q);
-    orow = hq + g.sh * t;
-    prow0 = (orow + g.ph - q) / g.sh - (A - 1);
-  }
-  const int sw = DGRAD ? 1 : (SW > 0 ? SW : g.sw);
-  const int pcol0 = DGRAD ? c0 + g.pw - g.kw + 1 : c0 * sw - g.pw;
-  const int RC = RCH ? c.RC : 1;
-  const int LL = L * RC;                       // staged (channel, tap-row chunk) pairs
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int cw = wave & 3, kk = wave >> 2;
-  const int plane_in = in_h * in_w;
-  const float* inn = in + (int64_t)n * L * plane_in;
-  constexpr bool CG = NGA > 0 && NBP_ > 0 && SW == 1 && !RCH;   // compile-time geometry
-  using CC = CxConst<(NGA > 0 ? NGA : 1), (NBP_ > 0 ? NBP_ : 1)>;
-  const int cP = CG ? CC::P : c.P;
-  const int cCOP = CG ? CC::COP : c.COP;
-  const int cKA = CG ? CC::KA : c.KA;
-  const int cPCOL = CG ? CC::PCOL : c.PCOL;
-  const int PPL = cPCOL * cP;                  // bf16 per patch plane
-  const int WPL = 32 * cCOP;                   // bf16 per weight plane
-  const int64_t wstride = (int64_t)NPL * WPL;  // one loop channel's image
-  const int en = NPL == 2 ? h3_exp(n_amax[n]) : 0;
-  const float nsc = h3_scale(en);
-  const unsigned short* wimg = img + ((int64_t)q * mbn + mb) * L * RC * wstride;
-  const int ngr = NGA > 0 ? NGA : cKA / 8;
-  const int nbp = NBP_ > 0 ? NBP_ : c.NBP;
-  const int units = cPCOL * ngr;
-  const int wchunks = (int)(wstride / 8);
-
-  float rp[PU][8];
-  u32x4 rw[CX_WQ];
-  auto load_w = [&](int l) {
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<unsigned short*>(wimg + (int64_t)l * wstride), (short)0,
-        static_cast<int>(wstride * 2), 0x00020000);
-#pragma unroll
-    for (int r = 0; r < CX_WQ; ++r) {
-      const int i = tid + CX_T * r;
-      rw[r] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                            wr, i < wchunks ? i * 16 : 0x7ffffff0, 0, 0));
-    }
-  };
-  auto load = [&](int l) {
-    const int ch = RCH ? l / RC : l, ar0 = RCH ? (l - ch * RC) * cKA : 0;   // chunk's first tap row
-    const __amdgpu_buffer_rsrc_t rs = conv_rsrc(inn + (int64_t)ch * plane_in, plane_in);
-#pragma unroll
-    for (int u = 0; u < PU; ++u) {
-      const int unit = tid + CX_T * u;
-      const int j = unit / ngr, rg = unit - (unit / ngr) * ngr;
-      const int ic = pcol0 + j;
-      const bool cok = unit < units && ic >= 0 && ic < in_w;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int a = ar0 + 8 * rg + i, ir = prow0 + a;
-        const bool ok = cok && a < A && ir >= 0 && ir < in_h;
-        rp[u][i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                 rs, ok ? (ir * in_w + ic) * 4 : 0x7ffffff0, 0, 0));
-      }
-    }
-    if (!DB) load_w(l);
-  };
-  auto store_patch = [&](unsigned short* dst) {
-#pragma unroll
-    for (int u = 0; u < PU; ++u) {
-      const int unit = tid + CX_T * u;
-      if (unit < units) {
-        const int j = unit / ngr, rg = unit - (unit / ngr) * ngr;
-        cx_store8<NPL>(dst, PPL, j * cP + 8 * rg, rp[u], nsc);
-      }
-    }
-  };
-  auto store_w = [&]() {
-#pragma unroll
-    for (int r = 0; r < CX_WQ; ++r) {
-      const int i = tid + CX_T * r;
-      if (i < wchunks) *reinterpret_cast<u32x4*>(ws + 8 * i) = rw[r];
-    }
-  };
-  auto store = [&]() {
-    store_patch(ps);
-    store_w();
-  };
-
-  f32x16 acc[2], acs[2];   // acs: fp16x3's small products (cx_mma_h3s)
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[j][r] = acs[j][r] = 0.f;
-  const int nks = ngr * nbp;
-  const int s_beg = kk == 0 ? 0 : (nks + 1) / 2;
-  const int s_end = kk == 0 ? (nks + 1) / 2 : nks;
-  const int fr = lane & 31, fh = lane >> 5;
-  const bool active = orow < out_h && c0 + 64 * cw < out_w;
-
-  load(0);
-  if (DB) load_w(0);
-  store();
-  __syncthreads();
-  for (int l = 0; l < LL; ++l) {
-    if (l + 1 < LL) load(l + 1);
-    const unsigned short* pcur = DB ? ps + (l & 1) * NPL * PPL : ps;
-    unsigned short* pnext = ps + ((l + 1) & 1) * NPL * PPL;
-    bool staged = false;
-    if (active) {
-      auto kstep = [&](int st) {
-        const int ga = st / nbp, p = st - (st / nbp) * nbp;
-        const int b = 2 * p + fh;
-        bf16x8 af[3], bfr[2][3];
-        const int aw = fr * cCOP + b * cKA + 8 * ga;
-#pragma unroll
-        for (int pl = 0; pl < NPL; ++pl) af[pl] = *reinterpret_cast<const bf16x8*>(ws + pl * WPL + aw);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int ap = ((64 * cw + 32 * j + fr) * sw + b) * cP + 8 * ga;
-#pragma unroll
-          for (int pl = 0; pl < NPL; ++pl)
-            bfr[j][pl] = *reinterpret_cast<const bf16x8*>(pcur + pl * PPL + ap);
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          if constexpr (NPL == 2) cx_mma_h3s(af, bfr[j], acc[j], acs[j]);
-          else acc[j] = cx_mma<NPL>(af, bfr[j], acc[j]);
-        }
-      };
-      if (NGA > 0 && NBP_ > 0) {
-        constexpr int NK = NGA * NBP_, H0 = (NK + 1) / 2;
-        constexpr int MID = H0 / 2 + 1;     // DB: stage the next patch after these k-steps
-        if (kk == 0) {
-#pragma unroll
-          for (int st = 0; st < H0; ++st) {
-            if (DB && st == MID && l + 1 < LL) {
-              store_patch(pnext);
-              load_w(l + 1);        // issued once rp is free: rp and rw never live together
-              staged = true;
-            }
-            kstep(st);
-            if (DB) __builtin_amdgcn_sched_barrier(0);   // bound the fragment-read hoisting
-          }
-        } else {
-#pragma unroll
-          for (int st = H0; st < NK; ++st) {
-            if (DB && st == H0 + MID && l + 1 < LL) {
-              store_patch(pnext);
-              load_w(l + 1);
-              staged = true;
-            }
-            kstep(st);
-            if (DB) __builtin_amdgcn_sched_barrier(0);
-          }
-        }
-      } else {
-        for (int st = s_beg; st < s_end; ++st) kstep(st);
-      }
-    }
-    if (DB && !staged && l + 1 < LL) {
-      store_patch(pnext);
-      load_w(l + 1);
-    }
-    __syncthreads();
-    if (l + 1 < LL) {
-      if (DB) {
-        store_w();
-      } else {
-        store();
-      }
-      __syncthreads();
-    }
-  }
-  if constexpr (NPL == 2) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[j] += acs[j];
-  }
-  // the two k halves meet in LDS (the patch area): half 1 writes, half 0 adds (fixed order).
-  // Sign split: half 1 ran on the negated weight image (its chains hold -(its sum)), so the
-  // MFMAs' toward -inf rounding of low addend bits (profiles/r5n_mfma_rounding.txt) drifts
-  // the two halves' contributions in opposite directions and they cancel to their difference.
-  float* red = reinterpret_cast<float*>(ps);
-  if (kk == 1) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) red[((cw * 2 + j) * 16 + r) * 64 + lane] = acc[j][r];
-  }
-  __syncthreads();
-  if (kk == 1 || !active) return;
-  const int len = (!DGRAD && out_lens != nullptr) ? out_lens[n] : out_w;
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int col = c0 + 64 * cw + 32 * j + fr;
-    if (col >= out_w) continue;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int m = m0 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-      if (m < M) {
-        float v = acc[j][r] - red[((cw * 2 + j) * 16 + r) * 64 + lane];   // sign split
-        if (NPL == 2) v = __builtin_ldexpf(v, -(m_exp[m] + en));
-        if (!DGRAD) {
-          if (bias != nullptr) v += bias[m];
-          if (col >= len) v = 0.f;
-        }
-        out[(((int64_t)n * M + m) * out_h + orow) * out_w + col] = v;
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// conv2 forward on fp16x3, two output rows per workgroup (height stride 2, width stride 1,
-// <= 24 tap rows, 6 kernel-column pairs: the model's 21 x 11 conv2).  With stride 2, output
-// rows r and r + 4 read input rows 8 apart -- exactly one 8-row fragment group -- so ONE
-// column-major patch of 32 input rows serves both: row r's B fragments are patch row groups
-// 0..2, row r + 4's are groups 1..3, and both multiply the SAME weight fragments (tap row group
-// ga).  Per loop channel a workgroup then stages 32 patch rows and one weight image for two
-// output rows (conv_x6_kernel: 24 rows and one image for one row), and every weight fragment
-// read feeds six MFMAs instead of three.  Rows r, r + 4 with r = 8 b + j (j < 4) tile the
-// output rows in pairs; a row past the output is computed and not stored.
-// Waves: 8 x 32 columns, each all 18 k-steps of both rows (no k halves).  The sign split of
-// conv_x6_kernel (one k half on negated weights) becomes a sign per loop channel: the weight
-// image stores odd channels negated, both MFMA chains (hi.hi and the small products,
-// cx_mma_h3s) restart from zero every channel and are folded into a VALU total with the
-// channel's sign (DS2_C2R_MODE 2, the default), so the MFMAs' floor of low addend bits drifts
-// one way in even channels and the other in odd ones and cancels in the total (DESIGN.md §4
-// "MFMA rounding").  Mode 1 (negate the running accumulators between channels, no restart)
-// spilled 46 VGPRs; mode 0 keeps no sign split.  The next channel's patch is double-buffered as
-// in conv_x6_kernel.
-#ifndef DS2_C2R_MODE
-#define DS2_C2R_MODE 2
-#endif
-constexpr int C2_KAP = 32;                                  // patch rows
-constexpr int C2_P = cx_pitch8odd(C2_KAP);                  // 40: 8 x odd bf16
-constexpr int C2_PCOL = CxConst<3, 6>::PCOL;                // 267
-constexpr int C2_PPL = C2_PCOL * C2_P;                      // fp16 per patch plane
-constexpr int C2_WPL = 32 * CxConst<3, 6>::COP;             // fp16 per weight plane
-constexpr int C2_WQ = (2 * C2_WPL / 8 + CX_T - 1) / CX_T;   // 16-B image chunks per thread
-constexpr int C2_PU = (C2_PCOL * (C2_KAP / 8) + CX_T - 1) / CX_T;   // patch units per thread
-
-__global__ __launch_bounds__(CX_T, 1) void conv_h3_fwd2r_kernel(
-    const float* __restrict__ in, const unsigned short* __restrict__ img,
-    const float* __restrict__ bias, float* __restrict__ out, ConvDims g,
-    const int* __restrict__ out_lens, int gx, int gy, const int* __restrict__ m_exp,
-    const unsigned* __restrict__ n_amax) {
-  using CC = CxConst<3, 6>;
-  __shared__ __attribute__((aligned(16))) unsigned short ps[2 * 2 * C2_PPL];
-  __shared__ __attribute__((aligned(16))) unsigned short ws[2 * C2_WPL];
-  const int M = g.co, L = g.ci;
-  const int mbn = (M + 31) / 32;
-  int bx, by, bz;
-  xcd_tile(gx, gy, bx, by, bz);
-  const int n = bz / mbn;
-  const int mb = bz - n * mbn;
-  const int m0 = mb * 32;
-  const int c0 = bx * CX_COLS;
-  const int orow = 8 * (by >> 2) + (by & 3);          // and orow + 4
-  const int prow0 = orow * 2 - g.ph;                   // the patch's first input row
-  const int pcol0 = c0 - g.pw;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int plane_in = g.hi * g.wi;
-  const float* inn = in + (int64_t)n * L * plane_in;
-  const int en = h3_exp(n_amax[n]);
-  const float nsc = h3_scale(en);
-  constexpr int wstride = 2 * C2_WPL;                  // one loop channel's image (fp16)
-  const unsigned short* wimg = img + (int64_t)mb * L * wstride;
-  constexpr int wchunks = wstride / 8;
-  constexpr int units = C2_PCOL * (C2_KAP / 8);
-  const int last_row = 2 * 4 + 20;                     // rows a >= 29 feed no tap of either row
-
-  float rp[C2_PU][8];
-  u32x4 rw[C2_WQ];
-  auto load_w = [&](int l) __attribute__((always_inline)) {
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<unsigned short*>(wimg + (int64_t)l * wstride), (short)0, wstride * 2, 0x00020000);
-#pragma unroll
-    for (int r = 0; r < C2_WQ; ++r) {
-      const int i = tid + CX_T * r;
-      rw[r] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                            wr, i < wchunks ? i * 16 : 0x7ffffff0, 0, 0));
-    }
-  };
-  auto load = [&](int l) __attribute__((always_inline)) {
-    const __amdgpu_buffer_rsrc_t rs = conv_rsrc(inn + (int64_t)l * plane_in, plane_in);
-#pragma unroll
-    for (int u = 0; u < C2_PU; ++u) {
-      const int unit = tid + CX_T * u;
-      const int j = unit >> 2, rg = unit & 3;
-      const int ic = pcol0 + j;
-      const bool cok = unit < units && ic >= 0 && ic < g.wi;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int a = 8 * rg + i, ir = prow0 + a;
-        const bool ok = cok && a <= last_row && ir >= 0 && ir < g.hi;
-        rp[u][i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                 rs, ok ? (ir * g.wi + ic) * 4 : 0x7ffffff0, 0, 0));
-      }
-    }
-  };
-  auto store_patch = [&](unsigned short* dst) __attribute__((always_inline)) {
-#pragma unroll
-    for (int u = 0; u < C2_PU; ++u) {
-      const int unit = tid + CX_T * u;
-      if (unit < units) cx_store8<2>(dst, C2_PPL, (unit >> 2) * C2_P + 8 * (unit & 3), rp[u], nsc);
-    }
-  };
-  auto store_w = [&]() __attribute__((always_inline)) {
-#pragma unroll
-    for (int r = 0; r < C2_WQ; ++r) {
-      const int i = tid + CX_T * r;
-      if (i < wchunks) *reinterpret_cast<u32x4*>(ws + 8 * i) = rw[r];
-    }
-  };
-
-  f32x16 acc[2], acs[2];
-#if DS2_C2R_MODE == 2
-  f32x16 tot[2];
-#endif
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      acc[j][r] = acs[j][r] = 0.f;
-#if DS2_C2R_MODE == 2
-      tot[j][r] = 0.f;
-#endif
-    }
-  const int fr = lane & 31, fh = lane >> 5;
-  const bool active = c0 + 32 * wave < g.wo;
-
-  load(0);
-  load_w(0);
-  store_patch(ps);
-  store_w();
-  __syncthreads();
-  for (int l = 0; l < L; ++l) {
-    if (l + 1 < L) load(l + 1);
-    const unsigned short* pcur = ps + (l & 1) * 2 * C2_PPL;
-    unsigned short* pnext = ps + ((l + 1) & 1) * 2 * C2_PPL;
-    bool staged = false;
-    if (active) {
-      constexpr int NK = 3 * 6, MID = 6;
-#pragma unroll
-      for (int st = 0; st < NK; ++st) {
-        if (st == MID && l + 1 < L) {
-          store_patch(pnext);
-          load_w(l + 1);
-          staged = true;
-        }
-        const int ga = st / 6, p = st - (st / 6) * 6;
-        const int b = 2 * p + fh;
-        bf16x8 af[3], b0[3], b1[3];
-        const int aw = fr * CC::COP + b * CC::KA + 8 * ga;
-        const int ap = (32 * wave + fr + b) * C2_P + 8 * ga;
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl) {
-          af[pl] = *reinterpret_cast<const bf16x8*>(ws + pl * C2_WPL + aw);
-          b0[pl] = *reinterpret_cast<const bf16x8*>(pcur + pl * C2_PPL + ap);
-          b1[pl] = *reinterpret_cast<const bf16x8*>(pcur + pl * C2_PPL + ap + 8);
-        }
-        cx_mma_h3s(af, b0, acc[0], acs[0]);
-        cx_mma_h3s(af, b1, acc[1], acs[1]);
-        __builtin_amdgcn_sched_barrier(0);   // bound the fragment-read hoisting
-      }
-    }
-    if (!staged && l + 1 < L) {
-      store_patch(pnext);
-      load_w(l + 1);
-    }
-#if DS2_C2R_MODE == 1
-    if (l + 1 < L) {
-      // the next channel's weights are stored negated when this one's were not (and back)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        acc[j] = -acc[j];
-        acs[j] = -acs[j];
-      }
-    }
-#elif DS2_C2R_MODE == 2
-    // both chains restart every channel and are folded into a VALU sum (RNE); odd channels
-    // ran on the negated weight image, so they are subtracted
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      if (l & 1) tot[j] -= acc[j] + acs[j];
-      else tot[j] += acc[j] + acs[j];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[j][r] = acs[j][r] = 0.f;
-    }
-#endif
-    __syncthreads();
-    if (l + 1 < L) {
-      store_w();
-      __syncthreads();
-    }
-  }
-  if (!active) return;
-#if DS2_C2R_MODE == 1
-  const float sgn = ((L - 1) & 1) ? -1.f : 1.f;        // the last channel's sign
-#else
-  const float sgn = 1.f;
-#endif
-#if DS2_C2R_MODE == 2
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    acc[j] = tot[j];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acs[j][r] = 0.f;
-  }
-#endif
-  const int len = out_lens != nullptr ? out_lens[n] : g.wo;
-  const int col = c0 + 32 * wave + fr;
-  if (col >= g.wo) return;
-#pragma unroll
-  for (int rr = 0; rr < 2; ++rr) {
-    const int row = orow + 4 * rr;
-    if (row >= g.ho) continue;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int m = m0 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-      if (m < M) {
-        float v = __builtin_ldexpf((acc[rr][r] + acs[rr][r]) * sgn, -(m_exp[m] + en));
-        if (bias != nullptr) v += bias[m];
-        if (col >= len) v = 0.f;
-        out[(((int64_t)n * M + m) * g.ho + row) * g.wo + col] = v;
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// bf16x6 weight gradient (width stride 1, <= 32 input and output channels; instantiated for
-// the model's conv2 columns: kw = 11, pw = 5) on v_mfma_f32_32x32x16_bf16 at fp32 accuracy:
-//   dW[co][ci][a][b] = sum over (n, ho, wo) of dy[n][co][ho][wo] x[n][ci][ho sh - ph + a][wo - pw + b]
-// For ONE tap (a, b) this is a 32 x 32 (co x ci) product over positions: M = co, N = ci,
-// K = 16 consecutive output columns.  Wave w of a workgroup owns tap row a = 4 gi + w and all
-// kw kernel columns (kw accumulators).  Its A fragment (dy: 8 consecutive columns of one co,
-// one ds_read_b128 per plane) serves all kw taps; the B fragments of the kw taps are windows
-// at offsets b + 8 - pw into 24 consecutive x columns of one ci (three aligned ds_read_b128
-// per plane), cut out by register selection (even offsets) or v_alignbit (odd).
-// Workgroup = (tap-row group gi, split s): it runs over the (n, ho) rows of split s in
-// 64-column stages -- dy[32 co][64] and x[4 rows][32 ci][80 columns] split into hi/mid/lo
-// bf16 planes in LDS (81 KB, so two workgroups share a CU and cover each other's staging) --
-// and writes its kw x 32 x 32 sums into slab s; wgrad_reduce_kernel adds the slabs in a fixed
-// order (deterministic).
-constexpr int CW_T = 256;
-constexpr int CW_COLS = 64;
-constexpr int CW_XP = 88;                  // x row pitch (bf16): 80 columns, 8 x odd
-constexpr int CW_DP = 72;                  // dy row pitch (bf16): 64 columns, 8 x odd
-constexpr int CW_XPL = 4 * 32 * CW_XP;     // bf16 per x plane
-constexpr int CW_DPL = 32 * CW_DP;         // bf16 per dy plane
-constexpr int CW_SLOTS = 512;              // workgroups per launch (two per CU)
-
-// 8 fp32 -> hi / mid / lo bf16 rows of 16 B (RNE casts, exact residuals)
-__device__ __forceinline__ void cw_split_store(unsigned short* __restrict__ s, int plane, int at,
-                                               const float (&v)[8]) {
-  cx_split_store8(s, plane, at, v);
-}
-
-// Partial sums of the bf16x6 weight-gradient kernels: one contiguous block per workgroup,
-// partial[s][gi][co 32][w 4][b KW][ci 32] (tap row a = 4 gi + w) -- lane fr = ci, so every
-// store instruction writes two whole 128-B runs; wgrad_reduce_x6_kernel sums the splits in
-// order and scatters into dW[co][ci][a][b].  (The [co][ci][a][b] slab layout had each lane
-// store to its own line: 2.6x the partial bytes in write traffic.)
-constexpr int X6W_BLOCK = 32 * 4 * 32;     // floats per (co, w, ci) plane of one kernel column
-                                           // (4 tap rows per group; NW rows: NW / 4 of them)
-template <int KW, int NW = 4>
-__device__ __forceinline__ void x6w_store_block(float* __restrict__ partial, int s, int G, int gi,
-                                                int wave, bool active, int fr, int fh,
-                                                const f32x16 (&acc)[KW]) {
-  if (!active) return;   // rows a >= kh: never read by the reduce
-  float* blk = partial + ((int64_t)s * G + gi) * (X6W_BLOCK / 4 * NW) * KW;
-#pragma unroll
-  for (int b = 0; b < KW; ++b)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int co = (r & 3) + 8 * (r >> 2) + 4 * fh;
-      blk[((co * NW + wave) * KW + b) * 32 + fr] = acc[b][r];
-    }
-}
-
-// dW[co][ci][a][b] = sum over the S splits (in order) of the blocks above; thread = one
-// (gi, co, w, b, ci) element in block order (coalesced loads)
-// co_amax / ci_amax (fp16x3 partials, else NULL): the sums are scaled by 2^(e_co + e_ci)
-__global__ void wgrad_reduce_x6_kernel(const float* __restrict__ partial, int S, int G, int KW,
-                                       int NW, ConvDims g, float* __restrict__ dw,
-                                       const unsigned* __restrict__ co_amax,
-                                       const unsigned* __restrict__ ci_amax) {
-  const int64_t per = (int64_t)G * (X6W_BLOCK / 4 * NW) * KW;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < per;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    int64_t r = i;
-    const int ci = static_cast<int>(r % 32); r /= 32;
-    const int b = static_cast<int>(r % KW); r /= KW;
-    const int w = static_cast<int>(r % NW); r /= NW;
-    const int co = static_cast<int>(r % 32);
-    const int gi = static_cast<int>(r / 32);
-    const int a = NW * gi + w;
-    if (a >= g.kh || co >= g.co || ci >= g.ci) continue;
-    float acc = 0.f;
-#pragma unroll 8
-    for (int s = 0; s < S; ++s) acc += partial[(int64_t)s * per + i];   // order kept
-    if (co_amax != nullptr) acc = __builtin_ldexpf(acc, -(h3_exp(co_amax[co]) + h3_exp(ci_amax[ci])));
-    dw[((int64_t)co * g.ci + ci) * g.kh * KW + a * KW + b] = acc;
-  }
-}
-
-template <int KW, int OFF0>
-__global__ __launch_bounds__(CW_T, 2) void conv_x6_wgrad_kernel(const float* __restrict__ dy,
-                                                                 const float* __restrict__ x,
-                                                                 float* __restrict__ partial,
-                                                                 ConvDims g, int S) {
-  __shared__ __attribute__((aligned(16))) unsigned short xs[3 * CW_XPL];
-  __shared__ __attribute__((aligned(16))) unsigned short ds[3 * CW_DPL];
-  constexpr int kOob = 0x7ffffff0;
-  const int G = (g.kh + 3) / 4;
-  // XCD-aware: the G tap-row groups of one split (the same x rows) get consecutive ids of
-  // one XCD's run (blocks are dealt to the XCDs round-robin), so they share its L2
-  int gi, s;
-  {
-    const int nwg = gridDim.x, o = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = o & 7;
-    const int id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (o >> 3);
-    gi = id % G;
-    s = id / G;
-  }
-  const int R = g.n * g.ho;
-  const int r0 = static_cast<int>((int64_t)s * R / S);
-  const int r1 = static_cast<int>((int64_t)(s + 1) * R / S);
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int a = 4 * gi + wave;
-  const bool active = a < g.kh;
-  const int fr = lane & 31, fh = lane >> 5;
-  const int nch = (g.wo + CW_COLS - 1) / CW_COLS;
-  const int dplane = g.ho * g.wo, xplane = g.hi * g.wi;   // host: channel stacks < 2^31 B
-  const int dco = tid >> 3, dseg = tid & 7;                 // dy staging: co, 8-column segment
-
-  f32x16 acc[KW];
-#pragma unroll
-  for (int b = 0; b < KW; ++b)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
-
-  for (int row = r0; row < r1; ++row) {
-    const int n = row / g.ho, ho = row - (row / g.ho) * g.ho;
-    const __amdgpu_buffer_rsrc_t drs = conv_rsrc(dy + (int64_t)n * g.co * dplane, (int64_t)g.co * dplane);
-    const __amdgpu_buffer_rsrc_t xrs = conv_rsrc(x + (int64_t)n * g.ci * xplane, (int64_t)g.ci * xplane);
-    const int xr0 = ho * g.sh - g.ph + 4 * gi;
-    for (int ch = 0; ch < nch; ++ch) {
-      const int c0 = ch * CW_COLS;
-      // one base offset per 8-column run; a column past either edge of its row (or a row
-      // outside the input) loads from the out-of-range offset, i.e. zero
-      float dv[8], xv[5][8];
-      {
-        const int cb = c0 + 8 * dseg;
-        const int vo = dco < g.co ? (dco * dplane + ho * g.wo + cb) * 4 : kOob;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          dv[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                drs, cb + i < g.wo ? vo + 4 * i : kOob, 0, 0));
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < 5; ++u) {
-        const int id = tid + CW_T * u;
-        const int j = id % 10, ci = (id / 10) & 31, w = id / 320;
-        const int xr = xr0 + w;
-        const bool ok = ci < g.ci && xr >= 0 && xr < g.hi && 4 * gi + w < g.kh;
-        const int cb = c0 - 8 + 8 * j;
-        const int vo = ok ? (ci * xplane + xr * g.wi + cb) * 4 : kOob;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const bool cok = cb + i >= 0 && cb + i < g.wi;
-          xv[u][i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                   xrs, cok ? vo + 4 * i : kOob, 0, 0));
-        }
-      }
-      __syncthreads();   // every wave is done with the previous stage's fragments
-      cw_split_store(ds, CW_DPL, dco * CW_DP + 8 * dseg, dv);
-#pragma unroll
-      for (int u = 0; u < 5; ++u) {
-        const int id = tid + CW_T * u;
-        const int j = id % 10, ci = (id / 10) & 31, w = id / 320;
-        cw_split_store(xs, CW_XPL, (w * 32 + ci) * CW_XP + 8 * j, xv[u]);
-      }
-      __syncthreads();
-      if (active) {
-#pragma unroll 1
-        for (int kst = 0; kst < CW_COLS / 16; ++kst) {
-          bf16x8 af[3];
-#pragma unroll
-          for (int pl = 0; pl < 3; ++pl)
-            af[pl] = *reinterpret_cast<const bf16x8*>(ds + pl * CW_DPL + fr * CW_DP + 16 * kst + 8 * fh);
-          // one plane of x at a time (12 window registers): products with the lo, then
-          // the mid, then the hi terms of x, each over the kw taps
-#pragma unroll
-          for (int pi = 0; pi < 3; ++pi) {
-            const int pl = 2 - pi;
-            unsigned wv[12];
-#pragma unroll
-            for (int jj = 0; jj < 3; ++jj) {
-              const u32x4 q = *reinterpret_cast<const u32x4*>(
-                  xs + pl * CW_XPL + (wave * 32 + fr) * CW_XP + 8 * (2 * kst + fh + jj));
-#pragma unroll
-              for (int e = 0; e < 4; ++e) wv[4 * jj + e] = q[e];
-            }
-#pragma unroll
-            for (int b = 0; b < KW; ++b) {
-              const int o = b + OFF0;   // window offset of tap column b (compile time)
-              u32x4 q;
-#pragma unroll
-              for (int e = 0; e < 4; ++e)
-                q[e] = (o & 1) ? __builtin_amdgcn_alignbit(wv[(o + 1) / 2 + e], wv[(o - 1) / 2 + e], 16)
-                               : wv[o / 2 + e];
-              const bf16x8 bx = __builtin_bit_cast(bf16x8, q);
-              // x term pl (0 hi, 1 mid, 2 lo) pairs with the dy terms i <= 2 - pl (the
-              // products that carry fp32 weight), smaller terms first
-#pragma unroll
-              for (int i = 2 - pl; i >= 0; --i)
-                acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bx, acc[b], 0, 0, 0);
-            }
-          }
-        }
-      }
-    }
-  }
-  x6w_store_block<KW>(partial, s, G, gi, wave, active, fr, fh, acc);
-}
-
-// ---------------------------------------------------------------------------
-// Sliding-window form of the bf16x6 weight gradient (default where conv_x6_wgrad_kernel
-// applies and the height stride is <= 2).  Same workgroups (tap-row group gi of 4 rows, split
-// s; 4 waves, one tap row each, kw accumulators) and the same per-tap MFMA step, but a split
-// walks the (n, 32-column chunk, ho) rows with ho fastest: output row ho + 1's four x rows are
-// row ho's moved down by sh, so each row stages only sh NEW x rows (plus its dy row) into a
-// 6-slot ring (4 window rows + 2 incoming) -- 1.5 instead of 5 staging units of 8 values per
-// thread -- while the MFMAs of row ho run on the other slots; one barrier per row.  Each x row
-// is staged once per (group, chunk) instead of kh / sh times, and the G groups of a split run on
-// one XCD (consecutive workgroup ids), so they share its L2 for x and dy.
-constexpr int SW_COLS = 32;                 // output columns per row stage (two 16-column k-steps)
-constexpr int SW_XP = 56;                   // x slot row pitch (bf16): columns c0 - 8 .. c0 + 39;
-                                            // 7 x 16 B (odd): ds_read_b128's 16-lane groups
-                                            // hit 16 distinct 16-B bank slots (48 had 2-way
-                                            // conflicts: 34 % of LDS cycles in SQ counters)
-constexpr int SW_DP = 40;                   // dy row pitch (bf16): 32 columns, 5 x 16 B
-constexpr int SW_XSL = 32 * SW_XP;          // bf16 per x slot (32 input channels)
-constexpr int SW_DPL = 32 * SW_DP;          // bf16 per dy plane
-
-// NW = 8: eight waves (tap rows) per group, one 512-thread workgroup per CU with a 10-slot ring
-// (123 KB of LDS): G = 3 groups instead of 6 for conv2's 21 tap rows, so every x and dy row is
-// staged -- and fetched -- half as often
-// NPL 2: fp16x3 -- dy staged as fp16 hi / lo of dy 2^e_co (co_amax: max |dy| of each output
-// channel over the batch), x as hi / lo of x 2^e_ci (ci_amax), three products per fragment pair;
-// wgrad_reduce_x6_kernel undoes 2^-(e_co + e_ci) on the summed partials
-// SWC = 64 (NW 8, fp16x3): 64-column row stages -- x slot pitch 88 (11 x 16 B), dy pitch 72
-// (9 x 16 B), 80 x columns staged per 64 output columns instead of 48 per 32, half the stages
-// and barriers per MFMA; 131 KB of LDS.  Staging units (x: 32 channels x 10 runs per row, dy: 32
-// x 8): unit a = tid (waves 0-4 x row 0, waves 5-7 x row 1 units 0-191), unit b = waves 0-1 x
-// row 1 units 192-319, waves 2-5 dy, waves 6-7 none (kinds wave-uniform)
-template <int KW, int OFF0, int NW = 4, int NPL = 3, int SWC = SW_COLS>
-__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_x6_wgrad_sw_kernel(
-    const float* __restrict__ dy, const float* __restrict__ x, float* __restrict__ partial,
-    ConvDims g, int S, const unsigned* __restrict__ co_amax, const unsigned* __restrict__ ci_amax) {
-  static_assert(NW == 4 || NW == 8, "waves per group");
-  static_assert(SWC == SW_COLS || (SWC == 64 && NW == 8 && NPL == 2), "64-column stages: NW 8, fp16x3");
-  constexpr int RING = NW + 2;                // NW window rows + 2 incoming
-  constexpr int XP = SWC == 64 ? 88 : SW_XP, DP = SWC == 64 ? 72 : SW_DP;
-  constexpr int XSL = 32 * XP, DPL = 32 * DP;
-  constexpr int XRUNS = (SWC + 16) / 8, DRUNS = SWC / 8;
-  constexpr bool DY_IN_A = NW == 8 && SWC == SW_COLS;   // the dy waves' unit rides in va
-  __shared__ __attribute__((aligned(16))) unsigned short xs[(SWC == 64 ? 2 : 3) * RING * XSL];
-  __shared__ __attribute__((aligned(16))) unsigned short ds[2][(SWC == 64 ? 2 : 3) * DPL];
-  constexpr int XPL = RING * XSL;
-  constexpr int kOob = 0x7ffffff0;
-  const int G = (g.kh + NW - 1) / NW;
-  int gi, s;
-  {
-    const int nwg = gridDim.x, o = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = o & 7;
-    const int id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (o >> 3);
-    gi = id % G;
-    s = id / G;
-  }
-  const int nch = (g.wo + SWC - 1) / SWC;
-  const int R = g.n * nch * g.ho;                           // host: < 2^31
-  const int r0 = static_cast<int>((int64_t)s * R / S);
-  const int r1 = static_cast<int>((int64_t)(s + 1) * R / S);
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int a = NW * gi + wave;
-  const bool active = a < g.kh;
-  const int fr = lane & 31, fh = lane >> 5;
-  const int dplane = g.ho * g.wo, xplane = g.hi * g.wi;   // host: channel stacks < 2^31 B
-  const int wtop = NW * gi - g.ph;                          // window row 0 of output row 0
-  // staging units (8 values each): 384 x units (incoming row r, channel, 8-column run j) and
-  // 128 dy units (channel, run j).  NW = 4: thread t takes units t and t + 256 (unit kinds are
-  // wave-uniform: waves 0-2 unit a row 0, wave 3 row 1; waves 0-1 unit b x row 1, waves 2-3
-  // dy -- so the buffer resources stay scalar).  NW = 8: thread t takes unit t alone (waves
-  // 0-2 x row 0, 3-5 x row 1, 6-7 dy; unit b unused)
-  const int u1 = NW == 4 ? tid + 256 : tid;
-  // (const initialisers, as in the 32-column form: assigning these inside if-constexpr branches
-  // made hipcc 7.2 pack sc_a / sc_b into one register pair and apply them with v_pk_mul_f32
-  // op_sel swapped -- wrong scales, test_conv_x6_wgrad_forms)
-  constexpr bool W64 = SWC == 64;
-  const int ta = W64 ? (wave < 5 ? tid : tid - 320) : (NW == 4 ? tid : (wave < 6 ? tid % 192 : 0));
-  const int xr_a = W64 ? (wave >= 5 ? 1 : 0) : NW == 4 ? (wave == 3 ? 1 : 0) : (wave >= 3 ? 1 : 0);
-  const int xc_a = W64 ? ta / XRUNS : NW == 4 ? (ta / 6) & 31 : ta / 6;
-  const int xj_a = W64 ? ta % XRUNS : ta % 6;
-  const bool a_is_x = W64 || NW == 4 || wave < 6;
-  const bool b_is_x = W64 ? wave < 2 : NW == 4 && wave < 2;
-  const bool b_is_dy = W64 ? (wave >= 2 && wave < 6) : NW == 4 ? wave >= 2 : wave >= 6;
-  const int xc_b = W64 ? (192 + tid) / XRUNS : (u1 / 6) & 31;      // x unit: incoming row 1
-  const int xj_b = W64 ? (192 + tid) % XRUNS : u1 % 6;
-  const int dc_b = W64 ? (tid - 128) / DRUNS : (u1 - 384) >> 2;    // dy unit
-  const int dj_b = W64 ? (tid - 128) % DRUNS : (u1 - 384) & 3;
-  // fp16x3 staging scales of this thread's units (channels fixed for the whole launch)
-  float sc_a = 1.f, sc_b = 1.f;
-  if constexpr (NPL == 2) {
-    if (a_is_x && xc_a < g.ci) sc_a = h3_scale(h3_exp(ci_amax[xc_a]));
-    if (b_is_x && xc_b < g.ci) sc_b = h3_scale(h3_exp(ci_amax[xc_b]));
-    if (b_is_dy && dc_b >= 0 && dc_b < g.co) {
-      const float s = h3_scale(h3_exp(co_amax[dc_b]));
-      if (DY_IN_A) sc_a = s; else sc_b = s;
-    }
-  }
-  f32x16 acc[KW];
-#pragma unroll
-  for (int b = 0; b < KW; ++b)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
-
-  float va[8], vb[8];
-  auto slot_of = [](int xr) { return ((xr % RING) + RING) % RING; };
-
-  int row = r0;
-  while (row < r1) {
-    const int ho0 = row % g.ho, q = row / g.ho;
-    const int ch = q % nch, n = q / nch;
-    const int nrow = min(r1 - row, g.ho - ho0);              // rows of this (n, chunk) segment
-    const int c0 = ch * SWC;
-    const __amdgpu_buffer_rsrc_t drs = conv_rsrc(dy + (int64_t)n * g.co * dplane, (int64_t)g.co * dplane);
-    const __amdgpu_buffer_rsrc_t xrs = conv_rsrc(x + (int64_t)n * g.ci * xplane, (int64_t)g.ci * xplane);
-    // loads of x rows xr0 + r (r < nr; r = 0 unit a, r = 1 unit b) and, when hd >= 0, dy row hd
-    auto load = [&](int xr0, int nr, int hd) {
-      if (a_is_x) {
-        const int xr = xr0 + xr_a, cb = c0 - 8 + 8 * xj_a;
-        const bool ok = xr_a < nr && xc_a < g.ci && xr >= 0 && xr < g.hi;
-        const int vo = ok ? (xc_a * xplane + xr * g.wi + cb) * 4 : kOob;
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-          va[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                xrs, (cb + i >= 0 && cb + i < g.wi) ? vo + 4 * i : kOob, 0, 0));
-      }
-      if (b_is_x) {
-        const int xr = xr0 + 1, cb = c0 - 8 + 8 * xj_b;
-        const bool ok = nr > 1 && xc_b < g.ci && xr >= 0 && xr < g.hi;
-        const int vo = ok ? (xc_b * xplane + xr * g.wi + cb) * 4 : kOob;
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-          vb[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                xrs, (cb + i >= 0 && cb + i < g.wi) ? vo + 4 * i : kOob, 0, 0));
-      } else if (b_is_dy) {
-        // (NW = 8, 32 columns: the dy waves' unit goes in va, which they use for nothing else)
-        const int cb = c0 + 8 * dj_b;
-        const int vo = (hd >= 0 && dc_b < g.co) ? (dc_b * dplane + hd * g.wo + cb) * 4 : kOob;
-        float* vd = DY_IN_A ? va : vb;
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-          vd[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                drs, cb + i < g.wo ? vo + 4 * i : kOob, 0, 0));
-      }
-    };
-    auto store = [&](int xr0, int nr, int db) {
-      if (a_is_x && xr_a < nr)
-        cx_store8<NPL>(xs, XPL, slot_of(xr0 + xr_a) * XSL + xc_a * XP + 8 * xj_a, va, sc_a);
-      if (b_is_x) {
-        if (nr > 1) cx_store8<NPL>(xs, XPL, slot_of(xr0 + 1) * XSL + xc_b * XP + 8 * xj_b, vb, sc_b);
-      } else if (b_is_dy && db >= 0) {
-        cx_store8<NPL>(ds[db], DPL, dc_b * DP + 8 * dj_b, DY_IN_A ? va : vb, DY_IN_A ? sc_a : sc_b);
-      }
-    };
-    // segment start: every slot and dy buffer is free once all waves pass this barrier; the
-    // NW window rows of ho0 go in NW / 2 passes (the first with ho0's dy row)
-    const int xb0 = ho0 * g.sh + wtop;
-    __syncthreads();
-#pragma unroll
-    for (int p = 0; p < NW / 2; ++p) {
-      load(xb0 + 2 * p, 2, p == 0 ? ho0 : -1);
-      store(xb0 + 2 * p, 2, p == 0 ? (ho0 & 1) : -1);
-    }
-    __syncthreads();
-    for (int k = 0; k < nrow; ++k) {
-      const int ho = ho0 + k;
-      const bool more = k + 1 < nrow;
-      const int xb = ho * g.sh + wtop;                      // window row 0 of this output row
-      const int xin = xb + NW;                              // row ho + 1's incoming rows
-      if (more) load(xin, g.sh, ho + 1);
-      if (active) {
-        const unsigned short* dsb = ds[ho & 1];
-        const unsigned short* xsl = xs + slot_of(xb + wave) * XSL + fr * XP;
-        // (SWC 64: unrolled by 2, 8 VGPRs spilled, 905 us in isolation; not unrolled, 1 spilled,
-        // 943 us; fully unrolled, 10 spilled)
-#pragma unroll(SWC == 64 ? 2 : SWC / 16)
-        for (int kst = 0; kst < SWC / 16; ++kst) {
-          bf16x8 af[3];
-#pragma unroll
-          for (int pl = 0; pl < NPL; ++pl)
-            af[pl] = *reinterpret_cast<const bf16x8*>(dsb + pl * DPL + fr * DP + 16 * kst + 8 * fh);
-#pragma unroll
-          for (int pi = 0; pi < NPL; ++pi) {
-            const int pl = NPL - 1 - pi;
-            unsigned wv[12];
-#pragma unroll
-            for (int jj = 0; jj < 3; ++jj) {
-              const u32x4 qv = *reinterpret_cast<const u32x4*>(xsl + pl * XPL + 8 * (2 * kst + fh + jj));
-#pragma unroll
-              for (int e = 0; e < 4; ++e) wv[4 * jj + e] = qv[e];
-            }
-#pragma unroll
-            for (int b = 0; b < KW; ++b) {
-              const int o = b + OFF0;
-              u32x4 qb;
-#pragma unroll
-              for (int e = 0; e < 4; ++e)
-                qb[e] = (o & 1) ? __builtin_amdgcn_alignbit(wv[(o + 1) / 2 + e], wv[(o - 1) / 2 + e], 16)
-                                : wv[o / 2 + e];
-              const bf16x8 bx = __builtin_bit_cast(bf16x8, qb);
-#pragma unroll
-              for (int i = NPL - 1 - pl; i >= 0; --i) {
-                if constexpr (NPL == 2)
-                  acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(cf16x8, af[i]),
-                                                                  __builtin_bit_cast(cf16x8, bx),
-                                                                  acc[b], 0, 0, 0);
-                else
-                  acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bx, acc[b], 0, 0, 0);
-              }
-            }
-          }
-        }
-      }
-      // the incoming slots held rows xb - 2, xb - 1 (read by row ho - 1, before the last
-      // barrier); the other dy buffer likewise
-      if (more) store(xin, g.sh, (ho + 1) & 1);
-      __syncthreads();
-    }
-    row += nrow;
-  }
-  x6w_store_block<KW, NW>(partial, s, G, gi, wave, active, fr, fh, acc);
-}
-
-// ---------------------------------------------------------------------------
-// bf16x6 dgrad with 4-row x 2-column fragments (default for <= 12 class tap rows and <= 12
-// kernel columns: conv2's 11 x 11 class taps take 3 x 3 k-steps of 16 taps -- 144 tap slots
-// for 121 -- instead of the 8-row fragments' 2 x 6 -- 192).  K order of k-step (row quad rq,
-// column quad cq): lane half h takes tap rows 4 rq .. + 3 x tap columns 4 cq + 2 h, + 1
-// (element 2 r + c).  The patch is stored as column PAIRS, [pair][row][2], twice -- pairs
-// starting at even columns (E) and at odd columns (O) -- so a lane's 8 values are one 16-B run
-// whatever the parity of its first column.  Pair pitch 24 bf16 (3 x 16 B) and the O copy 128 B
-// off the E copy's bank phase: the 8 E and 8 O lanes of a b128 lane group hit 16 distinct
-// 16-B bank slots.  Workgroup, waves, weight staging and epilogue as conv_x6_kernel's dgrad.
-constexpr int CQ_ROWS = 12;                          // class tap rows, padded to 4
-constexpr int CQ_PP = 2 * CQ_ROWS;                   // bf16 per column pair
-constexpr int CQ_PAIRS = (CX_COLS + 11 + 1) / 2;     // pairs per copy (<= 12 kernel columns)
-constexpr int CQ_OFFO = 3264;                        // O copy (bf16): 6528 B = 128 mod 256
-constexpr int CQ_PPL = 6656;                         // bf16 per plane: 13312 B = 0 mod 256
-constexpr int CQ_NK = 9;                             // 3 row quads x 3 column quads
-constexpr int CQ_COP = 152;                          // weight-image ci pitch: 8 x odd >= 144
-constexpr int CQ_UNITS = 2 * CQ_PAIRS * 3;           // staging units (copy, pair, row quad)
-static_assert(CQ_OFFO >= CQ_PAIRS * CQ_PP && CQ_OFFO + CQ_PAIRS * CQ_PP <= CQ_PPL, "patch plane");
-static_assert(CQ_UNITS <= 2 * CX_T, "two staging units per thread");
-
-// pre-split weight image [class][mb][co][plane][32 ci][CQ_COP]: k-step st, half h, element e
-// (NPL 2: fp16 hi / lo planes of w 2^m_exp[ci])
-template <int NPL = 3>
-__global__ void conv_x6q_wimg_kernel(const float* __restrict__ w, ConvDims g,
-                                     unsigned short* __restrict__ img,
-                                     const int* __restrict__ m_exp, int flip_odd = 0) {
-  const int M = g.ci, L = g.co;
-  const int mbn = (M + 31) / 32;
-  const int64_t per = (int64_t)32 * CQ_COP;
-  const int64_t total = (int64_t)g.sh * mbn * L * per;
-  const int KHW = g.kh * g.kw;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    int64_t r = i;
-    const int e = static_cast<int>(r % per); r /= per;
-    const int l = static_cast<int>(r % L); r /= L;
-    const int mb = static_cast<int>(r % mbn); r /= mbn;
-    const int q = static_cast<int>(r);
-    const int mm = e / CQ_COP, slot = e - mm * CQ_COP;
-    const int m = mb * 32 + mm;
-    float v = 0.f;
-    if (slot < CQ_NK * 16 && m < M) {
-      const int st = slot >> 4, h = (slot >> 3) & 1, x = slot & 7;
-      const int a = 4 * (st / 3) + (x >> 1), b = 4 * (st % 3) + 2 * h + (x & 1);
-      const int aq = class_taps(g, q);
-      if (a < aq && b < g.kw)
-        v = w[((int64_t)l * g.ci + m) * KHW + (q + g.sh * (aq - 1 - a)) * g.kw + (g.kw - 1 - b)];
-    }
-    // the second half of the k-steps (the kk = 1 waves' share) is stored negated: see the
-    // dgrad kernel's epilogue (flip_odd: the odd loop channels instead, conv_h3_dgrad2r_kernel)
-    if (flip_odd ? (l & 1) != 0 : slot >= ((CQ_NK + 1) / 2) * 16) v = -v;
-    const float sc = NPL == 2 && m < M ? h3_scale(m_exp[m]) : 1.f;
-    cx_wimg_put<NPL>(img, ((((int64_t)q * mbn + mb) * L + l) * NPL) * per + e, per, v, sc);
-  }
-}
-
-// DB: double-buffered patch and weight chunk (2 x 69 KB of LDS) -- channel l + 1 is staged
-// into the other buffer right after the k-steps of channel l, one barrier per channel.  The
-// patch gather offsets (and their bounds) are the same for every channel and are hoisted.
-// NPL 2: fp16x3, scales as conv_x6_kernel's (e_n from the sample's max |dy|, m = ci)
-// FL (fp16x3): the big products' chain restarts every input channel (see acf below).
-// Sign split: the kk = 1 waves run on the negated weight image, so their chains hold -(their
-// half), and the epilogue subtracts.  An MFMA rounds its addends' low bits toward -inf (bits
-// below ~2^-31 of its largest operand, C included; profiles/r5n_mfma_rounding.txt), so every
-// chain drifts negative; the negated half drifts the other way in the true sum and the two
-// drifts cancel to their difference (5 vs 4 k-steps per channel) instead of adding.
-template <bool DB, int NPL = 3, bool FL = true>
-__global__ __launch_bounds__(CX_T, 1) void conv_x6q_dgrad_kernel(const float* __restrict__ dy,
-                                                                 const unsigned short* __restrict__ img,
-                                                                 float* __restrict__ dx, ConvDims g,
-                                                                 int gx, int gy,
-                                                                 const int* __restrict__ m_exp,
-                                                                 const unsigned* __restrict__ n_amax) {
-  constexpr int NB = DB ? 2 : 1;
-  constexpr int WPL = 32 * CQ_COP;
-  constexpr int wstride = NPL * WPL;
-  __shared__ __attribute__((aligned(16))) unsigned short ps[NB * NPL * CQ_PPL];
-  __shared__ __attribute__((aligned(16))) unsigned short ws[NB * wstride];
-  const int M = g.ci, L = g.co;
-  const int in_h = g.ho, in_w = g.wo, out_h = g.hi, out_w = g.wi;
-  const int mbn = (M + 31) / 32;
-  int bx, by, bz;
-  xcd_tile(gx, gy, bx, by, bz);
-  const int n = bz / mbn;
-  const int mb = bz - n * mbn;
-  const int m0 = mb * 32;
-  const int c0 = bx * CX_COLS;
-  int t = by, hq = 0, q;
-  for (q = 0; q < g.sh; ++q) {
-    hq = ((q - g.ph) % g.sh + g.sh) % g.sh;
-    const int cnt = hq < g.hi ? (g.hi - 1 - hq) / g.sh + 1 : 0;
-    if (t < cnt) break;
-    t -= cnt;
-  }
-  const int A = class_taps(g, q);
-  const int orow = hq + g.sh * t;
-  const int prow0 = (orow + g.ph - q) / g.sh - (A - 1);
-  const int pcol0 = c0 + g.pw - g.kw + 1;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int cw = wave & 3, kk = wave >> 2;
-  const int plane_in = in_h * in_w;
-  const float* inn = dy + (int64_t)n * L * plane_in;
-  const unsigned short* wimg = img + ((int64_t)q * mbn + mb) * L * wstride;
-  constexpr int wchunks = wstride / 8;
-  constexpr int WR = (wchunks + CX_T - 1) / CX_T;
-  const int en = NPL == 2 ? h3_exp(n_amax[n]) : 0;
-  const float nsc = h3_scale(en);
-
-  // per-thread gather offsets (bytes; out-of-range elements read the buffer's zero tail)
-  int goff[2][8];
-  int soff[2];
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const int unit = tid + CX_T * u;
-    const int cp = unit / (CQ_PAIRS * 3), rem = unit - cp * (CQ_PAIRS * 3);
-    const int j = rem / 3, rq = rem - (rem / 3) * 3;
-    const int col = pcol0 + 2 * j + cp;            // the pair's first column
-    soff[u] = unit < CQ_UNITS ? cp * CQ_OFFO + j * CQ_PP + 8 * rq : -1;
-#pragma unroll
-    for (int x = 0; x < 8; ++x) {
-      const int a = 4 * rq + (x >> 1), ir = prow0 + a, ic = col + (x & 1);
-      const bool ok = unit < CQ_UNITS && a < A && ir >= 0 && ir < in_h && ic >= 0 && ic < in_w;
-      goff[u][x] = ok ? (ir * in_w + ic) * 4 : 0x7ffffff0;
-    }
-  }
-
-  float rp[2][8];
-  u32x4 rw[WR];
-  auto load = [&](int l) {
-    const __amdgpu_buffer_rsrc_t rs = conv_rsrc(inn + (int64_t)l * plane_in, plane_in);
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int x = 0; x < 8; ++x)
-        rp[u][x] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, goff[u][x], 0, 0));
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<unsigned short*>(wimg + (int64_t)l * wstride), (short)0, wstride * 2, 0x00020000);
-#pragma unroll
-    for (int r = 0; r < WR; ++r) {
-      const int i = tid + CX_T * r;
-      rw[r] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                            wr, i < wchunks ? i * 16 : 0x7ffffff0, 0, 0));
-    }
-  };
-  auto store = [&](int b) {
-    unsigned short* pb = ps + b * (NPL * CQ_PPL);
-    unsigned short* wb = ws + b * wstride;
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-      if (soff[u] >= 0) cx_store8<NPL>(pb, CQ_PPL, soff[u], rp[u], nsc);
-#pragma unroll
-    for (int r = 0; r < WR; ++r) {
-      const int i = tid + CX_T * r;
-      if (i < wchunks) *reinterpret_cast<u32x4*>(wb + 8 * i) = rw[r];
-    }
-  };
-
-  // acs: fp16x3's small products (cx_mma_h3s); acf: the big products' running sum.  The
-  // big chain restarts from zero every input channel and is added into acf by the VALU
-  // (RNE): an MFMA floors the addend bits below ~2^-31 of its largest operand, C included,
-  // so a chain over all 32 channels drifted negative by ~160 x 2^-32 |C| at every position
-  // -- the drift BatchNorm1's gradients (sums of dx over 1.3 M positions per channel)
-  // collected, 5x the fp32 oracle's distance from fp64 (scripts/conv_block_stage_probe.py)
-  f32x16 acc[2], acs[2], acf[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[j][r] = acs[j][r] = acf[j][r] = 0.f;
-  const int fr = lane & 31, fh = lane >> 5;
-  const bool active = orow < out_h && c0 + 64 * cw < out_w;
-  constexpr int H0 = (CQ_NK + 1) / 2;
-
-  load(0);
-  store(0);
-  __syncthreads();
-  for (int l = 0; l < L; ++l) {
-    const int cur = DB ? (l & 1) : 0;
-    if (l + 1 < L) load(l + 1);
-    if (active) {
-      const unsigned short* pc = ps + cur * (NPL * CQ_PPL);
-      const unsigned short* wc = ws + cur * wstride;
-      auto kstep = [&](int st) {
-        const int rq = st / 3, cq = st - (st / 3) * 3;
-        bf16x8 af[3], bfr[2][3];
-        const int aw = fr * CQ_COP + (st * 2 + fh) * 8;
-#pragma unroll
-        for (int pl = 0; pl < NPL; ++pl) af[pl] = *reinterpret_cast<const bf16x8*>(wc + pl * WPL + aw);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int sc = 64 * cw + 32 * j + fr + 4 * cq + 2 * fh;   // first patch column
-          const int ap = (sc & 1) * CQ_OFFO + (sc >> 1) * CQ_PP + 8 * rq;
-#pragma unroll
-          for (int pl = 0; pl < NPL; ++pl)
-            bfr[j][pl] = *reinterpret_cast<const bf16x8*>(pc + pl * CQ_PPL + ap);
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          if constexpr (NPL == 2) cx_mma_h3s(af, bfr[j], acc[j], acs[j]);
-          else acc[j] = cx_mma<NPL>(af, bfr[j], acc[j]);
-        }
-      };
-      if (kk == 0) {
-#pragma unroll
-        for (int st = 0; st < H0; ++st) kstep(st);
-      } else {
-#pragma unroll
-        for (int st = H0; st < CQ_NK; ++st) kstep(st);
-      }
-      if constexpr (NPL == 2 && FL) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          acf[j] += acc[j];
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-        }
-      }
-    }
-    if (DB) {
-      // the other buffer was last read in channel l - 1, before the previous barrier
-      if (l + 1 < L) store(cur ^ 1);
-      __syncthreads();
-    } else {
-      __syncthreads();
-      if (l + 1 < L) {
-        store(0);
-        __syncthreads();
-      }
-    }
-  }
-  if constexpr (NPL == 2) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[j] = FL ? acf[j] + acs[j] : acc[j] + acs[j];
-  }
-  // the two k halves meet in LDS (the patch area): half 1 writes, half 0 adds (fixed order)
-  float* red = reinterpret_cast<float*>(ps);
-  if (kk == 1) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) red[((cw * 2 + j) * 16 + r) * 64 + lane] = acc[j][r];
-  }
-  __syncthreads();
-  if (kk == 1 || !active) return;
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int col = c0 + 64 * cw + 32 * j + fr;
-    if (col >= out_w) continue;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int m = m0 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-      if (m < M) {
-        float v = acc[j][r] - red[((cw * 2 + j) * 16 + r) * 64 + lane];   // sign split
-        if (NPL == 2) v = __builtin_ldexpf(v, -(m_exp[m] + en));
-        dx[(((int64_t)n * M + m) * out_h + orow) * out_w + col] = v;
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// conv2 dgrad on fp16x3, two dx rows per workgroup: rows t and t + 4 of one stride class (dx
-// rows hq + sh t) read dy rows 4 apart -- exactly one row quad of the 4 x 2 fragments -- so ONE
-// column-pair patch of 16 dy rows serves both (row t's B fragments are quads 0..2, row t + 4's
-// quads 1..3) and both multiply the SAME weight fragments.  Per loop channel a workgroup then
-// stages 16 patch rows and one weight image for two dx rows (conv_x6q_dgrad_kernel: 12 rows and
-// one image for one row).  Waves: 8 x 32 columns, all 9 k-steps of both rows.  Both MFMA chains
-// (big and small products) restart every channel and are folded into a VALU sum (RNE), so no
-// chain is longer than 9 MFMAs; and the k-half sign split becomes a split by channel parity: odd
-// channels run on the negated weight image and are subtracted, so the MFMAs' floor of low
-// addend bits drifts the even and the odd channels' terms in opposite directions.  Pair pitch 40 fp16
-// (5 x 16 B, odd) and the O copy 128 B off the E copy's bank phase keep the b128 fragment reads
-// conflict-free as in conv_x6q_dgrad_kernel.
-constexpr int C2Q_ROWS = 16;                          // patch rows: 12 class taps + one quad
-constexpr int C2Q_PP = 40;                            // fp16 per column pair
-constexpr int C2Q_OFFO = 5440;                        // O copy: 10880 B = 128 mod 256
-constexpr int C2Q_PPL = 10880;                        // fp16 per plane: 21760 B = 0 mod 256
-constexpr int C2Q_UNITS = 2 * CQ_PAIRS * (C2Q_ROWS / 4);   // (copy, pair, row quad) units
-constexpr int C2Q_PU = (C2Q_UNITS + CX_T - 1) / CX_T;
-static_assert(C2Q_OFFO >= CQ_PAIRS * C2Q_PP && C2Q_OFFO + CQ_PAIRS * C2Q_PP <= C2Q_PPL, "patch plane");
-
-__global__ __launch_bounds__(CX_T, 1) void conv_h3_dgrad2r_kernel(
-    const float* __restrict__ dy, const unsigned short* __restrict__ img, float* __restrict__ dx,
-    ConvDims g, int gx, int gy, const int* __restrict__ m_exp,
-    const unsigned* __restrict__ n_amax) {
-  constexpr int WPL = 32 * CQ_COP;
-  constexpr int wstride = 2 * WPL;
-  __shared__ __attribute__((aligned(16))) unsigned short ps[2 * 2 * C2Q_PPL];
-  __shared__ __attribute__((aligned(16))) unsigned short ws[2 * wstride];
-  const int M = g.ci, L = g.co;
-  const int in_h = g.ho, in_w = g.wo, out_h = g.hi, out_w = g.wi;
-  const int mbn = (M + 31) / 32;
-  int bx, by, bz;
-  xcd_tile(gx, gy, bx, by, bz);
-  const int n = bz / mbn;
-  const int mb = bz - n * mbn;
-  const int m0 = mb * 32;
-  const int c0 = bx * CX_COLS;
-  // (class q, row pair) of this workgroup: rows t and t + 4 with t = 8 b + j, j < 4
-  int pr = by, hq = 0, q, cnt = 0;
-  for (q = 0; q < g.sh; ++q) {
-    hq = ((q - g.ph) % g.sh + g.sh) % g.sh;
-    cnt = hq < g.hi ? (g.hi - 1 - hq) / g.sh + 1 : 0;
-    const int pairs = 4 * (cnt / 8) + min(4, cnt % 8);
-    if (pr < pairs) break;
-    pr -= pairs;
-  }
-  const int t = 8 * (pr >> 2) + (pr & 3);
-  const int A = class_taps(g, q);
-  const int orow = hq + g.sh * t;                      // and orow + 4 sh (class row t + 4)
-  const bool second = t + 4 < cnt;
-  const int prow0 = (orow + g.ph - q) / g.sh - (A - 1);
-  const int pcol0 = c0 + g.pw - g.kw + 1;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int plane_in = in_h * in_w;
-  const float* inn = dy + (int64_t)n * L * plane_in;
-  const unsigned short* wimg = img + ((int64_t)q * mbn + mb) * L * wstride;
-  constexpr int wchunks = wstride / 8;
-  constexpr int WR = (wchunks + CX_T - 1) / CX_T;
-  const int en = h3_exp(n_amax[n]);
-  const float nsc = h3_scale(en);
-
-  int goff[C2Q_PU][8];
-  int soff[C2Q_PU];
-#pragma unroll
-  for (int u = 0; u < C2Q_PU; ++u) {
-    const int unit = tid + CX_T * u;
-    const int cp = unit / (CQ_PAIRS * 4), rem = unit - cp * (CQ_PAIRS * 4);
-    const int j = rem >> 2, rq = rem & 3;
-    const int col = pcol0 + 2 * j + cp;
-    soff[u] = unit < C2Q_UNITS ? cp * C2Q_OFFO + j * C2Q_PP + 8 * rq : -1;
-#pragma unroll
-    for (int x = 0; x < 8; ++x) {
-      const int a = 4 * rq + (x >> 1), ir = prow0 + a, ic = col + (x & 1);
-      const bool ok = unit < C2Q_UNITS && a < A + 4 && ir >= 0 && ir < in_h && ic >= 0 && ic < in_w;
-      goff[u][x] = ok ? (ir * in_w + ic) * 4 : 0x7ffffff0;
-    }
-  }
-
-  float rp[C2Q_PU][8];
-  u32x4 rw[WR];
-  auto load = [&](int l) __attribute__((always_inline)) {
-    const __amdgpu_buffer_rsrc_t rs = conv_rsrc(inn + (int64_t)l * plane_in, plane_in);
-#pragma unroll
-    for (int u = 0; u < C2Q_PU; ++u)
-#pragma unroll
-      for (int x = 0; x < 8; ++x)
-        rp[u][x] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, goff[u][x], 0, 0));
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<unsigned short*>(wimg + (int64_t)l * wstride), (short)0, wstride * 2, 0x00020000);
-#pragma unroll
-    for (int r = 0; r < WR; ++r) {
-      const int i = tid + CX_T * r;
-      rw[r] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                            wr, i < wchunks ? i * 16 : 0x7ffffff0, 0, 0));
-    }
-  };
-  auto store = [&](int b) __attribute__((always_inline)) {
-    unsigned short* pb = ps + b * (2 * C2Q_PPL);
-    unsigned short* wb = ws + b * wstride;
-#pragma unroll
-    for (int u = 0; u < C2Q_PU; ++u)
-      if (soff[u] >= 0) cx_store8<2>(pb, C2Q_PPL, soff[u], rp[u], nsc);
-#pragma unroll
-    for (int r = 0; r < WR; ++r) {
-      const int i = tid + CX_T * r;
-      if (i < wchunks) *reinterpret_cast<u32x4*>(wb + 8 * i) = rw[r];
-    }
-  };
-
-  f32x16 acc[2], acs[2], acf[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[j][r] = acs[j][r] = acf[j][r] = 0.f;
-  const int fr = lane & 31, fh = lane >> 5;
-  const bool active = c0 + 32 * wave < out_w;
-
-  load(0);
-  store(0);
-  __syncthreads();
-  for (int l = 0; l < L; ++l) {
-    const int cur = l & 1;
-    if (l + 1 < L) load(l + 1);
-    if (active) {
-      const unsigned short* pc = ps + cur * (2 * C2Q_PPL);
-      const unsigned short* wc = ws + cur * wstride;
-#pragma unroll
-      for (int st = 0; st < CQ_NK; ++st) {
-        const int rq = st / 3, cq = st - (st / 3) * 3;
-        bf16x8 af[3], b0[3], b1[3];
-        const int aw = fr * CQ_COP + (st * 2 + fh) * 8;
-        const int sc = 32 * wave + fr + 4 * cq + 2 * fh;   // the lane's first patch column
-        const int ap = (sc & 1) * C2Q_OFFO + (sc >> 1) * C2Q_PP + 8 * rq;
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl) {
-          af[pl] = *reinterpret_cast<const bf16x8*>(wc + pl * WPL + aw);
-          b0[pl] = *reinterpret_cast<const bf16x8*>(pc + pl * C2Q_PPL + ap);
-          b1[pl] = *reinterpret_cast<const bf16x8*>(pc + pl * C2Q_PPL + ap + 8);
-        }
-        cx_mma_h3s(af, b0, acc[0], acs[0]);
-        cx_mma_h3s(af, b1, acc[1], acs[1]);
-      }
-      // both chains restart every channel; odd channels ran on negated weights, so their
-      // chains hold -(their sum) and drift the other way in the true sum
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        if (l & 1) acf[j] -= acc[j] + acs[j];
-        else acf[j] += acc[j] + acs[j];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[j][r] = acs[j][r] = 0.f;
-      }
-    }
-    // the other buffer was last read in channel l - 1, before the previous barrier
-    if (l + 1 < L) store(cur ^ 1);
-    __syncthreads();
-  }
-  if (!active) return;
-  const int col = c0 + 32 * wave + fr;
-  if (col >= out_w) return;
-#pragma unroll
-  for (int rr = 0; rr < 2; ++rr) {
-    if (rr == 1 && !second) continue;
-    const int row = orow + 4 * g.sh * rr;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int m = m0 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-      if (m < M) {
-        const float v = __builtin_ldexpf(acf[rr][r], -(m_exp[m] + en));
-        dx[(((int64_t)n * M + m) * out_h + row) * out_w + col] = v;
-      }
-    }
-  }
-}
-
-static inline bool make_dims(ConvDims& g, int n, int c_in, int h_in, int w_in, int c_out, int kh,
-                             int kw, int sh, int sw, int ph, int pw) {
-  if (n < 0 || c_in < 1 || h_in < 1 || w_in < 1 || c_out < 1 || kh < 1 || kw < 1 || sh < 1 ||
-      sw < 1 || ph < 0 || pw < 0)
-    return false;
-  g = ConvDims{n, c_in, h_in, w_in, c_out, kh, kw, sh, sw, ph, pw, 0, 0};
-  g.ho = (h_in + 2 * ph - kh) / sh + 1;
-  g.wo = (w_in + 2 * pw - kw) / sw + 1;
-  return g.ho >= 1 && g.wo >= 1;
-}
-
-// the LDS-patch kernel covers width stride 1 with patches / tap tiles that fit its LDS
-static inline bool patch_ok(const ConvDims& g, bool dgrad) {
-  if (g.sw != 1 || g.kw < 2 || g.kw > PT_PITCH - PT_COLS + 1) return false;
-  const int a = dgrad ? (g.kh + g.sh - 1) / g.sh : g.kh;
-  const int rows = (PT_ROWS - 1) * (dgrad ? 1 : g.sh) + a + 1;
-  const int taps = ((a * g.kw) + 1) & ~1;
-  const int64_t plane = dgrad ? (int64_t)g.ho * g.wo : (int64_t)g.hi * g.wi;
-  return rows <= PT_PROWS && taps <= PT_TMAX && plane * 4 < (1ll << 31) - 64;
-}
 
 static int conv_cus() {
   static int cus = -1;
@@ -2718,333 +992,22 @@ static int conv_cus() {
   return cus;
 }
 
-// the single-channel patch forward (conv1_patch_fwd_kernel): one input channel, <= 32 output
-// channels, 3 <= kw <= 12, a patch and filter bank that fit its LDS, input planes within 32-bit
-// offsets (other shapes: the implicit-GEMM kernel)
-static inline bool c1_ok(const ConvDims& g) {
-  if (g.ci != 1 || g.co > 32 || g.kw < 3 || g.kw > 12) return false;
-  const int kw2 = (g.kw + 1) & ~1;
-  const int64_t pe = (int64_t)((C1_RW - 1) * g.sh + g.kh) * ((C1_WC - 1) * g.sw + kw2);
-  return pe <= C1_PATCH && g.kh * kw2 <= C1_KROWS;
-}
-
-static size_t patch_ws_bytes(const ConvDims& g, bool dgrad) {
-  if (!patch_ok(g, dgrad)) return 0;
-  const int M = dgrad ? g.ci : g.co;
-  const int L = dgrad ? g.co : g.ci;
-  const int classes = dgrad ? g.sh : 1;
-  return (size_t)classes * ((M + 31) / 32) * L * wimg_tile(wimg_tstride(g, dgrad)) * sizeof(float);
-}
-
-// the bf16x6 kernel covers width stride 1 with <= 12 kernel columns and <= 24 tap rows (one
-// chunk), patches and weight chunks that fit its LDS and planes that fit 32-bit buffer
-// offsets (DS2_CONV_X6=0 selects the fp32 patch kernels).  conv1 (stride 2, 41 tap rows)
-// stays on the fp32 LDS-patch kernels: a bf16x6 form of it (removed in round 4) moved
-// hardtanh inputs of the tiny golden batch across the kink.
-static inline bool x6_on() {
-  const char* e = getenv("DS2_CONV_X6");
-  return !(e != nullptr && e[0] == '0');
-}
-static inline bool x6_ok(const ConvDims& g, bool dgrad) {
-  if (!x6_on()) return false;
-  if (g.sw != 1 || g.kw < 1 || g.kw > 12) return false;
-  const CxGeom c = cx_geom(g, dgrad);
-  if (c.RC > 1) return false;
-  if (c.KA > 24 || 3 * c.PCOL * c.P > CX_PATCH || 3 * 32 * c.COP > CX_WIMG) return false;
-  if (c.PCOL * (c.KA / 8) > CX_PU * CX_T || 3 * 32 * c.COP / 8 > CX_WQ * CX_T) return false;
-  const int64_t plane = dgrad ? (int64_t)g.ho * g.wo : (int64_t)g.hi * g.wi;
-  return plane * 4 < (1ll << 31) - 64;
-}
-
-// the 4 x 2-fragment dgrad (conv_x6q_dgrad_kernel): width stride 1, <= 12 class tap rows and
-// <= 12 kernel columns (other shapes: the 8-row-fragment conv_x6_kernel dgrad)
-static inline bool x6q_ok(const ConvDims& g) {
-  if (!x6_on()) return false;
-  if (g.sw != 1 || g.kw < 1 || g.kw > 12 || class_taps(g, 0) > CQ_ROWS) return false;
-  const int64_t plane = (int64_t)g.ho * g.wo;
-  const int64_t wimg = (int64_t)g.co * 3 * 32 * CQ_COP * 2;
-  return plane * 4 < (1ll << 31) - 64 && wimg < (1ll << 31) - 64;
-}
-
-// fp16x3 for the conv2-shaped bf16x6 kernels (the double-buffered forward and the 4 x 2
-// dgrad; DS2_CONV_H3=0 keeps bf16x6): two fp16 planes per image / patch instead of three bf16,
-// three MFMAs per fragment pair instead of six, and per-row power-of-two scales
-static inline bool h3c_on() {
-  const char* e = getenv("DS2_CONV_H3");
-  return !(e != nullptr && e[0] == '0');
-}
-// DS2_CONV_2R=0 keeps conv2's fp16x3 forward on one output row per workgroup (conv_x6_kernel)
-static inline bool c2r_on() {
-  const char* e = getenv("DS2_CONV_2R");
-  return !(e != nullptr && e[0] == '0');
-}
-
-
-// workspace of a split-weight image of `elems` values per plane: NPL 3 planes, or 2 planes +
-// the fp16x3 scales (m_exp[M] int, n_amax[n] unsigned) at the next 256-B boundary
-static size_t cx_ws_bytes(int64_t elems, int M, int n) {
-  const size_t x6 = (size_t)elems * 3 * sizeof(unsigned short);
-  const size_t h3 = ((size_t)elems * 2 * sizeof(unsigned short) + 255) / 256 * 256 +
-                    ((size_t)M + (size_t)n) * 4;
-  return x6 > h3 ? x6 : h3;
-}
-
-// the fp16x3 scales: m_exp (per output row m of the implicit GEMM) and n_amax (per sample of the
-// staged input `in`, [n][L][plane_in])
 template <bool DGRAD>
-static void cx_h3_scales(const float* in, const float* w, const ConvDims& g, int64_t elems,
-                         void* ws, int*& m_exp, unsigned*& n_amax, hipStream_t st) {
-  const int M = DGRAD ? g.ci : g.co;
-  const int L = DGRAD ? g.co : g.ci;
-  const int64_t per = (int64_t)L * (DGRAD ? (int64_t)g.ho * g.wo : (int64_t)g.hi * g.wi);
-  char* base = static_cast<char*>(ws) + ((size_t)elems * 2 * sizeof(unsigned short) + 255) / 256 * 256;
-  m_exp = reinterpret_cast<int*>(base);
-  n_amax = reinterpret_cast<unsigned*>(base + (size_t)M * 4);
-  hipLaunchKernelGGL(conv_h3_wexp_kernel<DGRAD>, dim3(M), dim3(256), 0, st, w, g, m_exp);
-  (void)hipMemsetAsync(n_amax, 0, (size_t)g.n * 4, st);
-  int64_t chunks = cdiv(per, 8192);
-  const int64_t cap = cdiv(2048, g.n);
-  chunks = chunks < 1 ? 1 : (chunks > cap ? cap : chunks);
-  hipLaunchKernelGGL(conv_h3_samax_kernel, dim3(static_cast<unsigned>(chunks), g.n), dim3(256), 0, st,
-                     in, per, n_amax);
-}
-
-static int64_t x6q_img_elems(const ConvDims& g) {
-  return (int64_t)g.sh * ((g.ci + 31) / 32) * g.co * 32 * CQ_COP;
-}
-
-static size_t x6q_ws_bytes(const ConvDims& g) {
-  if (!x6q_ok(g)) return 0;
-  return cx_ws_bytes(x6q_img_elems(g), g.ci, g.n);
-}
-
-static ds2_status_t launch_x6q(const float* dy, const float* w, float* dx, const ConvDims& g,
-                               void* ws, hipStream_t st) {
-  unsigned short* img = static_cast<unsigned short*>(ws);
-  const int64_t total = x6q_img_elems(g);
-  const int wgrid = cdiv(total, 256) > 2048 ? 2048 : cdiv(total, 256);
-  const int gx = cdiv(g.wi, CX_COLS);
-  const int64_t nwg = (int64_t)gx * g.hi * g.n * cdiv(g.ci, 32);
-  if (nwg > 0x7fffffff) return DS2_UNSUPPORTED_SHAPE;
-  if (h3c_on()) {
-    int* m_exp;
-    unsigned* n_amax;
-    cx_h3_scales<true>(dy, w, g, total, ws, m_exp, n_amax, st);
-    if (c2r_on()) {
-      // two dx rows per workgroup (conv_h3_dgrad2r_kernel)
-      hipLaunchKernelGGL(conv_x6q_wimg_kernel<2>, dim3(wgrid), dim3(256), 0, st, w, g, img, m_exp, 1);
-      int pairs = 0;
-      for (int q = 0; q < g.sh; ++q) {
-        const int hq = ((q - g.ph) % g.sh + g.sh) % g.sh;
-        const int cnt = hq < g.hi ? (g.hi - 1 - hq) / g.sh + 1 : 0;
-        pairs += 4 * (cnt / 8) + std::min(4, cnt % 8);
-      }
-      const int64_t nwg2 = (int64_t)gx * pairs * g.n * cdiv(g.ci, 32);
-      hipLaunchKernelGGL(conv_h3_dgrad2r_kernel, dim3(static_cast<unsigned>(nwg2)), dim3(CX_T), 0, st,
-                         dy, img, dx, g, gx, pairs, m_exp, n_amax);
-      return launch_status("ds2_conv2d_dgrad");
-    }
-    hipLaunchKernelGGL(conv_x6q_wimg_kernel<2>, dim3(wgrid), dim3(256), 0, st, w, g, img, m_exp);
-    static const bool flush = !(getenv("DS2_CONV_DG_FLUSH") && atoi(getenv("DS2_CONV_DG_FLUSH")) == 0);
-    if (flush)
-      hipLaunchKernelGGL((conv_x6q_dgrad_kernel<true, 2, true>), dim3(static_cast<unsigned>(nwg)),
-                         dim3(CX_T), 0, st, dy, img, dx, g, gx, g.hi, m_exp, n_amax);
-    else
-      hipLaunchKernelGGL((conv_x6q_dgrad_kernel<true, 2, false>), dim3(static_cast<unsigned>(nwg)),
-                         dim3(CX_T), 0, st, dy, img, dx, g, gx, g.hi, m_exp, n_amax);
-  } else {
-    hipLaunchKernelGGL(conv_x6q_wimg_kernel<3>, dim3(wgrid), dim3(256), 0, st, w, g, img, nullptr);
-    hipLaunchKernelGGL((conv_x6q_dgrad_kernel<true, 3>), dim3(static_cast<unsigned>(nwg)), dim3(CX_T),
-                       0, st, dy, img, dx, g, gx, g.hi, nullptr, nullptr);
-  }
-  return launch_status("ds2_conv2d_dgrad");
-}
-
-static int64_t x6_img_elems(const ConvDims& g, bool dgrad) {
-  const CxGeom c = cx_geom(g, dgrad);
-  const int M = dgrad ? g.ci : g.co;
-  const int L = dgrad ? g.co : g.ci;
-  const int classes = dgrad ? g.sh : 1;
-  return (int64_t)classes * ((M + 31) / 32) * L * c.RC * 32 * c.COP;
-}
-
-static size_t x6_ws_bytes(const ConvDims& g, bool dgrad) {
-  if (!x6_ok(g, dgrad)) return 0;
-  return cx_ws_bytes(x6_img_elems(g, dgrad), dgrad ? g.ci : g.co, g.n);
-}
-
-template <bool DGRAD>
-static ds2_status_t launch_x6(const float* in, const float* w, const float* bias, float* out,
-                              const ConvDims& g, const int* out_lens, void* ws, hipStream_t st) {
-  const CxGeom c = cx_geom(g, DGRAD);
-  unsigned short* img = static_cast<unsigned short*>(ws);
-  const int64_t total = x6_img_elems(g, DGRAD);   // elements of one plane
-  const int wgrid = cdiv(total, 256) > 2048 ? 2048 : cdiv(total, 256);
-  const int M = DGRAD ? g.ci : g.co;
-  const int gy = DGRAD ? g.hi : g.ho;
-  const int gx = cdiv(DGRAD ? g.wi : g.wo, CX_COLS);
-  const int64_t nwg = (int64_t)gx * gy * g.n * cdiv(M, 32);
-  if (nwg > 0x7fffffff) return DS2_UNSUPPORTED_SHAPE;
-  const dim3 grid(static_cast<unsigned>(nwg));
-  const int nga = c.KA / 8;
-  bool small = g.sw == 1 && c.RC == 1 && 3 * c.PCOL * c.P <= CX_PATCH1 && c.PCOL * nga <= 2 * CX_T;
-#define DS2_CX(NG, NB, PU, SW, RCH)                                                          \
-  hipLaunchKernelGGL((conv_x6_kernel<DGRAD, NG, NB, PU, SW, RCH>), grid, dim3(CX_T), 0, st, in, \
-                     img, bias, out, g, out_lens, c, gx, gy, nullptr, nullptr)
-  // the compile-time-geometry instantiations must see the geometry cx_geom computed
-  const bool c36 = c.KA == CxConst<3, 6>::KA && c.P == CxConst<3, 6>::P &&
-                   c.COP == CxConst<3, 6>::COP && c.PCOL == CxConst<3, 6>::PCOL && c.NBP == 6;
-  const bool c26 = c.KA == CxConst<2, 6>::KA && c.P == CxConst<2, 6>::P &&
-                   c.COP == CxConst<2, 6>::COP && c.PCOL == CxConst<2, 6>::PCOL && c.NBP == 6;
-  small = small && (DGRAD ? c26 : c36);
-  const bool db = small && 2 * 3 * c.PCOL * c.P <= CX_PATCH_DB;
-  const bool conv2f = small && !DGRAD && nga == 3 && c.NBP == 6 && db;
-  if (conv2f && h3c_on()) {                              // conv2 fwd, fp16x3
-    int* m_exp;
-    unsigned* n_amax;
-    cx_h3_scales<DGRAD>(in, w, g, total, ws, m_exp, n_amax, st);
-    // two output rows per workgroup where the height stride is 2 (conv_h3_fwd2r_kernel)
-    if (!DGRAD && g.sh == 2 && c.RC == 1 && c2r_on()) {
-      hipLaunchKernelGGL((conv_x6_wimg_kernel<DGRAD, 2>), dim3(wgrid), dim3(256), 0, st, w, g, c, img,
-                         m_exp, DS2_C2R_MODE == 0 ? 2 : 1);
-      const int pairs = 4 * (g.ho / 8) + std::min(4, g.ho % 8);
-      const int64_t nwg2 = (int64_t)gx * pairs * g.n * cdiv(M, 32);
-      hipLaunchKernelGGL(conv_h3_fwd2r_kernel, dim3(static_cast<unsigned>(nwg2)), dim3(CX_T), 0, st,
-                         in, img, bias, out, g, out_lens, gx, pairs, m_exp, n_amax);
-      return launch_status("ds2_conv2d_fwd");
-    }
-    hipLaunchKernelGGL((conv_x6_wimg_kernel<DGRAD, 2>), dim3(wgrid), dim3(256), 0, st, w, g, c, img, m_exp);
-    hipLaunchKernelGGL((conv_x6_kernel<DGRAD, 3, 6, 2, 1, false, true, 2>), grid, dim3(CX_T), 0, st,
-                       in, img, bias, out, g, out_lens, c, gx, gy, m_exp, n_amax);
-    return launch_status("ds2_conv2d_fwd");
-  }
-  hipLaunchKernelGGL((conv_x6_wimg_kernel<DGRAD, 3>), dim3(wgrid), dim3(256), 0, st, w, g, c, img, nullptr);
-  if (conv2f)
-    hipLaunchKernelGGL((conv_x6_kernel<DGRAD, 3, 6, 2, 1, false, true>), grid, dim3(CX_T), 0, st,
-                       in, img, bias, out, g, out_lens, c, gx, gy, nullptr, nullptr);   // conv2 fwd, double-buffered
-  else if (small && !DGRAD && nga == 3 && c.NBP == 6)
-    DS2_CX(3, 6, 2, 1, false);                           // conv2 fwd
-  else if (small && DGRAD && nga == 2 && c.NBP == 6)
-    DS2_CX(2, 6, 2, 1, false);                           // conv2 dgrad (8-row fragments)
-  else
-    DS2_CX(0, 0, 3, 0, true);
-#undef DS2_CX
-  return launch_status(DGRAD ? "ds2_conv2d_dgrad" : "ds2_conv2d_fwd");
-}
-
-template <bool DGRAD>
-static ds2_status_t launch_patch(const float* in, const float* w, const float* bias, float* out,
-                                 const ConvDims& g, const int* out_lens, void* ws, hipStream_t st) {
-  const int tstride = wimg_tstride(g, DGRAD);
+static ds2_status_t launch_patch(const ConvPlan& p, const ConvDims& g, const float* in,
+                                 const float* w, const float* bias, float* out,
+                                 const int* out_lens, void* ws, hipStream_t st) {
   float* img = static_cast<float*>(ws);
-  const int64_t total = (int64_t)patch_ws_bytes(g, DGRAD) / sizeof(float);
-  hipLaunchKernelGGL(conv_wimg_kernel<DGRAD>, dim3(cdiv(total, 256) > 2048 ? 2048 : cdiv(total, 256)),
-                     dim3(256), 0, st, w, g, tstride, img);
-  int ty = 0;
-  if (!DGRAD) {
-    ty = cdiv(g.ho, PT_ROWS);
-  } else {
-    for (int q = 0; q < g.sh; ++q) {
-      const int hq = ((q - g.ph) % g.sh + g.sh) % g.sh;
-      const int cnt = hq < g.hi ? (g.hi - 1 - hq) / g.sh + 1 : 0;
-      ty += cdiv(cnt, PT_ROWS);
-    }
-  }
-  const int M = DGRAD ? g.ci : g.co;
-  const int gx = cdiv(DGRAD ? g.wi : g.wo, PT_COLS);
-  const int64_t nwg = (int64_t)gx * ty * g.n * cdiv(M, 32);
-  if (nwg > 0x7fffffff) return DS2_UNSUPPORTED_SHAPE;
-  hipLaunchKernelGGL(conv_patch_kernel<DGRAD>, dim3(static_cast<unsigned>(nwg)), dim3(256), 0, st,
-                     in, img, bias, out, g, out_lens, tstride, gx, ty);
+  hipLaunchKernelGGL(conv_wimg_kernel<DGRAD>, dim3(std::min(cdiv(p.img, 256), 2048)), dim3(256), 0,
+                     st, w, g, p.tstride, img);
+  hipLaunchKernelGGL(conv_patch_kernel<DGRAD>, dim3(static_cast<unsigned>(p.grid)), dim3(256), 0, st,
+                     in, img, bias, out, g, out_lens, p.tstride, p.gx, p.gy);
   return launch_status(DGRAD ? "ds2_conv2d_dgrad" : "ds2_conv2d_fwd");
 }
 
-constexpr int WG_XS_SMALL = 3200;    // x patch floats, <= 8 tap tiles (conv2: 23 x 139)
-constexpr int WG_XS_LARGE = 11520;   // x patch floats, <= 16 tap tiles (conv1: 43 x 267)
-
-struct WgradPlan {
-  int nt;        // tap tiles per wave (0: use the implicit-GEMM kernel)
-  int bands;     // output-row bands per (n, ci): more workgroups, more partial slabs
-  int xpitch;    // x patch row pitch (== 11 mod 32 spreads the 3 tap rows of a tile over banks)
-};
-
-static inline WgradPlan wgrad_plan(const ConvDims& g) {
-  WgradPlan pl{0, 1, 0};
-  if (g.sw > 2) return pl;                 // kernels instantiated for width stride 1 and 2
-  const int T = g.kh * g.kw;
-  const int prow = (WG_RW - 1) * g.sh + g.kh;
-  const int pcol = (WG_CW - 1) * g.sw + g.kw;
-  int pitch = pcol + ((11 - pcol % 32) + 32) % 32;
-  const int64_t dplane = (int64_t)g.ho * g.wo, xplane = (int64_t)g.hi * g.wi;
-  if (32 * dplane * 4 >= (1ll << 31) - 64 || xplane * 4 >= (1ll << 31) - 64) return pl;
-  if (T <= 8 * 32 && prow * pitch <= WG_XS_SMALL) {
-    pl.nt = 2;
-  } else if (T <= 16 * 32 && prow * pitch <= WG_XS_LARGE) {
-    pl.nt = 4;
-  } else {
-    return pl;
-  }
-  pl.xpitch = pitch;
-  // one round of equal workgroups: 2 per CU (80 KB of LDS each at NT 4) x 256 CUs; the
-  // bands split each sample's chunk list evenly (conv1: 32 x 16 bands of 10-11 chunks)
-  const int64_t wgs = (int64_t)g.n * g.ci * ((g.co + 31) / 32);
-  const int nck = ((g.ho + WG_RW - 1) / WG_RW) * ((g.wo + WG_CW - 1) / WG_CW);
-  int bands = static_cast<int>((512 + wgs / 2) / wgs);
-  pl.bands = bands < 1 ? 1 : (bands > nck ? nck : bands);
-  return pl;
-}
-
-// the bf16x6 weight-gradient kernel: width stride 1, the instantiated kernel columns (kw 11,
-// pw 5), <= 32 channels each side, channel stacks that fit 32-bit buffer offsets
-static inline bool x6w_ok(const ConvDims& g) {
-  if (!x6_on()) return false;
-  if (g.sw != 1 || g.kw != 11 || g.pw != 5 || g.ci > 32 || g.co > 32) return false;
-  const int64_t lim = (1ll << 31) - 64;
-  return (int64_t)g.co * g.ho * g.wo * 4 < lim && (int64_t)g.ci * g.hi * g.wi * 4 < lim;
-}
-
-// the sliding-window wgrad (conv_x6_wgrad_sw_kernel) for row strides <= 2, the per-row
-// re-staging form (conv_x6_wgrad_kernel) otherwise
-static inline bool x6w_sw(const ConvDims& g) {
-  const int64_t R = (int64_t)g.n * ((g.wo + SW_COLS - 1) / SW_COLS) * g.ho;
-  return g.sh <= 2 && R < (1ll << 31) - 1;
-}
-
-// tap rows per group: 8 for the sliding-window form (one workgroup per CU), 4 otherwise
-static inline int x6w_nw(const ConvDims& g) { return x6w_sw(g) ? 8 : 4; }
-
-// the sliding-window wgrad on fp16x3 (default; DS2_CONV_H3W=0 keeps bf16x6)
-static inline bool h3w_on() {
-  const char* e = getenv("DS2_CONV_H3W");
-  return !(e != nullptr && e[0] == '0');
-}
-
-// DS2_CONV_W64=1: the fp16x3 sliding-window wgrad on 64-column row stages (read per call).
-// Opt-in: 0.70 GB of HBM per launch against 0.93 GB (PMC, FETCH_SIZE x 2 + WRITE_SIZE), but
-// 905 vs 860-880 us at the model's conv2 shape (scripts/bench_conv2_wgrad.py): the second
-// staging unit per thread pushes it past 256 VGPRs (8 spilled)
-static inline bool w64_on() {
-  const char* e = getenv("DS2_CONV_W64");
-  return e != nullptr && e[0] == '1';
-}
-
-static inline int x6w_splits(const ConvDims& g);
-// bytes of the x6 wgrad partial blocks (the fp16x3 channel maxima follow, 256-B aligned)
-static inline size_t x6w_part_bytes(const ConvDims& g) {
-  const int nw = x6w_nw(g);
-  const size_t b = (size_t)x6w_splits(g) * ((g.kh + nw - 1) / nw) * (X6W_BLOCK / 4 * nw) * g.kw *
-                   sizeof(float);
-  return (b + 255) / 256 * 256;
-}
-
-static inline int x6w_splits(const ConvDims& g) {
-  const int nw = x6w_nw(g);
-  const int G = (g.kh + nw - 1) / nw;
-  const int64_t R = x6w_sw(g) ? (int64_t)g.n * ((g.wo + SW_COLS - 1) / SW_COLS) * g.ho
-                              : (int64_t)g.n * g.ho;
-  int64_t S = (nw == 8 ? CW_SLOTS / 2 : CW_SLOTS) / G;
-  if (S < 1) S = 1;
-  return static_cast<int>(S > R ? R : S);
+// the caller's workspace covers the plan; the one-row grid fits a launch
+static inline ds2_status_t plan_fits(const ConvPlan& p, const void* ws, size_t ws_bytes) {
+  if (p.ws_bytes > 0 && (ws == nullptr || ws_bytes < p.ws_bytes)) return DS2_WORKSPACE_TOO_SMALL;
+  return p.too_big ? DS2_UNSUPPORTED_SHAPE : DS2_OK;
 }
 
 }  // namespace ds2
@@ -3057,11 +1020,7 @@ size_t ds2_conv2d_workspace_size(int n, int c_in, int h_in, int w_in, int c_out,
                                  int sh, int sw, int ph, int pw) {
   ConvDims g;
   if (!make_dims(g, n, c_in, h_in, w_in, c_out, kh, kw, sh, sw, ph, pw)) return 0;
-  size_t a = patch_ws_bytes(g, false), b = patch_ws_bytes(g, true);
-  a = a > x6_ws_bytes(g, false) ? a : x6_ws_bytes(g, false);
-  b = b > x6_ws_bytes(g, true) ? b : x6_ws_bytes(g, true);
-  b = b > x6q_ws_bytes(g) ? b : x6q_ws_bytes(g);
-  return (a > b ? a : b) + 256;
+  return conv_ws_max(g, conv_switches());
 }
 
 ds2_status_t ds2_conv2d_fwd(const float* x, const float* w, const float* bias, float* y, int n,
@@ -3072,37 +1031,30 @@ ds2_status_t ds2_conv2d_fwd(const float* x, const float* w, const float* bias, f
   if (!make_dims(g, n, c_in, h_in, w_in, c_out, kh, kw, sh, sw, ph, pw)) return DS2_INVALID_VALUE;
   if (n == 0) return DS2_OK;
   if (g.ho > 65535) return DS2_UNSUPPORTED_SHAPE;
-  if (x6_ok(g, false)) {
-    if (ws == nullptr || ws_bytes < x6_ws_bytes(g, false)) return DS2_WORKSPACE_TOO_SMALL;
-    return launch_x6<false>(x, w, bias, y, g, out_lens, ws, as_stream(stream));
-  }
-  if (patch_ok(g, false)) {
-    if (ws == nullptr || ws_bytes < patch_ws_bytes(g, false)) return DS2_WORKSPACE_TOO_SMALL;
-    return launch_patch<false>(x, w, bias, y, g, out_lens, ws, as_stream(stream));
-  }
-  if (c1_ok(g)) {
-    const int gx = cdiv(g.wo, C1_WC), gy = cdiv(g.ho, C1_RW);
-    const int64_t tiles = (int64_t)gx * gy * n;
-    if (tiles > 0x7fffffff) return DS2_UNSUPPORTED_SHAPE;
-    const int grid = static_cast<int>(std::min<int64_t>(tiles, conv_cus()));   // one per CU
-    const int tl = static_cast<int>(tiles);
-#define DS2_C1(KWH)                                                                          \
-  hipLaunchKernelGGL(conv1_patch_fwd_kernel<KWH>, dim3(grid), dim3(C1_T), 0, as_stream(stream), \
-                     x, w, bias, y, g, out_lens, gx, gy, tl)
-    switch ((g.kw + 1) / 2) {
-      case 6: DS2_C1(6); break;
-      case 5: DS2_C1(5); break;
-      case 4: DS2_C1(4); break;
-      case 3: DS2_C1(3); break;
-      default: DS2_C1(2); break;
+  const ConvPlan p = conv_plan_fwd(g, conv_switches());
+  const ds2_status_t fits = plan_fits(p, ws, ws_bytes);
+  if (fits != DS2_OK) return fits;
+  hipStream_t st = as_stream(stream);
+  switch (p.rung) {
+    case DS2_CONV_FWD_PATCH:
+      return launch_patch<false>(p, g, x, w, bias, y, out_lens, ws, st);
+    case DS2_CONV_FWD_C1: {
+      const int grid = static_cast<int>(std::min<int64_t>(p.grid, conv_cus()));   // one per CU
+      const auto k = p.a == 6 ? conv1_patch_fwd_kernel<6> : p.a == 5 ? conv1_patch_fwd_kernel<5>
+                   : p.a == 4 ? conv1_patch_fwd_kernel<4> : p.a == 3 ? conv1_patch_fwd_kernel<3>
+                                                                      : conv1_patch_fwd_kernel<2>;
+      hipLaunchKernelGGL(k, dim3(grid), dim3(C1_T), 0, st, x, w, bias, y, g, out_lens, p.gx, p.gy,
+                         static_cast<int>(p.grid));
+      return launch_status("ds2_conv2d_fwd");
     }
-#undef DS2_C1
-    return launch_status("ds2_conv2d_fwd");
+    case DS2_CONV_FWD_GEMM: {
+      dim3 grid(cdiv(g.wo, CBN), g.ho, n * cdiv(c_out, 32));
+      hipLaunchKernelGGL(conv_fwd_kernel, grid, dim3(256), 0, st, x, w, bias, y, g, out_lens);
+      return launch_status("ds2_conv2d_fwd");
+    }
+    default:
+      return launch_conv_split(p, g, x, w, bias, y, out_lens, ws, st);
   }
-  dim3 grid(cdiv(g.wo, CBN), g.ho, n * cdiv(c_out, 32));
-  hipLaunchKernelGGL(conv_fwd_kernel, grid, dim3(256), 0, as_stream(stream), x, w, bias, y, g,
-                     out_lens);
-  return launch_status("ds2_conv2d_fwd");
 }
 
 ds2_status_t ds2_conv2d_dgrad(const float* dy, const float* w, float* dx, int n, int c_in,
@@ -3111,31 +1063,28 @@ ds2_status_t ds2_conv2d_dgrad(const float* dy, const float* w, float* dx, int n,
   ConvDims g;
   if (!make_dims(g, n, c_in, h_in, w_in, c_out, kh, kw, sh, sw, ph, pw)) return DS2_INVALID_VALUE;
   if (n == 0) return DS2_OK;
-  if (x6q_ok(g)) {
-    if (ws == nullptr || ws_bytes < x6q_ws_bytes(g)) return DS2_WORKSPACE_TOO_SMALL;
-    return launch_x6q(dy, w, dx, g, ws, as_stream(stream));
+  const ConvPlan p = conv_plan_dgrad(g, conv_switches());
+  const ds2_status_t fits = plan_fits(p, ws, ws_bytes);
+  if (fits != DS2_OK) return fits;
+  hipStream_t st = as_stream(stream);
+  switch (p.rung) {
+    case DS2_CONV_DG_PATCH:
+      return launch_patch<true>(p, g, dy, w, nullptr, dx, nullptr, ws, st);
+    case DS2_CONV_DG_GEMM: {
+      dim3 grid(cdiv(w_in, CBN), h_in, n * cdiv(c_in, 32));
+      hipLaunchKernelGGL(conv_dgrad_kernel, grid, dim3(256), 0, st, dy, w, dx, g);
+      return launch_status("ds2_conv2d_dgrad");
+    }
+    default:
+      return launch_conv_split(p, g, dy, w, nullptr, dx, nullptr, ws, st);
   }
-  if (x6_ok(g, true)) {
-    if (ws == nullptr || ws_bytes < x6_ws_bytes(g, true)) return DS2_WORKSPACE_TOO_SMALL;
-    return launch_x6<true>(dy, w, nullptr, dx, g, nullptr, ws, as_stream(stream));
-  }
-  if (patch_ok(g, true)) {
-    if (ws == nullptr || ws_bytes < patch_ws_bytes(g, true)) return DS2_WORKSPACE_TOO_SMALL;
-    return launch_patch<true>(dy, w, nullptr, dx, g, nullptr, ws, as_stream(stream));
-  }
-  dim3 grid(cdiv(w_in, CBN), h_in, n * cdiv(c_in, 32));
-  hipLaunchKernelGGL(conv_dgrad_kernel, grid, dim3(256), 0, as_stream(stream), dy, w, dx, g);
-  return launch_status("ds2_conv2d_dgrad");
 }
 
 size_t ds2_conv2d_wgrad_workspace_size(int n, int c_in, int h_in, int w_in, int c_out, int kh,
                                        int kw, int sh, int sw, int ph, int pw) {
   ConvDims g;
   if (!make_dims(g, n, c_in, h_in, w_in, c_out, kh, kw, sh, sw, ph, pw)) return 0;
-  const size_t per = (size_t)c_out * c_in * kh * kw * sizeof(float);
-  if (x6w_ok(g)) return x6w_part_bytes(g) + ((size_t)c_out + c_in) * 4 + 512;
-  const WgradPlan pl = wgrad_plan(g);
-  return (size_t)n * (pl.nt > 0 ? pl.bands : 1) * per + 256;
+  return conv_plan_wgrad(g, conv_switches()).ws_bytes;
 }
 
 ds2_status_t ds2_conv2d_wgrad(const float* dy, const float* x, float* dw, float* dbias, int n,
@@ -3145,77 +1094,59 @@ ds2_status_t ds2_conv2d_wgrad(const float* dy, const float* x, float* dw, float*
   ConvDims g;
   if (!make_dims(g, n, c_in, h_in, w_in, c_out, kh, kw, sh, sw, ph, pw)) return DS2_INVALID_VALUE;
   if (n == 0) return DS2_OK;
-  if (ws == nullptr ||
-      ws_bytes < ds2_conv2d_wgrad_workspace_size(n, c_in, h_in, w_in, c_out, kh, kw, sh, sw, ph, pw))
-    return DS2_WORKSPACE_TOO_SMALL;
+  const ConvPlan p = conv_plan_wgrad(g, conv_switches());
+  if (ws == nullptr || ws_bytes < p.ws_bytes) return DS2_WORKSPACE_TOO_SMALL;
   hipStream_t st = as_stream(stream);
-  const int Kc = c_in * kh * kw;
   float* partial = static_cast<float*>(ws);
-  const WgradPlan pl = wgrad_plan(g);
+  const int64_t per = (int64_t)c_out * c_in * kh * kw;
   int slabs = n;
-  unsigned* co_am = nullptr;   // fp16x3 channel maxima (the sliding-window wgrad)
-  unsigned* ci_am = nullptr;
-  if (x6w_ok(g)) {
-    slabs = x6w_splits(g);
-    const int nw = x6w_nw(g);
-    const int G = (kh + nw - 1) / nw;
-    if (x6w_sw(g) && h3w_on()) {
-      co_am = reinterpret_cast<unsigned*>(static_cast<char*>(ws) + x6w_part_bytes(g));
-      ci_am = co_am + c_out;
-      if (hipMemsetAsync(co_am, 0, ((size_t)c_out + c_in) * 4, st) != hipSuccess)
-        return launch_status("ds2_conv2d_wgrad");
-      const int64_t dpl = (int64_t)g.ho * g.wo, xpl = (int64_t)g.hi * g.wi;
-      const int cd = static_cast<int>(std::min<int64_t>(64, cdiv((int64_t)n * dpl, 16384)));
-      const int cx = static_cast<int>(std::min<int64_t>(64, cdiv((int64_t)n * xpl, 16384)));
-      hipLaunchKernelGGL(conv_h3_chamax_kernel, dim3(cd, c_out), dim3(256), 0, st, dy, n, c_out,
-                         dpl, co_am);
-      hipLaunchKernelGGL(conv_h3_chamax_kernel, dim3(cx, c_in), dim3(256), 0, st, x, n, c_in, xpl,
-                         ci_am);
-      if (w64_on())
-        hipLaunchKernelGGL((conv_x6_wgrad_sw_kernel<11, 3, 8, 2, 64>), dim3(G * slabs), dim3(512), 0,
-                           st, dy, x, partial, g, slabs, co_am, ci_am);
-      else
-        hipLaunchKernelGGL((conv_x6_wgrad_sw_kernel<11, 3, 8, 2>), dim3(G * slabs), dim3(512), 0, st,
-                           dy, x, partial, g, slabs, co_am, ci_am);
-    } else if (x6w_sw(g))
-      hipLaunchKernelGGL((conv_x6_wgrad_sw_kernel<11, 3, 8>), dim3(G * slabs), dim3(512), 0, st, dy,
-                         x, partial, g, slabs, nullptr, nullptr);
-    else
-      hipLaunchKernelGGL((conv_x6_wgrad_kernel<11, 3>), dim3(G * slabs), dim3(CW_T), 0, st, dy, x,
-                         partial, g, slabs);
-  } else if (pl.nt > 0) {
-    dim3 grid(static_cast<unsigned>((int64_t)pl.bands * c_in * n * cdiv(c_out, 32)));
-#define DS2_WGP(NT_, XS_, SW_)                                                               \
-  hipLaunchKernelGGL((conv_wgrad_patch_kernel<NT_, XS_, SW_>), grid, dim3(256), 0, st, dy, x, \
-                     partial, g, pl.bands, pl.xpitch)
-    if (pl.nt == 2) {
-      if (g.sw == 2) DS2_WGP(2, WG_XS_SMALL, 2); else DS2_WGP(2, WG_XS_SMALL, 1);
-    } else {
-      if (g.sw == 2) DS2_WGP(4, WG_XS_LARGE, 2); else DS2_WGP(4, WG_XS_LARGE, 1);
+  switch (p.rung) {
+    case DS2_CONV_WG_PATCH: {
+      const auto k = p.a == 2 ? (p.b == 2 ? conv_wgrad_patch_kernel<2, WG_XS_SMALL, 2>
+                                          : conv_wgrad_patch_kernel<2, WG_XS_SMALL, 1>)
+                              : (p.b == 2 ? conv_wgrad_patch_kernel<4, WG_XS_LARGE, 2>
+                                          : conv_wgrad_patch_kernel<4, WG_XS_LARGE, 1>);
+      hipLaunchKernelGGL(k, dim3(static_cast<unsigned>(p.grid)), dim3(256), 0, st, dy, x, partial, g,
+                         p.bands, p.pitch);
+      slabs = n * p.bands;
+      break;
     }
-#undef DS2_WGP
-    slabs = n * pl.bands;
-  } else {
-    dim3 grid(cdiv(Kc, CBNW), n, cdiv(c_out, 32));
-    hipLaunchKernelGGL(conv_wgrad_kernel, grid, dim3(256), 0, st, dy, x, partial, g);
+    case DS2_CONV_WG_GEMM: {
+      dim3 grid(cdiv(c_in * kh * kw, CBNW), n, cdiv(c_out, 32));
+      hipLaunchKernelGGL(conv_wgrad_kernel, grid, dim3(256), 0, st, dy, x, partial, g);
+      break;
+    }
+    default: {
+      const ds2_status_t rc = launch_conv_split_wgrad(p, g, dy, x, dw, ws, st);
+      if (rc != DS2_OK) return rc;
+      slabs = 0;   // reduced there
+    }
   }
-  const int64_t per = (int64_t)c_out * Kc;
-  int rg = cdiv(per, 256);
-  if (rg > 2048) rg = 2048;
-  if (x6w_ok(g)) {
-    const int nw = x6w_nw(g);
-    const int G = (kh + nw - 1) / nw;
-    const int64_t blk = (int64_t)G * (X6W_BLOCK / 4 * nw) * kw;
-    const int xg = static_cast<int>(std::min<int64_t>(cdiv(blk, 256), 2048));
-    hipLaunchKernelGGL(wgrad_reduce_x6_kernel, dim3(xg), dim3(256), 0, st, partial, slabs, G, kw,
-                       nw, g, dw, co_am, ci_am);
-  } else {
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(rg), dim3(256), 0, st, partial, slabs, per, dw);
-  }
+  if (slabs > 0)
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(std::min(cdiv(per, 256), 2048)), dim3(256), 0, st,
+                       partial, slabs, per, dw);
   if (dbias != nullptr)
     hipLaunchKernelGGL(bias_grad_kernel, dim3(c_out), dim3(BG_T), 0, st, dy, n, c_out,
                        (int64_t)g.ho * g.wo, dbias);
   return launch_status("ds2_conv2d_wgrad");
+}
+
+ds2_status_t ds2_test_conv2d_plan(int dir, int n, int c_in, int h_in, int w_in, int c_out, int kh,
+                                  int kw, int sh, int sw, int ph, int pw, int* out) {
+  ConvDims g;
+  if (dir < 0 || dir > 2 || out == nullptr ||
+      !make_dims(g, n, c_in, h_in, w_in, c_out, kh, kw, sh, sw, ph, pw))
+    return DS2_INVALID_VALUE;
+  const ConvSwitches s = conv_switches();
+  const ConvPlan p = dir == 0 ? conv_plan_fwd(g, s) : dir == 1 ? conv_plan_dgrad(g, s)
+                                                               : conv_plan_wgrad(g, s);
+  const int vals[11] = {p.rung, p.a, p.b,
+                        static_cast<int>(p.ws_bytes & 0xffffffffu),
+                        static_cast<int>((uint64_t)p.ws_bytes >> 32),
+                        p.gx, p.gy, p.splits, p.bands, p.pitch,
+                        static_cast<int>(std::min<int64_t>(p.grid, 0x7fffffff))};
+  std::copy(vals, vals + 11, out);
+  return DS2_OK;
 }
 
 }  // extern "C"

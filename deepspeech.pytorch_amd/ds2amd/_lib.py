@@ -121,6 +121,7 @@ _PROTOS = {
     "ds2_test_ring_traffic": (_c_int, [_vp, _c_i64, _c_int, _vp, _c_int, ctypes.c_double, _vp]),
     "ds2_test_beam_stamps": (_c_int, [_vp]),
     "ds2_test_rnn_last_launch": (_c_int, [_vp]),
+    "ds2_test_conv2d_plan": (_c_int, [_c_int] * 12 + [_vp]),
     "ds2_gru_bwd": (_c_int, [_c_int, _c_int, _c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp,
                              _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ds2_gru_bwd_bias": (_c_int, [_c_int, _c_int, _c_int, _c_int, _vp, _c_int, _vp, _vp, _vp,

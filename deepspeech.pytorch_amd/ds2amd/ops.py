@@ -277,6 +277,28 @@ def conv_out_shape(h: int, w: int, kh: int, kw: int, sh: int, sw: int, ph: int, 
     return (h + 2 * ph - kh) // sh + 1, (w + 2 * pw - kw) // sw + 1
 
 
+# the DS2_CONV_* rungs of include/ds2hip_test.h (DESIGN.md "Conv2d dispatch")
+CONV_RUNGS = ("none", "fwd_h3_2r", "fwd_h3_1r", "fwd_x6_db", "fwd_x6", "fwd_patch", "fwd_c1",
+              "fwd_gemm", "dg_h3_2r", "dg_h3_q", "dg_h3_q_noflush", "dg_x6_q", "dg_x6_26", "dg_x6",
+              "dg_patch", "dg_gemm", "wg_h3_sw32", "wg_h3_sw64", "wg_x6_sw", "wg_x6_row",
+              "wg_patch", "wg_gemm")
+ConvPlan = collections.namedtuple("ConvPlan", "rung a b ws_bytes gx gy splits bands pitch grid")
+
+
+def conv2d_plan(direction, x_shape, w_shape, stride, padding) -> ConvPlan:
+    """What conv2d_fwd ("fwd"), conv2d_dgrad ("dgrad") or conv2d_wgrad ("wgrad") launches for
+    the shape under the current DS2_CONV_* environment: the library's own plan, host only (no
+    device, nothing launched).  a, b: the rung's parameters (fwd_c1: KWH; wg_patch: NT, SW; the
+    wg_h3 / wg_x6 rungs: tap rows per group, groups)."""
+    n, ci, h, w = x_shape
+    co, _, kh, kw = w_shape
+    out = (ctypes.c_int * 11)()
+    _lib.call("ds2_test_conv2d_plan", ("fwd", "dgrad", "wgrad").index(direction), n, ci, h, w, co,
+              kh, kw, stride[0], stride[1], padding[0], padding[1], ctypes.addressof(out))
+    v = list(out)
+    return ConvPlan(CONV_RUNGS[v[0]], v[1], v[2], (v[4] << 32) | (v[3] & 0xffffffff), *v[5:])
+
+
 def conv2d_fwd(x, weight, bias, stride, padding, out_lens=None):
     x = _need(x, "conv2d.x")
     weight = _need(weight, "conv2d.weight")

@@ -72,6 +72,47 @@ enum {
 };
 ds2_status_t ds2_test_rnn_last_launch(int* out);
 
+/* ------------------------------------------------------------------------ */
+/* ds2_test_conv2d_plan: what ds2_conv2d_fwd (dir 0), ds2_conv2d_dgrad (1) or ds2_conv2d_wgrad
+ * (2) would launch for the shape under the current DS2_CONV_* environment.  Host only, no
+ * device needed, nothing launched: it calls the function the entry point switches on
+ * (csrc/conv_host.h conv_plan_*).  DS2_INVALID_VALUE for a shape the entry point rejects.
+ * out[11] =
+ *   [0] rung: a DS2_CONV_* value, a row of DESIGN.md's conv dispatch table
+ *   [1] [2] its parameters: FWD_C1 KWH, 0; WG_PATCH NT, SW; the WG_H3 / WG_X6 rungs: tap rows
+ *       per group, groups; 0 elsewhere
+ *   [3] [4] workspace bytes the rung needs, low and high 32 bits
+ *   [5] gx: column tiles           [6] gy: rows / row pairs / row tiles
+ *   [7] splits  [8] bands  [9] x patch pitch (wgrad; 0 elsewhere)
+ *   [10] workgroups of the convolution kernel (FWD_C1: tiles), saturating at INT_MAX;
+ *        0 for the implicit-GEMM rungs (3-D grids)                                    */
+enum {
+  DS2_CONV_NONE = 0,
+  DS2_CONV_FWD_H3_2R = 1,        /* conv_h3_fwd2r_kernel */
+  DS2_CONV_FWD_H3_1R = 2,        /* conv_x6_kernel<false, 3, 6, 2, 1, false, true, 2> */
+  DS2_CONV_FWD_X6_DB = 3,        /* conv_x6_kernel<false, 3, 6, 2, 1, false, true> */
+  DS2_CONV_FWD_X6 = 4,           /* conv_x6_kernel<false, 0, 0, 3, 0, true> */
+  DS2_CONV_FWD_PATCH = 5,        /* conv_patch_kernel<false> */
+  DS2_CONV_FWD_C1 = 6,           /* conv1_patch_fwd_kernel<KWH> */
+  DS2_CONV_FWD_GEMM = 7,         /* conv_fwd_kernel */
+  DS2_CONV_DG_H3_2R = 8,         /* conv_h3_dgrad2r_kernel */
+  DS2_CONV_DG_H3_Q = 9,          /* conv_x6q_dgrad_kernel<true, 2, true> */
+  DS2_CONV_DG_H3_Q_NOFLUSH = 10, /* conv_x6q_dgrad_kernel<true, 2, false> */
+  DS2_CONV_DG_X6_Q = 11,         /* conv_x6q_dgrad_kernel<true, 3> */
+  DS2_CONV_DG_X6_26 = 12,        /* conv_x6_kernel<true, 2, 6, 2, 1, false> */
+  DS2_CONV_DG_X6 = 13,           /* conv_x6_kernel<true, 0, 0, 3, 0, true> */
+  DS2_CONV_DG_PATCH = 14,        /* conv_patch_kernel<true> */
+  DS2_CONV_DG_GEMM = 15,         /* conv_dgrad_kernel */
+  DS2_CONV_WG_H3_SW32 = 16,      /* conv_x6_wgrad_sw_kernel<11, 3, 8, 2> */
+  DS2_CONV_WG_H3_SW64 = 17,      /* conv_x6_wgrad_sw_kernel<11, 3, 8, 2, 64> */
+  DS2_CONV_WG_X6_SW = 18,        /* conv_x6_wgrad_sw_kernel<11, 3, 8> */
+  DS2_CONV_WG_X6_ROW = 19,       /* conv_x6_wgrad_kernel<11, 3> */
+  DS2_CONV_WG_PATCH = 20,        /* conv_wgrad_patch_kernel<NT, XS, SW> */
+  DS2_CONV_WG_GEMM = 21          /* conv_wgrad_kernel */
+};
+ds2_status_t ds2_test_conv2d_plan(int dir, int n, int c_in, int h_in, int w_in, int c_out, int kh,
+                                  int kw, int sh, int sw, int ph, int pw, int* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -321,7 +321,33 @@ CONVS = [  # (n, ci, h, w, co, kh, kw, sh, sw, ph, pw)
     (3, 5, 19, 140, 40, 3, 3, 1, 1, 1, 1),
     (2, 4, 30, 50, 8, 7, 5, 3, 1, 3, 2),
     (1, 2, 9, 7, 3, 4, 2, 2, 1, 3, 0),
+    # rungs of the dispatch table (DESIGN.md "Conv2d dispatch") no shape above reaches: the
+    # 8-row 2 x 6 dgrad (16 class tap rows; fp32 mode: the NT 4 width-stride-1 wgrad), the
+    # general bf16x6 dgrad (15 class tap rows, 3 column pairs), the one-row fp16x3 forward at
+    # height stride 1, and the implicit-GEMM wgrad (width stride 3)
+    (1, 3, 40, 30, 5, 31, 11, 2, 1, 15, 5),
+    (1, 2, 20, 20, 3, 15, 5, 1, 1, 7, 2),
+    (1, 3, 30, 40, 5, 21, 11, 1, 1, 10, 5),
+    (2, 4, 20, 40, 8, 5, 5, 1, 3, 2, 2),
 ]
+# what the four shapes above are there for: {shape: {mode: (direction, rung)}}
+CONV_RUNGS = {
+    (1, 3, 40, 30, 5, 31, 11, 2, 1, 15, 5): {"h3": ("dgrad", "dg_x6_26"), "x6": ("dgrad", "dg_x6_26"),
+                                             "fp32": ("wgrad", "wg_patch")},
+    (1, 2, 20, 20, 3, 15, 5, 1, 1, 7, 2): {"h3": ("dgrad", "dg_x6"), "x6": ("dgrad", "dg_x6")},
+    (1, 3, 30, 40, 5, 21, 11, 1, 1, 10, 5): {"h3": ("fwd", "fwd_h3_1r"), "x6": ("fwd", "fwd_x6_db")},
+    (2, 4, 20, 40, 8, 5, 5, 1, 3, 2, 2): {"h3": ("wgrad", "wg_gemm"), "fp32": ("wgrad", "wg_gemm")},
+}
+CONV_FP16X3 = {"fwd_h3_2r", "fwd_h3_1r", "dg_h3_2r", "dg_h3_q", "dg_h3_q_noflush", "wg_h3_sw32",
+               "wg_h3_sw64"}
+CONV_FP32 = {"fwd_patch", "fwd_c1", "fwd_gemm", "dg_patch", "dg_gemm", "wg_patch", "wg_gemm"}
+
+
+def _conv_rungs(cfg):
+    """(fwd, dgrad, wgrad) rungs the library plans for the shape under the current switches."""
+    n, ci, h, w, co, kh, kw, sh, sw, ph, pw = cfg
+    return tuple(ops.conv2d_plan(d, (n, ci, h, w), (co, ci, kh, kw), (sh, sw), (ph, pw)).rung
+                 for d in ("fwd", "dgrad", "wgrad"))
 
 
 def _conv_mode(monkeypatch, mode):
@@ -343,6 +369,16 @@ def test_conv_fwd_bwd(dev, cfg, mode, monkeypatch):
     implicit-GEMM kernels (DS2_CONV_X6=0, and every shape the bf16x6 kernels do not cover)."""
     _conv_mode(monkeypatch, mode)
     n, ci, h, w, co, kh, kw, sh, sw, ph, pw = cfg
+    rungs = _conv_rungs(cfg)
+    if mode == "fp32":
+        assert set(rungs) <= CONV_FP32, rungs
+    if mode == "x6":
+        assert not set(rungs) & CONV_FP16X3, rungs
+    if mode == "h3" and (ci, co, kh, kw, sh, sw) == (32, 32, 21, 11, 2, 1):   # conv2-shaped
+        assert set(rungs) <= CONV_FP16X3, rungs
+    if mode in CONV_RUNGS.get(cfg, {}):
+        d, want = CONV_RUNGS[cfg][mode]
+        assert rungs[("fwd", "dgrad", "wgrad").index(d)] == want, rungs
     g = torch.Generator().manual_seed(sum(cfg))
     x = torch.randn(n, ci, h, w, generator=g, dtype=torch.float64)
     wt = torch.randn(co, ci, kh, kw, generator=g, dtype=torch.float64) * 0.1
@@ -381,8 +417,11 @@ def test_conv_x6_is_fp32_accurate(dev, monkeypatch):
     dxr = torch.nn.grad.conv2d_input(x.shape, wt, dy, stride=(sh, sw), padding=(ph, pw))
     dwr = torch.nn.grad.conv2d_weight(x, wt.shape, dy, stride=(sh, sw), padding=(ph, pw))
     errs = {}
+    want = {"h3": ("fwd_h3_2r", "dg_h3_2r", "wg_h3_sw32"), "x6": ("fwd_x6_db", "dg_x6_q", "wg_x6_sw"),
+            "fp32": ("fwd_patch", "dg_patch", "wg_patch")}
     for mode in ("h3", "x6", "fp32"):
         _conv_mode(monkeypatch, mode)
+        assert _conv_rungs((n, ci, h, w, co, kh, kw, sh, sw, ph, pw)) == want[mode]
         yd = ops.conv2d_fwd(x.float().to(dev), wt.float().to(dev), None, (sh, sw), (ph, pw))
         dx = ops.conv2d_dgrad(dy.float().to(dev), wt.float().to(dev), x.shape, (sh, sw), (ph, pw))
         dw, _ = ops.conv2d_wgrad(dy.float().to(dev), x.float().to(dev), tuple(wt.shape), (sh, sw),
@@ -417,6 +456,8 @@ def test_conv2_two_row_forward(dev, h, w, n, lens, monkeypatch):
     outs = {}
     for two in ("1", "0"):
         monkeypatch.setenv("DS2_CONV_2R", two)
+        assert _conv_rungs((n, ci, h, w, co, kh, kw, sh, sw, ph, pw))[0] == \
+            {"1": "fwd_h3_2r", "0": "fwd_h3_1r"}[two]
         outs[two] = ops.conv2d_fwd(x.float().to(dev), wt.float().to(dev), b.float().to(dev),
                                    (sh, sw), (ph, pw), out_lens=ld).double().cpu()
     scale = ref.abs().max().item()
@@ -444,6 +485,8 @@ def test_conv2_two_row_dgrad(dev, h, w, n, monkeypatch):
     outs = {}
     for two in ("1", "0"):
         monkeypatch.setenv("DS2_CONV_2R", two)
+        assert _conv_rungs((n, ci, h, w, co, kh, kw, sh, sw, ph, pw))[1] == \
+            {"1": "dg_h3_2r", "0": "dg_h3_q"}[two]
         outs[two] = ops.conv2d_dgrad(dy.float().to(dev), wt.float().to(dev), (n, ci, h, w), (sh, sw),
                                      (ph, pw)).double().cpu()
     scale = ref.abs().max().item()
@@ -453,6 +496,23 @@ def test_conv2_two_row_dgrad(dev, h, w, n, monkeypatch):
     err = (outs["1"] - ref)[ref != 0]
     drift = (err.mean() / err.abs().mean()).item()
     assert abs(drift) < 0.1, drift
+
+
+def test_conv2_one_row_dgrad_without_flush(dev, monkeypatch):
+    """conv_x6q_dgrad_kernel<true, 2, false> (DS2_CONV_2R=0 and DS2_CONV_DG_FLUSH=0: the one-row
+    fp16x3 dgrad without the per-channel chain flush) against fp64 at 1e-5, on the smallest
+    two-row dgrad case above (class rows 5 + 4)."""
+    n, ci, h, w, co, kh, kw, sh, sw, ph, pw = 1, 32, 9, 40, 32, 21, 11, 2, 1, 10, 5
+    monkeypatch.setenv("DS2_CONV_2R", "0")
+    monkeypatch.setenv("DS2_CONV_DG_FLUSH", "0")
+    assert _conv_rungs((n, ci, h, w, co, kh, kw, sh, sw, ph, pw))[1] == "dg_h3_q_noflush"
+    g = torch.Generator().manual_seed(h * 1000 + w + 7)
+    ho, wo = (h + 2 * ph - kh) // sh + 1, (w + 2 * pw - kw) // sw + 1
+    wt = torch.randn(co, ci, kh, kw, generator=g, dtype=torch.float64) * 0.05
+    dy = torch.randn(n, co, ho, wo, generator=g, dtype=torch.float64)
+    ref = torch.nn.grad.conv2d_input((n, ci, h, w), wt, dy, stride=(sh, sw), padding=(ph, pw))
+    dx = ops.conv2d_dgrad(dy.float().to(dev), wt.float().to(dev), (n, ci, h, w), (sh, sw), (ph, pw))
+    _close(dx, ref, 1e-5, "conv dgrad, no flush")
 
 
 def test_conv_h3_scales_over_twelve_decades(dev, monkeypatch):
@@ -482,8 +542,10 @@ def test_conv_h3_scales_over_twelve_decades(dev, monkeypatch):
     dwr = torch.nn.grad.conv2d_weight(xw, wt.shape, dyw, stride=(sh, sw), padding=(ph, pw))
     dwb = torch.nn.grad.conv2d_weight(xw.abs(), wt.shape, dyw.abs(), stride=(sh, sw), padding=(ph, pw))
     errs = {}
+    want = {"h3": ("fwd_h3_2r", "dg_h3_2r", "wg_h3_sw32"), "x6": ("fwd_x6_db", "dg_x6_q", "wg_x6_sw")}
     for mode in ("h3", "x6"):
         _conv_mode(monkeypatch, mode)
+        assert _conv_rungs((n, ci, h, w, co, kh, kw, sh, sw, ph, pw)) == want[mode]
         yd = ops.conv2d_fwd(x.float().to(dev), wt.float().to(dev), None, (sh, sw), (ph, pw))
         dx = ops.conv2d_dgrad(dy.float().to(dev), wt2.float().to(dev), x.shape, (sh, sw), (ph, pw))
         dwd, _ = ops.conv2d_wgrad(dyw.float().to(dev), xw.float().to(dev), tuple(wt.shape), (sh, sw),
@@ -500,13 +562,17 @@ def test_conv_h3_scales_over_twelve_decades(dev, monkeypatch):
                                  (2, 8, 40, 60, 16, 7, 11, 3, 1, 3, 5)])
 @pytest.mark.parametrize("w64", ["0", "1"])
 def test_conv_x6_wgrad_forms(dev, cfg, w64, monkeypatch):
-    """The bf16x6 weight gradients against fp64 torch: the sliding-window form (row strides
-    <= 2: sh new x rows per output row into a 6-slot ring; splits that start mid-segment and
-    segments of one row, 4 x 70 columns = 3 chunks per row) and the per-row-restaging form
-    (row stride 3).  w64 = 1: the fp16x3 sliding window on 64-column stages (DS2_CONV_W64;
-    200 columns = 4 chunks with a partial last one, 70 = 2)."""
+    """The split-operand weight gradients for 11 kernel columns against fp64 torch.  Row strides
+    <= 2 run the fp16x3 sliding window (the default; sh new x rows per output row into a 6-slot
+    ring; splits that start mid-segment and segments of one row, 4 x 70 columns = 3 chunks per
+    row): on 32-column stages for w64 = 0, on 64-column stages for w64 = 1 (DS2_CONV_W64; 200
+    columns = 4 chunks with a partial last one, 70 = 2).  Row stride 3 runs the bf16x6
+    per-row-restaging form under both settings.  (The bf16x6 sliding window, DS2_CONV_H3W=0, is
+    test_conv_fwd_bwd's x6 mode.)"""
     monkeypatch.setenv("DS2_CONV_W64", w64)
     n, ci, h, w, co, kh, kw, sh, sw, ph, pw = cfg
+    assert _conv_rungs(cfg)[2] == ("wg_x6_row" if sh == 3 else
+                                   {"0": "wg_h3_sw32", "1": "wg_h3_sw64"}[w64])
     g = torch.Generator().manual_seed(sum(cfg) + 1)
     x = torch.randn(n, ci, h, w, generator=g, dtype=torch.float64)
     wt = torch.randn(co, ci, kh, kw, generator=g, dtype=torch.float64) * 0.1

@@ -26,6 +26,7 @@
 // of the loop is LDS-DMA + ds_read; no ordinary global load is pending in the loop (hipcc would
 // drain the DMA queue at it).
 #include "common.h"
+#include "gemm_host.h"
 
 #include <algorithm>
 
@@ -54,41 +55,7 @@ __device__ __forceinline__ void bg_barrier() {
   asm volatile("" ::: "memory");
 }
 
-// Tile decode shared with gemm.hip's planner: whole tiles first, then the split-K tail pieces
-// (the same XCD-aware bijective remap as decode_work, grouped tile order of 4 tile rows).
-__device__ __forceinline__ void bg_decode(int M, int N, int K, int main_wgs, int tail_tile0,
-                                          int tail_tiles, int nsplit, int kchunk, float* partial,
-                                          int& m0, int& n0, int& kbeg, int& kend, float*& part) {
-  const int tn = (N + BG_N - 1) / BG_N, tm = (M + BG_M - 1) / BG_M;
-  const int orig = blockIdx.x;
-  int tile, z = 0;
-  part = nullptr;
-  if (orig < main_wgs) {
-    const int q = main_wgs >> 3, r = main_wgs & 7;
-    const int xcd = orig & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-  } else {
-    const int np = gridDim.x - main_wgs;
-    const int o = orig - main_wgs;
-    const int q = np >> 3, r = np & 7;
-    const int xcd = o & 7;
-    const int pidx = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (o >> 3);
-    z = pidx / tail_tiles;
-    const int lt = pidx - z * tail_tiles;
-    tile = tail_tile0 + lt;
-    if (nsplit > 1) part = partial + ((int64_t)z * tail_tiles + lt) * (BG_M * BG_N);
-  }
-  constexpr int G = 4;
-  const int g = tile / (G * tn);
-  const int rem = tile - g * G * tn;
-  const int rows = min(G, tm - g * G);
-  const int tile_n = rem / rows;
-  const int tile_m = g * G + (rem - tile_n * rows);
-  kbeg = orig < main_wgs ? 0 : z * kchunk;
-  kend = orig < main_wgs ? K : min(K, kbeg + kchunk);
-  m0 = tile_m * BG_M;
-  n0 = tile_n * BG_N;
-}
+// bg_decode: the work decode, shared with the host (gemm_host.h)
 
 template <bool KCHK>
 __global__ __launch_bounds__(BG_T, 1) void bgemm_nt_kernel(
@@ -99,8 +66,8 @@ __global__ __launch_bounds__(BG_T, 1) void bgemm_nt_kernel(
   __shared__ __attribute__((aligned(16))) unsigned short lds[2 * BG_IMG];   // 128 KB
   int m0, n0, kbeg, kend;
   float* part;
-  bg_decode(M, N, K, main_wgs, tail_tile0, tail_tiles, nsplit, kchunk, partial, m0, n0, kbeg,
-            kend, part);
+  bg_decode(blockIdx.x, gridDim.x, M, N, K, main_wgs, tail_tile0, tail_tiles, nsplit, kchunk,
+            partial, m0, n0, kbeg, kend, part);
   const int t = threadIdx.x;
   const int lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -415,10 +382,6 @@ __global__ void bg_reduce_kernel(const float* __restrict__ partial, int M, int N
   }
 }
 
-struct BgPlan {
-  int main_wgs, tail_tile0, tail_tiles, nsplit, kchunk;
-};
-
 static int bg_cus() {
   static int cus = -1;
   if (cus < 0) {
@@ -431,41 +394,9 @@ static int bg_cus() {
   return cus;
 }
 
-// Whole tiles in full rounds of one workgroup per CU; the last partial round's tiles get their
-// K range split so the pieces fill a round (time model in units of one 64-deep tile step;
-// a split piece adds its 256 KB partial slab written and read back, ~1/8 of a step).
-static BgPlan bg_plan(int m, int n, int k) {
-  const int cus = bg_cus();
-  const int tiles = cdiv(m, BG_M) * cdiv(n, BG_N);
-  BgPlan p{(tiles / cus) * cus, 0, 0, 1, k};
-  p.tail_tile0 = p.main_wgs;
-  p.tail_tiles = tiles - p.main_wgs;
-  if (p.tail_tiles == 0) {
-    p.main_wgs = 0;
-    p.tail_tile0 = 0;
-    p.tail_tiles = tiles;
-  }
-  const int ksteps = cdiv(k, BG_K);
-  double best = 1e30;
-  for (int s = 1; s <= 32 && s <= ksteps; ++s) {
-    const int kc = cdiv(ksteps, s);
-    const int ns = cdiv(ksteps, kc);
-    if (s > 1 && ns != s) continue;
-    const int64_t pieces = (int64_t)p.tail_tiles * ns;
-    const double t = (double)((pieces + cus - 1) / cus) * kc + (ns > 1 ? 0.125 * (double)pieces / cus + 1.0 : 0.0);
-    if (t < best - 1e-9) {
-      best = t;
-      p.nsplit = ns;
-      p.kchunk = kc * BG_K;
-    }
-  }
-  if (p.nsplit == 1) p.kchunk = k;
-  return p;
-}
-
-static size_t bg_ws(const BgPlan& p) {
-  return p.nsplit > 1 ? (size_t)p.nsplit * p.tail_tiles * BG_M * BG_N * sizeof(float) + 256 : 0;
-}
+// the plan (bg_plan) and every flag come from gemm_select (gemm_host.h); its tile is this kernel's
+static_assert(kGBgM == BG_M && kGBgN == BG_N && kGBgK == BG_K,
+              "gemm_host.h plans for another tile than bgemm_nt_kernel's");
 
 }  // namespace ds2
 
@@ -475,47 +406,32 @@ extern "C" {
 
 size_t ds2_bgemm_workspace_size(int m, int n, int k) {
   if (m <= 0 || n <= 0 || k <= 0) return 0;
-  return bg_ws(bg_plan(m, n, k));
+  return plan_ws(bg_plan(m, n, k, bg_cus()), 1);
 }
 
 ds2_status_t ds2_bgemm_nt(int m, int n, int k, float alpha, const void* a, int64_t lda,
                           const void* b, int64_t ldb, float beta, float* c, int64_t ldc,
                           const float* bias, void* ws, size_t ws_bytes, ds2_stream_t stream) {
-  if (m < 0 || n < 0 || k < 0) return DS2_INVALID_VALUE;
-  if (m == 0 || n == 0) return DS2_OK;
-  if (a == nullptr || b == nullptr || c == nullptr || lda < k || ldb < k || ldc < n)
-    return DS2_INVALID_VALUE;
-  // 16-B DMA granules: 16-B aligned operands, k and the row strides multiples of 8 bf16
-  if ((reinterpret_cast<uintptr_t>(a) & 15) || (reinterpret_cast<uintptr_t>(b) & 15) ||
-      (lda & 7) || (ldb & 7) || (k & 7) || (int64_t)m * lda * 2 >= (1ll << 31) ||
-      (int64_t)n * ldb * 2 >= (1ll << 31) || lda >= (1 << 30) || ldb >= (1 << 30))
-    return DS2_UNSUPPORTED_SHAPE;
-  if (k == 0) return DS2_UNSUPPORTED_SHAPE;
-  BgPlan p = bg_plan(m, n, k);
-  if (p.nsplit > 1 && (ws == nullptr || ws_bytes < bg_ws(p))) {
-    p.nsplit = 1;
-    p.kchunk = k;
-  }
+  const GemmCall g{2, 0, 1, m, n, k, reinterpret_cast<uintptr_t>(a), lda, 0,
+                   reinterpret_cast<uintptr_t>(b), ldb, 0, reinterpret_cast<uintptr_t>(c), ldc, 0,
+                   1, reinterpret_cast<uintptr_t>(bias), ws != nullptr, ws_bytes};
+  const GemmChoice ch = gemm_select(g, gemm_switches(), bg_cus());
+  if (ch.status != DS2_OK || ch.rung == DS2_GEMM_NONE) return ch.status;
+  const GemmPlan& p = ch.p;
   float* partial = p.nsplit > 1 ? static_cast<float*>(ws) : nullptr;
-  const int64_t nwg = p.main_wgs + (int64_t)p.tail_tiles * p.nsplit;
-  if (nwg > 0x7fffffff) return DS2_UNSUPPORTED_SHAPE;
+  const dim3 grid(static_cast<unsigned>(ch.grid));
   hipStream_t st = as_stream(stream);
-  const bool kalign = k % BG_K == 0 && p.kchunk % BG_K == 0;
-  // 16-B row runs of C (and of bias) when every row starts 16-B aligned
-  const int cvec = !((reinterpret_cast<uintptr_t>(c) & 15) || (ldc & 3) ||
-                     (bias != nullptr && (reinterpret_cast<uintptr_t>(bias) & 15)));
+  const int cvec = ch.vec ? 1 : 0;
   const unsigned short* A = static_cast<const unsigned short*>(a);
   const unsigned short* B = static_cast<const unsigned short*>(b);
-  if (kalign)
-    hipLaunchKernelGGL(bgemm_nt_kernel<false>, dim3(static_cast<unsigned>(nwg)), dim3(BG_T), 0, st,
-                       m, n, k, alpha, A, static_cast<int>(lda), B, static_cast<int>(ldb), beta, c,
-                       ldc, bias, p.main_wgs, p.tail_tile0, p.tail_tiles, p.nsplit, p.kchunk,
-                       partial, cvec);
+  if (ch.rung == DS2_GEMM_BF16_DMA)
+    hipLaunchKernelGGL(bgemm_nt_kernel<false>, grid, dim3(BG_T), 0, st, m, n, k, alpha, A,
+                       static_cast<int>(lda), B, static_cast<int>(ldb), beta, c, ldc, bias,
+                       p.main_wgs, p.tail_tile0, p.tail_tiles, p.nsplit, p.kchunk, partial, cvec);
   else
-    hipLaunchKernelGGL(bgemm_nt_kernel<true>, dim3(static_cast<unsigned>(nwg)), dim3(BG_T), 0, st,
-                       m, n, k, alpha, A, static_cast<int>(lda), B, static_cast<int>(ldb), beta, c,
-                       ldc, bias, p.main_wgs, p.tail_tile0, p.tail_tiles, p.nsplit, p.kchunk,
-                       partial, cvec);
+    hipLaunchKernelGGL(bgemm_nt_kernel<true>, grid, dim3(BG_T), 0, st, m, n, k, alpha, A,
+                       static_cast<int>(lda), B, static_cast<int>(ldb), beta, c, ldc, bias,
+                       p.main_wgs, p.tail_tile0, p.tail_tiles, p.nsplit, p.kchunk, partial, cvec);
   if (p.nsplit > 1) {
     const int64_t total = (int64_t)p.tail_tiles * BG_M * BG_N;
     const int g = static_cast<int>(std::min<int64_t>(cdiv(total, 256), 4096));

@@ -11,6 +11,7 @@
 // (+2 floats) makes those 8 ds_write_b32 per thread conflict-free.
 #include "common.h"
 #include "amax_rc.h"
+#include "gemm_host.h"
 
 #include <type_traits>
 
@@ -92,63 +93,7 @@ __device__ __forceinline__ void store_tile(float* __restrict__ s, const float (&
   }
 }
 
-// Work items (blockIdx.x in dispatch order):
-//   [0, main_wgs)       one whole output tile each (batch == 1), XCD-aware order;
-//   [main_wgs, grid)    "tail" pieces: (batch, split, tile) of the tiles from tail_tile0
-//                       on, K range split nsplit ways; dispatched last, they fill the
-//                       slots the whole tiles leave in the final round.
-// XCD-aware (bijective) remap of both ranges: the blocks the dispatcher deals to one XCD
-// (ids congruent mod 8) get a contiguous run of tiles (pieces) in the grouped order below,
-// so workgroups sharing an operand panel share that XCD's L2.
-// Grouped tile order: tile ids run over groups of g_tile_group m-rows, inside a group column
-// by column (m fastest), so the ~32 tiles one XCD runs at once span 4 m-rows x 8 n-columns
-// (A: 4 panels, B: 8) instead of ~2 m-rows x every n-column (the input projection's 15 B
-// panels, 7.7 MB, overflow the XCD's 4-MB L2 and were fetched again for every m-row).
-constexpr int kTileGroup = 4;
-
-__device__ __forceinline__ void tile_coords(int tile, int tn, int tm, int& tile_m, int& tile_n) {
-  constexpr int G = kTileGroup;
-  const int g = tile / (G * tn);
-  const int rem = tile - g * G * tn;
-  const int rows = min(G, tm - g * G);
-  tile_n = rem / rows;
-  tile_m = g * G + (rem - tile_n * rows);
-}
-
-__device__ __forceinline__ void decode_work(int M, int N, int K, int main_wgs, int tail_tile0,
-                                            int tail_tiles, int nsplit, int kchunk,
-                                            float* partial, int& m0, int& n0, int& kbeg,
-                                            int& kend, int& bz, float*& part, int bn = BN,
-                                            int bm = BM) {
-  const int tn = (N + bn - 1) / bn;
-  const int orig = blockIdx.x;
-  int tile, z = 0;
-  part = nullptr;
-  if (orig < main_wgs) {
-    const int q = main_wgs >> 3, r = main_wgs & 7;
-    const int xcd = orig & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-  } else {
-    const int np = gridDim.x - main_wgs;
-    const int o = orig - main_wgs;
-    const int q = np >> 3, r = np & 7;
-    const int xcd = o & 7;
-    const int pidx = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (o >> 3);
-    z = pidx / tail_tiles;
-    const int lt = pidx - z * tail_tiles;
-    tile = tail_tile0 + lt;
-    if (nsplit > 1) part = partial + ((int64_t)z * tail_tiles + lt) * (bm * bn);
-  }
-  int tile_m, tile_n;
-  tile_coords(tile, tn, (M + bm - 1) / bm, tile_m, tile_n);
-  // z = batch * nsplit + split
-  bz = z / nsplit;
-  const int sp = z - bz * nsplit;
-  kbeg = orig < main_wgs ? 0 : sp * kchunk;
-  kend = orig < main_wgs ? K : min(K, kbeg + kchunk);
-  m0 = tile_m * bm;
-  n0 = tile_n * bn;
-}
+// tile_coords / decode_work: the work decode, shared with the host (gemm_host.h)
 
 // Epilogue: C/D map of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 * (r >> 2) +
 // 4 * (lane >> 5).  Split pieces write a tile-local [BM][BN] partial slab.
@@ -204,8 +149,8 @@ __global__ __launch_bounds__(256) void sgemm_kernel(
 
   int m0, n0, kbeg, kend, bz;
   float* part;
-  decode_work(M, N, K, main_wgs, tail_tile0, tail_tiles, nsplit, kchunk, partial, m0, n0, kbeg,
-              kend, bz, part);
+  decode_work(blockIdx.x, gridDim.x, M, N, K, main_wgs, tail_tile0, tail_tiles, nsplit, kchunk,
+              partial, m0, n0, kbeg, kend, bz, part);
   A += bz * sA;
   B += bz * sB;
   C += bz * sC;
@@ -373,8 +318,8 @@ __global__ __launch_bounds__(256, 2) void sgemm64_kernel(
 
   int m0, n0, kbeg, kend, bz;
   float* part;
-  decode_work(M, N, K, main_wgs, tail_tile0, tail_tiles, nsplit, kchunk, partial, m0, n0, kbeg,
-              kend, bz, part, TBN);
+  decode_work(blockIdx.x, gridDim.x, M, N, K, main_wgs, tail_tile0, tail_tiles, nsplit, kchunk,
+              partial, m0, n0, kbeg, kend, bz, part, TBN);
   A += bz * sA;
   B += bz * sB;
   C += bz * sC;
@@ -559,8 +504,8 @@ __global__ __launch_bounds__(256, 2) void sbgemm_kernel(
 
   int m0, n0, kbeg, kend, bz;
   float* part;
-  decode_work(M, N, K, main_wgs, tail_tile0, tail_tiles, nsplit, kchunk, partial, m0, n0, kbeg,
-              kend, bz, part, TBN);
+  decode_work(blockIdx.x, gridDim.x, M, N, K, main_wgs, tail_tile0, tail_tiles, nsplit, kchunk,
+              partial, m0, n0, kbeg, kend, bz, part, TBN);
   A += bz * sA;
   B += bz * sB;
   C += bz * sC;
@@ -1305,8 +1250,8 @@ __global__ __launch_bounds__(X2T, 1) void sxgemm2_kernel(
 
   int m0, n0, kbeg, kend, bz;
   float* part;
-  decode_work(M, N, K, main_wgs, tail_tile0, tail_tiles, nsplit, kchunk, partial, m0, n0, kbeg,
-              kend, bz, part, TBN, X2M);
+  decode_work(blockIdx.x, gridDim.x, M, N, K, main_wgs, tail_tile0, tail_tiles, nsplit, kchunk,
+              partial, m0, n0, kbeg, kend, bz, part, TBN, X2M);
   A += bz * sA;
   B += bz * sB;
   C += bz * sC;
@@ -1561,118 +1506,13 @@ static int device_cus() {
   return g_cus;
 }
 
-// Work plan.  Whole tiles run in full rounds of `slots` resident workgroups (3 per CU);
-// the tiles of a last, partial round ("tail") have their K range split so that the
-// round is filled: e.g. the input projection 16032 x 2400 = 2394 tiles = 3 rounds of
-// 768 + 90 tail tiles x 8 splits; the weight gradient 2400 x 800 (133 tiles, K = 16032)
-// becomes 133 tiles x 5 splits.  Split partials are reduced in a fixed order.
-struct GemmPlan {
-  int main_wgs, tail_tile0, tail_tiles, nsplit, kchunk, bn, bm;
-};
+// The plan, the rung and every flag come from gemm_select (gemm_host.h); its tile sizes are
+// these kernels'
+static_assert(kG16M == BM && kG16N == BN && kG16K == BK && kG64K == K64 && kGB16K == KB16 &&
+                  kGX2M == X2M && kGXS == XS,
+              "gemm_host.h plans for other tiles than the kernels'");
 
-// DS2_GEMM_X6=0 selects the fp32-MFMA kernels (the accuracy cross-check of the tests); the
-// bf16x6 kernel needs float4-staged operands (the fp32 kernels take any alignment; the
-// deep-K sgemm64_kernel runs 2 workgroups per CU and BK = 64, the original one 3 per CU and
-// BK = 16, for operands that are not float4-aligned)
-static bool x6_enabled(bool va, bool vb) {
-  if (!va || !vb) return false;
-  const char* e = getenv("DS2_GEMM_X6");
-  return !(e != nullptr && e[0] == '0');
-}
-
-// 32-bit buffer offsets: each operand (one batch entry) must span < 2^31 bytes
-static bool fits_rsrc(int64_t rows, int64_t ld) { return rows * ld * 4 < (1ll << 31); }
-
-// Plan for tile width bn.  The split count s of the tail is chosen by a time model in
-// units of one workgroup slot's MFMA time per (128-row x k) tile step: whole rounds
-// cost k each, the tail ceil(pieces / slots) * kchunk; a split adds its partial-slab
-// write + read (8 B per element at ~4 TB/s) and the reduce launch.  `eff` is the tile's
-// relative MFMA efficiency (160-wide tiles: 5 B fragments per 4 A, measured ~7 % faster
-// per unit of work than 128-wide in isolation; 1.15 in the plan, where it also stands in
-// for the 160-wide tile's smaller tail: a whole training step measured 1.0 < 1.07 < 1.15
-// ~ 1.25 ~ 1.4, the last three within noise).
-struct PlanChoice {
-  GemmPlan p;
-  double t;   // seconds (model)
-};
-
-static PlanChoice plan_bn(int m, int n, int k, int batch, int bn, int slots, int bk,
-                          double eff, int bm = BM) {
-  const int tiles = cdiv(m, bm) * cdiv(n, bn);
-  GemmPlan p{0, 0, tiles, 1, std::max(k, 1), bn, bm};
-  if (batch == 1) {
-    p.main_wgs = (tiles / slots) * slots;
-    p.tail_tile0 = p.main_wgs;
-    p.tail_tiles = tiles - p.main_wgs;
-    if (p.tail_tiles == 0) {   // full rounds only
-      p.main_wgs = 0;
-      p.tail_tile0 = 0;
-      p.tail_tiles = tiles;
-    }
-  }
-  // seconds per unit (one k step of one BM x bn tile on one slot)
-  const double unit = 2.0 * bm * bn / (157.3e12 * eff / slots);
-  const double main_t = (double)(p.main_wgs / slots) * k * unit;
-  const int64_t tail = (int64_t)p.tail_tiles * batch;
-  const int smax = std::max(1, std::min(32, k / 256));
-  double best = 1e30;
-  int bs = 1;
-  for (int s = 1; s <= smax; ++s) {
-    const int kc = cdiv(cdiv(k, s), bk) * bk;
-    const int ns = cdiv(k, kc);
-    if (s > 1 && ns != s) continue;
-    const int64_t pieces = tail * ns;
-    double t = (double)((pieces + slots - 1) / slots) * kc * unit;
-    if (ns > 1) t += (double)pieces * bm * bn * 8.0 / 4e12 + 6e-6;
-    if (t < best - 1e-12) {
-      best = t;
-      bs = ns;
-    }
-  }
-  if (bs > 1) {
-    p.kchunk = cdiv(cdiv(k, bs), bk) * bk;
-    p.nsplit = cdiv(k, p.kchunk);
-  }
-  return {p, main_t + best};
-}
-
-// 160-wide tiles are ~7 % faster per unit of work than 128-wide in isolation (5 B fragments
-// per 4 A); 1.15 in the time model, where it also stands in for the 160-wide tile's smaller
-// tail (a whole training step measured 1.0 < 1.07 < 1.15 ~ 1.25 ~ 1.4, the last three
-// within noise)
-constexpr double kEff160 = 1.15;
-
-static GemmPlan gemm_plan(int m, int n, int k, int batch, bool k64) {
-  const int cus = device_cus();
-  if (!k64) return plan_bn(m, n, k, batch, BN, 3 * cus, BK, 1.0).p;
-  const PlanChoice a = plan_bn(m, n, k, batch, 128, 2 * cus, K64, 1.0);
-  const PlanChoice b = plan_bn(m, n, k, batch, 160, 2 * cus, K64, kEff160);
-  return b.t < a.t ? b.p : a.p;
-}
-
-static size_t plan_ws(const GemmPlan& p, int batch) {
-  return p.nsplit > 1 ? (size_t)p.nsplit * batch * p.tail_tiles * p.bm * p.bn * sizeof(float) + 256
-                      : 0;
-}
-
-// the bf16x6 kernel: 256-row tiles, one workgroup per CU, split-K in 32-k chunks; 160-wide
-// tiles measured faster on every step shape with N >= 800 (scripts/bench_gemm_x6.py: 180-201
-// vs 159-194 TF), 128-wide on narrow N (the FC's 29 columns)
-static GemmPlan x6_plan(int m, int n, int k, int batch) {
-  return plan_bn(m, n, k, batch, n >= 256 ? 160 : 128, device_cus(), XS, 1.0, X2M).p;
-}
-
-// fp16x3 (default since round 5; DS2_GEMM_H3=0 selects the bf16x6 kernel): the x6 kernel's
-// plan and tiles with the operands split into two fp16 terms of row-scaled values and three
-// products per pair (see x2_split_store); the row maxima come from the caller
-// (ds2_sgemm_amax_ws) or from a pre-pass over each operand into the workspace after the
-// split-K slabs.  On the step's shapes 1.4-1.7x the bf16x6 kernel's rate at equal or lower
-// error against fp64 (scripts/bench_gemm_h3.py, profiles/r5b_gemm_h3_vs_x6.txt).
-static bool h3_enabled() {
-  const char* e = getenv("DS2_GEMM_H3");
-  return !(e != nullptr && e[0] == '0');
-}
-static size_t h3_ws(int m, int n) { return (size_t)(m + n) * 4 + 512; }
+static inline uintptr_t addr(const void* p) { return reinterpret_cast<uintptr_t>(p); }
 
 extern "C" ds2_status_t ds2_amax(const float* x, int rows, int cols, int64_t ld,
                                  unsigned* row_amax, unsigned* col_amax, ds2_stream_t stream) {
@@ -1708,89 +1548,82 @@ extern "C" ds2_status_t ds2_amax(const float* x, int rows, int cols, int64_t ld,
 // large enough for any kernel's plan (the choice depends on operand alignment)
 extern "C" size_t ds2_sgemm_workspace_size(int m, int n, int k, int batch) {
   if (m <= 0 || n <= 0 || k <= 0 || batch <= 0) return 0;
-  return std::max(std::max(plan_ws(gemm_plan(m, n, k, batch, false), batch),
-                           plan_ws(gemm_plan(m, n, k, batch, true), batch)),
-                  plan_ws(x6_plan(m, n, k, batch), batch) + h3_ws(m, n));
+  return gemm_ws_any(m, n, k, batch, device_cus());
 }
 
-static ds2_status_t sgemm_run(int trans_a, int trans_b, int m, int n, int k, float alpha,
-                              const float* a, int64_t lda, int64_t stride_a, const float* b,
-                              int64_t ldb, int64_t stride_b, float beta, float* c, int64_t ldc,
-                              int64_t stride_c, int batch, const float* bias, void* ws,
-                              size_t ws_bytes, const unsigned* a_amax_in,
-                              const unsigned* b_amax_in, ds2_stream_t stream);
-
-extern "C" ds2_status_t ds2_sgemm_ws(int trans_a, int trans_b, int m, int n, int k, float alpha,
-                                     const float* a, int64_t lda, int64_t stride_a,
-                                     const float* b, int64_t ldb, int64_t stride_b, float beta,
-                                     float* c, int64_t ldc, int64_t stride_c, int batch,
-                                     const float* bias, void* ws, size_t ws_bytes,
-                                     ds2_stream_t stream) {
-  return sgemm_run(trans_a, trans_b, m, n, k, alpha, a, lda, stride_a, b, ldb, stride_b, beta, c,
-                   ldc, stride_c, batch, bias, ws, ws_bytes, nullptr, nullptr, stream);
-}
-
-extern "C" ds2_status_t ds2_sgemm_amax_ws(int trans_a, int trans_b, int m, int n, int k,
-                                          float alpha, const float* a, int64_t lda,
-                                          const float* b, int64_t ldb, float beta, float* c,
-                                          int64_t ldc, const float* bias, const unsigned* a_amax,
-                                          const unsigned* b_amax, void* ws, size_t ws_bytes,
-                                          ds2_stream_t stream) {
-  return sgemm_run(trans_a, trans_b, m, n, k, alpha, a, lda, 0, b, ldb, 0, beta, c, ldc, 0, 1,
-                   bias, ws, ws_bytes, a_amax, b_amax, stream);
-}
-
-static ds2_status_t sgemm_run(int trans_a, int trans_b, int m, int n, int k, float alpha,
-                              const float* a, int64_t lda, int64_t stride_a, const float* b,
-                              int64_t ldb, int64_t stride_b, float beta, float* c, int64_t ldc,
-                              int64_t stride_c, int batch, const float* bias, void* ws,
-                              size_t ws_bytes, const unsigned* a_amax_in,
-                              const unsigned* b_amax_in, ds2_stream_t stream) {
-  if (m < 0 || n < 0 || k < 0 || batch < 0) return DS2_INVALID_VALUE;
-  if (m == 0 || n == 0 || batch == 0) return DS2_OK;
-  if (ldc < n) return DS2_INVALID_VALUE;
-  if (trans_a ? lda < m : lda < k) return DS2_INVALID_VALUE;
-  if (trans_b ? ldb < k : ldb < n) return DS2_INVALID_VALUE;
-  // vector (float4) staging is legal when every float4 is fully in or out of bounds
-  const bool va = aligned16(a) && (lda % 4 == 0) && (stride_a % 4 == 0) &&
-                  (trans_a ? (m % 4 == 0) : (k % 4 == 0));
-  const bool vb = aligned16(b) && (ldb % 4 == 0) && (stride_b % 4 == 0) &&
-                  (trans_b ? (k % 4 == 0) : (n % 4 == 0));
-  const bool fits = fits_rsrc(trans_a ? k : m, lda) && fits_rsrc(trans_b ? n : k, ldb);
-  const bool x6 = fits && x6_enabled(va, vb);
-  const bool k64 = !x6 && va && vb && fits;
-  GemmPlan p = x6 ? x6_plan(m, n, k, batch) : gemm_plan(m, n, k, batch, k64);
-  if (p.nsplit > 1 && (ws == nullptr || ws_bytes < plan_ws(p, batch))) {
-    p.nsplit = 1;                       // no workspace: whole-K pieces
-    p.kchunk = std::max(k, 1);
+// One launch per rung of gemm_select (DESIGN.md "GEMM dispatch").  fp16x3 (default since round
+// 5; DS2_GEMM_H3=0 selects the bf16x6 kernel): the x6 kernel's plan and tiles with the operands
+// split into two fp16 terms of row-scaled values and three products per pair (see
+// x2_split_store); the row maxima come from the caller (ds2_sgemm_amax_ws) or from a pre-pass
+// over each operand into the workspace after the split-K slabs.  On the step's shapes 1.4-1.7x
+// the bf16x6 kernel's rate at equal or lower error against fp64 (scripts/bench_gemm_h3.py,
+// profiles/r5b_gemm_h3_vs_x6.txt).
+template <int TA, int TB>
+static void launch_rung(const GemmChoice& ch, hipStream_t st, int m, int n, int k, float alpha,
+                        const float* a, int64_t lda, int64_t stride_a, const float* b,
+                        int64_t ldb, int64_t stride_b, float beta, float* c, int64_t ldc,
+                        int64_t stride_c, const float* bias, float* partial,
+                        const unsigned* a_amax, const unsigned* b_amax) {
+  const GemmPlan& p = ch.p;
+  const dim3 grid(static_cast<unsigned>(ch.grid));
+#define DS2_X6(KCHK_, BN_, M16_)                                                              \
+  hipLaunchKernelGGL((sxgemm2_kernel<TA, TB, KCHK_, BN_, 3, M16_>), grid, dim3(X2T), 0, st, m,  \
+                     n, k, alpha, a, lda, stride_a, b, ldb, stride_b, beta, c, ldc, stride_c,   \
+                     bias, p.main_wgs, p.tail_tile0, p.tail_tiles, p.nsplit, p.kchunk, partial, \
+                     nullptr, nullptr)
+#define DS2_H3(BN_)                                                                           \
+  hipLaunchKernelGGL((sxgemm2_kernel<TA, TB, false, BN_, 2, true>), grid, dim3(X2T), 0, st, m,  \
+                     n, k, alpha, a, lda, stride_a, b, ldb, stride_b, beta, c, ldc, stride_c,   \
+                     bias, p.main_wgs, p.tail_tile0, p.tail_tiles, p.nsplit, p.kchunk, partial, \
+                     a_amax, b_amax)
+  switch (ch.rung) {
+    case DS2_GEMM_H3_160: DS2_H3(160); break;
+    case DS2_GEMM_H3_128: DS2_H3(128); break;
+    case DS2_GEMM_X6_M16_160: DS2_X6(false, 160, true); break;
+    case DS2_GEMM_X6_M16_128: DS2_X6(false, 128, true); break;
+    case DS2_GEMM_X6_160: DS2_X6(false, 160, false); break;
+    case DS2_GEMM_X6_128: DS2_X6(false, 128, false); break;
+    case DS2_GEMM_X6_K_160: DS2_X6(true, 160, false); break;
+    case DS2_GEMM_X6_K_128: DS2_X6(true, 128, false); break;
+    case DS2_GEMM_F64_160:
+    case DS2_GEMM_F64_128:
+      launch_k64<TA, TB>(p.bn, grid, st, m, n, k, alpha, a, lda, stride_a, b, ldb, stride_b, beta,
+                         c, ldc, stride_c, bias, p.main_wgs, p.tail_tile0, p.tail_tiles, p.nsplit,
+                         p.kchunk, partial);
+      break;
+    case DS2_GEMM_F16:
+      launch_sgemm_t<TA, TB>(ch.va, ch.vb, grid, st, m, n, k, alpha, a, lda, stride_a, b, ldb,
+                             stride_b, beta, c, ldc, stride_c, bias, p.main_wgs, p.tail_tile0,
+                             p.tail_tiles, p.nsplit, p.kchunk, partial);
+      break;
+    case DS2_GEMM_BF16_STAGED:
+      hipLaunchKernelGGL((sbgemm_kernel<TA, TB>), grid, dim3(256), 0, st, m, n, k, alpha, a, lda,
+                         stride_a, b, ldb, stride_b, beta, c, ldc, stride_c, bias, p.main_wgs,
+                         p.tail_tile0, p.tail_tiles, p.nsplit, p.kchunk, partial);
+      break;
+    default: break;
   }
+#undef DS2_X6
+#undef DS2_H3
+}
+
+// kind 0: the fp32 family, 1: the staged-bf16 kernel.  Switches on gemm_select's choice only.
+static ds2_status_t sgemm_run(int kind, const char* where, int trans_a, int trans_b, int m,
+                              int n, int k, float alpha, const float* a, int64_t lda,
+                              int64_t stride_a, const float* b, int64_t ldb, int64_t stride_b,
+                              float beta, float* c, int64_t ldc, int64_t stride_c, int batch,
+                              const float* bias, void* ws, size_t ws_bytes,
+                              const unsigned* a_amax, const unsigned* b_amax,
+                              ds2_stream_t stream) {
+  const GemmCall g{kind, trans_a, trans_b, m, n, k, addr(a), lda, stride_a, addr(b), ldb,
+                   stride_b, addr(c), ldc, stride_c, batch, addr(bias), ws != nullptr, ws_bytes};
+  const GemmChoice ch = gemm_select(g, gemm_switches(), device_cus());
+  if (ch.status != DS2_OK || ch.rung == DS2_GEMM_NONE) return ch.status;
+  const GemmPlan& p = ch.p;
   float* partial = p.nsplit > 1 ? static_cast<float*>(ws) : nullptr;
-  const int64_t nwg = p.main_wgs + (int64_t)p.tail_tiles * batch * p.nsplit;
-  if (nwg > 0x7fffffff) return DS2_UNSUPPORTED_SHAPE;
-  dim3 grid(static_cast<unsigned>(nwg));
   hipStream_t st = as_stream(stream);
-  // every stage of every piece lies wholly inside [0, K): no per-element k check
-  const bool kalign = k % XS == 0 && (p.nsplit == 1 || p.kchunk % XS == 0);
-#define DS2_X6(TA_, TB_, KCHK_, BN_, M16_)                                                    \
-  hipLaunchKernelGGL((sxgemm2_kernel<TA_, TB_, KCHK_, BN_, 3, M16_>), grid, dim3(X2T), 0, st,   \
-                     m, n, k, alpha, a, lda, stride_a, b, ldb, stride_b, beta, c, ldc,          \
-                     stride_c, bias, p.main_wgs, p.tail_tile0, p.tail_tiles, p.nsplit,          \
-                     p.kchunk, partial, nullptr, nullptr)
-#define DS2_H3(TA_, TB_, BN_)                                                                   \
-  hipLaunchKernelGGL((sxgemm2_kernel<TA_, TB_, false, BN_, 2, true>), grid, dim3(X2T), 0, st,   \
-                     m, n, k, alpha, a, lda, stride_a, b, ldb, stride_b, beta, c, ldc,          \
-                     stride_c, bias, p.main_wgs, p.tail_tile0, p.tail_tiles, p.nsplit,          \
-                     p.kchunk, partial, a_amax, b_amax)
-  // the 16x16x32 form wherever every stage lies inside K (r4d: 0-15 % faster on the step's
-  // shapes, profiles/r4d_gemm_x6_m16_sk_ab.txt), the 32x32x16 form for a K tail
-  const bool m16 = x6 && kalign;
-  const size_t slabs = p.nsplit > 1 ? plan_ws(p, batch) : 0;
-  const bool h3 = m16 && batch == 1 && h3_enabled() && ws != nullptr &&
-                  ws_bytes >= slabs + h3_ws(m, n);
-  const unsigned* a_amax = a_amax_in;
-  const unsigned* b_amax = b_amax_in;
-  if (h3) {
-    const uintptr_t base = (reinterpret_cast<uintptr_t>(ws) + slabs + 255) & ~uintptr_t(255);
+  if (ch.h3) {
+    const uintptr_t base = (addr(ws) + ch.slabs + 255) & ~uintptr_t(255);
     unsigned* wa = reinterpret_cast<unsigned*>(base);
     unsigned* wb = wa + m;
     if (a_amax == nullptr) {
@@ -1802,42 +1635,23 @@ static ds2_status_t sgemm_run(int trans_a, int trans_b, int m, int n, int k, flo
       b_amax = wb;
     }
   }
-#define DS2_G(TA_, TB_)                                                                       \
-  if (h3 && p.bn == 160) DS2_H3(TA_, TB_, 160);                                               \
-  else if (h3) DS2_H3(TA_, TB_, 128);                                                         \
-  else if (m16 && p.bn == 160) DS2_X6(TA_, TB_, false, 160, true);                          \
-  else if (m16) DS2_X6(TA_, TB_, false, 128, true);                                          \
-  else if (x6 && kalign && p.bn == 160) DS2_X6(TA_, TB_, false, 160, false);                 \
-  else if (x6 && p.bn == 160) DS2_X6(TA_, TB_, true, 160, false);                            \
-  else if (x6 && kalign) DS2_X6(TA_, TB_, false, 128, false);                                \
-  else if (x6) DS2_X6(TA_, TB_, true, 128, false);                                           \
-  else if (k64)                                                                               \
-    launch_k64<TA_, TB_>(p.bn, grid, st, m, n, k, alpha, a, lda, stride_a, b, ldb, stride_b,   \
-                         beta, c, ldc, stride_c, bias, p.main_wgs, p.tail_tile0, p.tail_tiles,  \
-                         p.nsplit, p.kchunk, partial);                                         \
-  else                                                                                        \
-    launch_sgemm_t<TA_, TB_>(va, vb, grid, st, m, n, k, alpha, a, lda, stride_a, b, ldb,       \
-                             stride_b, beta, c, ldc, stride_c, bias, p.main_wgs, p.tail_tile0, \
-                             p.tail_tiles, p.nsplit, p.kchunk, partial)
-  if (!trans_a && !trans_b) {
-    DS2_G(0, 0);
-  } else if (!trans_a && trans_b) {
-    DS2_G(0, 1);
-  } else if (trans_a && !trans_b) {
-    DS2_G(1, 0);
-  } else {
-    DS2_G(1, 1);
-  }
-#undef DS2_G
-#undef DS2_X6
-#undef DS2_H3
+  if (!trans_a && !trans_b)
+    launch_rung<0, 0>(ch, st, m, n, k, alpha, a, lda, stride_a, b, ldb, stride_b, beta, c, ldc,
+                      stride_c, bias, partial, a_amax, b_amax);
+  else if (!trans_a && trans_b)
+    launch_rung<0, 1>(ch, st, m, n, k, alpha, a, lda, stride_a, b, ldb, stride_b, beta, c, ldc,
+                      stride_c, bias, partial, a_amax, b_amax);
+  else if (trans_a && !trans_b)
+    launch_rung<1, 0>(ch, st, m, n, k, alpha, a, lda, stride_a, b, ldb, stride_b, beta, c, ldc,
+                      stride_c, bias, partial, a_amax, b_amax);
+  else
+    launch_rung<1, 1>(ch, st, m, n, k, alpha, a, lda, stride_a, b, ldb, stride_b, beta, c, ldc,
+                      stride_c, bias, partial, a_amax, b_amax);
   if (p.nsplit > 1) {
-    const bool vec = p.bn % 4 == 0 && aligned16(c) && ldc % 4 == 0 && stride_c % 4 == 0 &&
-                     (bias == nullptr || aligned16(bias));
-    const int64_t total = (int64_t)batch * p.tail_tiles * p.bm * p.bn / (vec ? 4 : 1);
+    const int64_t total = (int64_t)batch * p.tail_tiles * p.bm * p.bn / (ch.vec ? 4 : 1);
     int g = cdiv(total, 256);
     if (g > 4096) g = 4096;
-    if (vec)
+    if (ch.vec)
       hipLaunchKernelGGL(splitk_reduce_kernel<true>, dim3(g), dim3(256), 0, st, partial, m, n,
                          p.nsplit, batch, p.tail_tile0, p.tail_tiles, alpha, beta, c, ldc,
                          stride_c, bias, p.bn, p.bm);
@@ -1846,7 +1660,28 @@ static ds2_status_t sgemm_run(int trans_a, int trans_b, int m, int n, int k, flo
                          p.nsplit, batch, p.tail_tile0, p.tail_tiles, alpha, beta, c, ldc,
                          stride_c, bias, p.bn, p.bm);
   }
-  return launch_status("ds2_sgemm");
+  return launch_status(where);
+}
+
+extern "C" ds2_status_t ds2_sgemm_ws(int trans_a, int trans_b, int m, int n, int k, float alpha,
+                                     const float* a, int64_t lda, int64_t stride_a,
+                                     const float* b, int64_t ldb, int64_t stride_b, float beta,
+                                     float* c, int64_t ldc, int64_t stride_c, int batch,
+                                     const float* bias, void* ws, size_t ws_bytes,
+                                     ds2_stream_t stream) {
+  return sgemm_run(0, "ds2_sgemm", trans_a, trans_b, m, n, k, alpha, a, lda, stride_a, b, ldb,
+                   stride_b, beta, c, ldc, stride_c, batch, bias, ws, ws_bytes, nullptr, nullptr,
+                   stream);
+}
+
+extern "C" ds2_status_t ds2_sgemm_amax_ws(int trans_a, int trans_b, int m, int n, int k,
+                                          float alpha, const float* a, int64_t lda,
+                                          const float* b, int64_t ldb, float beta, float* c,
+                                          int64_t ldc, const float* bias, const unsigned* a_amax,
+                                          const unsigned* b_amax, void* ws, size_t ws_bytes,
+                                          ds2_stream_t stream) {
+  return sgemm_run(0, "ds2_sgemm", trans_a, trans_b, m, n, k, alpha, a, lda, 0, b, ldb, 0, beta,
+                   c, ldc, 0, 1, bias, ws, ws_bytes, a_amax, b_amax, stream);
 }
 
 // bf16-operand GEMM (sbgemm_kernel): same contract as ds2_sgemm_ws; every operand must be
@@ -1854,7 +1689,7 @@ static ds2_status_t sgemm_run(int trans_a, int trans_b, int m, int n, int k, flo
 // < 2^31 bytes, else DS2_UNSUPPORTED_SHAPE (no silent fp32 fallback).
 extern "C" size_t ds2_sgemm_bf16_workspace_size(int m, int n, int k, int batch) {
   if (m <= 0 || n <= 0 || k <= 0 || batch <= 0) return 0;
-  return plan_ws(plan_bn(m, n, k, batch, 128, 2 * device_cus(), KB16, 1.0).p, batch);
+  return plan_ws(bf16_plan(m, n, k, batch, device_cus()), batch);
 }
 
 extern "C" ds2_status_t ds2_sgemm_bf16_ws(int trans_a, int trans_b, int m, int n, int k,
@@ -1863,45 +1698,9 @@ extern "C" ds2_status_t ds2_sgemm_bf16_ws(int trans_a, int trans_b, int m, int n
                                           int64_t stride_b, float beta, float* c, int64_t ldc,
                                           int64_t stride_c, int batch, const float* bias,
                                           void* ws, size_t ws_bytes, ds2_stream_t stream) {
-  if (m < 0 || n < 0 || k < 0 || batch < 0) return DS2_INVALID_VALUE;
-  if (m == 0 || n == 0 || batch == 0) return DS2_OK;
-  if (ldc < n) return DS2_INVALID_VALUE;
-  if (trans_a ? lda < m : lda < k) return DS2_INVALID_VALUE;
-  if (trans_b ? ldb < k : ldb < n) return DS2_INVALID_VALUE;
-  const bool va = aligned16(a) && (lda % 4 == 0) && (stride_a % 4 == 0) &&
-                  (trans_a ? (m % 4 == 0) : (k % 4 == 0));
-  const bool vb = aligned16(b) && (ldb % 4 == 0) && (stride_b % 4 == 0) &&
-                  (trans_b ? (k % 4 == 0) : (n % 4 == 0));
-  if (!va || !vb || !fits_rsrc(trans_a ? k : m, lda) || !fits_rsrc(trans_b ? n : k, ldb))
-    return DS2_UNSUPPORTED_SHAPE;
-  GemmPlan p = plan_bn(m, n, k, batch, 128, 2 * device_cus(), KB16, 1.0).p;
-  if (p.nsplit > 1 && (ws == nullptr || ws_bytes < plan_ws(p, batch))) {
-    p.nsplit = 1;
-    p.kchunk = std::max(k, 1);
-  }
-  float* partial = p.nsplit > 1 ? static_cast<float*>(ws) : nullptr;
-  const int64_t nwg = p.main_wgs + (int64_t)p.tail_tiles * batch * p.nsplit;
-  if (nwg > 0x7fffffff) return DS2_UNSUPPORTED_SHAPE;
-  dim3 grid(static_cast<unsigned>(nwg));
-  hipStream_t st = as_stream(stream);
-#define DS2_B(TA_, TB_)                                                                        \
-  hipLaunchKernelGGL((sbgemm_kernel<TA_, TB_>), grid, dim3(256), 0, st, m, n, k, alpha, a, lda, \
-                     stride_a, b, ldb, stride_b, beta, c, ldc, stride_c, bias, p.main_wgs,      \
-                     p.tail_tile0, p.tail_tiles, p.nsplit, p.kchunk, partial)
-  if (!trans_a && !trans_b) DS2_B(0, 0);
-  else if (!trans_a && trans_b) DS2_B(0, 1);
-  else if (trans_a && !trans_b) DS2_B(1, 0);
-  else DS2_B(1, 1);
-#undef DS2_B
-  if (p.nsplit > 1) {
-    const int64_t total = (int64_t)batch * p.tail_tiles * p.bm * p.bn;
-    int g = cdiv(total, 256);
-    if (g > 4096) g = 4096;
-    hipLaunchKernelGGL(splitk_reduce_kernel<false>, dim3(g), dim3(256), 0, st, partial, m, n, p.nsplit,
-                       batch, p.tail_tile0, p.tail_tiles, alpha, beta, c, ldc, stride_c, bias,
-                       p.bn, p.bm);
-  }
-  return launch_status("ds2_sgemm_bf16");
+  return sgemm_run(1, "ds2_sgemm_bf16", trans_a, trans_b, m, n, k, alpha, a, lda, stride_a, b,
+                   ldb, stride_b, beta, c, ldc, stride_c, batch, bias, ws, ws_bytes, nullptr,
+                   nullptr, stream);
 }
 
 extern "C" ds2_status_t ds2_sgemm(int trans_a, int trans_b, int m, int n, int k, float alpha,
@@ -1911,4 +1710,36 @@ extern "C" ds2_status_t ds2_sgemm(int trans_a, int trans_b, int m, int n, int k,
                                   ds2_stream_t stream) {
   return ds2_sgemm_ws(trans_a, trans_b, m, n, k, alpha, a, lda, stride_a, b, ldb, stride_b, beta,
                       c, ldc, stride_c, batch, bias, nullptr, 0, stream);
+}
+
+// Test hooks (include/ds2hip_test.h): the selection and the decode, host only
+extern "C" ds2_status_t ds2_test_sgemm_plan(int kind, int trans_a, int trans_b, int m, int n,
+                                            int k, unsigned long long a, int64_t lda,
+                                            int64_t stride_a, unsigned long long b, int64_t ldb,
+                                            int64_t stride_b, unsigned long long c, int64_t ldc,
+                                            int64_t stride_c, int batch, unsigned long long bias,
+                                            int have_ws, size_t ws_bytes, int amax_given,
+                                            int cus, int* out) {
+  if (kind < 0 || kind > 2 || out == nullptr || cus < 0) return DS2_INVALID_VALUE;
+  const GemmCall g{kind, trans_a, trans_b, m, n, k, static_cast<uintptr_t>(a), lda, stride_a,
+                   static_cast<uintptr_t>(b), ldb, stride_b, static_cast<uintptr_t>(c), ldc,
+                   stride_c, kind == 2 ? 1 : batch, static_cast<uintptr_t>(bias), have_ws != 0,
+                   ws_bytes};
+  const GemmChoice ch = gemm_select(g, gemm_switches(), cus > 0 ? cus : device_cus());
+  const int pre = ch.h3 ? 2 - (amax_given & 1) - ((amax_given >> 1) & 1) : 0;
+  const int vals[14] = {ch.rung, ch.p.bm, ch.p.bn, ch.p.main_wgs, ch.p.tail_tile0,
+                        ch.p.tail_tiles, ch.p.nsplit, ch.p.kchunk,
+                        static_cast<int>(std::min<int64_t>(ch.grid, 0x7fffffff)),
+                        static_cast<int>(ch.ws_need & 0xffffffffu),
+                        static_cast<int>((uint64_t)ch.ws_need >> 32), ch.vec ? 1 : 0,
+                        static_cast<int>(ch.status), pre};
+  std::copy(vals, vals + 14, out);
+  return DS2_OK;
+}
+
+extern "C" long long ds2_test_sgemm_cover(int m, int n, int k, int batch, int bm, int bn,
+                                          int main_wgs, int tail_tile0, int tail_tiles,
+                                          int nsplit, int kchunk, int grid) {
+  return gemm_cover_defects(m, n, k, batch, bm, bn, main_wgs, tail_tile0, tail_tiles, nsplit,
+                            kchunk, grid);
 }

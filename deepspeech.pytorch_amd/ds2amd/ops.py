@@ -120,7 +120,11 @@ def sgemm(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor, *, m: int, n: int, 
     ds2_sgemm_bf16_ws) -- the opt-in precision of BASELINE cfg4's RNN GEMMs.
     ``a_amax`` / ``b_amax``: int32 tensors holding the float bits of max |op(A)[m, :]| /
     max |op(B)[:, n]| (ds2_amax; an upper bound is valid): the fp16x3 kernel's row scales,
-    shared between GEMMs instead of recomputed by each (ds2_sgemm_amax_ws).
+    shared between GEMMs instead of recomputed by each (ds2_sgemm_amax_ws).  What a loose bound
+    costs: an element keeps 22 bits only within 2^17 of the CLAIMED row maximum and an absolute
+    error of 2^-39 of it below that, so |C - C64| <= 2^-20 |A||B| + 2^-38 (amax_A (x) sum_k |B|
+    + sum_k |A| (x) amax_B) element-wise; bounds up to 2^16 above the true maxima stay below 1e-7
+    componentwise, 2^20 reaches 1e-6 (DESIGN.md "fp16x3"; test_h3_scale_edges).
     """
     es = 4
     if (a_amax is not None or b_amax is not None) and not bf16:
@@ -145,6 +149,64 @@ def sgemm(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor, *, m: int, n: int, 
               float(beta), c.data_ptr() + es * c_off, ldc, 0, 1, _p(bias), _p(ws),
               0 if ws is None else ws.numel(), _stream())
     return c
+
+
+# the DS2_GEMM_* rungs of include/ds2hip_test.h (DESIGN.md "GEMM dispatch")
+GEMM_RUNGS = ("none", "h3_160", "h3_128", "x6_m16_160", "x6_m16_128", "x6_160", "x6_128",
+              "x6_k_160", "x6_k_128", "f64_160", "f64_128", "f16", "bf16_staged", "bf16_dma",
+              "bf16_dma_k")
+GEMM_KINDS = ("sgemm", "sgemm_bf16", "bgemm_nt")
+GemmPlan = collections.namedtuple(
+    "GemmPlan", "rung bm bn main_wgs tail_tile0 tail_tiles nsplit kchunk grid ws_bytes vec status "
+    "amax_passes")
+
+
+def gemm_plan(kind, *, m, n, k, trans_a=False, trans_b=False, a=256, lda, stride_a=0, b=256, ldb,
+              stride_b=0, c=256, ldc, stride_c=0, batch=1, bias=0, ws_bytes=None, amax_given=0,
+              cus=0) -> GemmPlan:
+    """What ds2_sgemm / ds2_sgemm_ws / ds2_sgemm_amax_ws ("sgemm"), ds2_sgemm_bf16_ws
+    ("sgemm_bf16") or ds2_bgemm_nt ("bgemm_nt") launches for the call under the current
+    DS2_GEMM_* environment: the library's own selection, host only (nothing launched; no device
+    with cus > 0).  a, b, c, bias: the addresses (only alignment and null-ness count);
+    ws_bytes None: no workspace.  status: what the entry point returns before any launch."""
+    out = (ctypes.c_int * 14)()
+    _lib.call("ds2_test_sgemm_plan", GEMM_KINDS.index(kind), int(trans_a), int(trans_b), m, n, k,
+              int(a), lda, stride_a, int(b), ldb, stride_b, int(c), ldc, stride_c, batch,
+              int(bias), int(ws_bytes is not None), int(ws_bytes or 0), amax_given, cus,
+              ctypes.addressof(out))
+    v = list(out)
+    return GemmPlan(GEMM_RUNGS[v[0]], *v[1:9], (v[10] << 32) | (v[9] & 0xffffffff), v[11], v[12],
+                    v[13])
+
+
+def gemm_cover(m, n, k, batch, p: GemmPlan) -> int:
+    """Defects of plan p's work decode over its whole grid (ds2_test_sgemm_cover; 0: every
+    (batch, tile) has its K range covered exactly once and no piece falls outside)."""
+    return _lib.size("ds2_test_sgemm_cover", m, n, k, batch, p.bm, p.bn, p.main_wgs, p.tail_tile0,
+                     p.tail_tiles, p.nsplit, p.kchunk, p.grid)
+
+
+def sgemm_plan(a, b, c, *, m, n, k, trans_a=False, trans_b=False, lda, ldb, ldc, bias=None,
+               a_off=0, b_off=0, c_off=0, bf16=False, a_amax=None, b_amax=None, **_) -> GemmPlan:
+    """The plan of the GEMM kernel sgemm() launches for the same arguments (it takes the
+    branches of sgemm below; the library decides)."""
+    ptr = dict(a=a.data_ptr() + 4 * a_off, b=b.data_ptr() + 4 * b_off, c=c.data_ptr() + 4 * c_off,
+               bias=0 if bias is None else bias.data_ptr())
+    dims = dict(m=m, n=n, k=k, ldc=ldc)
+    if (a_amax is not None or b_amax is not None) and not bf16:
+        given = int(a_amax is not None) | 2 * int(b_amax is not None)
+        nbytes = _lib.size("ds2_sgemm_workspace_size", m, n, k, 1)
+        return gemm_plan("sgemm", trans_a=trans_a, trans_b=trans_b, lda=lda, ldb=ldb,
+                         ws_bytes=nbytes or None, amax_given=given, **dims, **ptr)
+    if (bf16 and k % 8 == 0 and k > 0 and m > 0 and n > 0 and 2 * m * k < 2**31
+            and 2 * n * k < 2**31):
+        nbytes = _lib.size("ds2_bgemm_workspace_size", m, n, k)
+        return gemm_plan("bgemm_nt", lda=k, ldb=k, ws_bytes=nbytes or None, c=ptr["c"],
+                         bias=ptr["bias"], **dims)
+    kind = "sgemm_bf16" if bf16 else "sgemm"
+    nbytes = _lib.size("ds2_" + kind + "_workspace_size", m, n, k, 1)
+    return gemm_plan(kind, trans_a=trans_a, trans_b=trans_b, lda=lda, ldb=ldb,
+                     ws_bytes=nbytes or None, **dims, **ptr)
 
 
 def h3_enabled() -> bool:

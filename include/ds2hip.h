@@ -136,7 +136,11 @@ ds2_status_t ds2_pcm_decode(const int16_t* pcm, int64_t pcm_elems, const int64_t
  * trans_a = 0: A is [m][lda];  1: A is stored [k][lda] (A^T)
  * trans_b = 0: B is [k][ldb];  1: B is stored [n][ldb] (B^T)
  * Replaces cuBLAS behind cuDNN's RNN input projection / BPTT weight gradients
- * (ref model.py:90-91,104 nn.GRU) and nn.Linear (ref model.py:337).          */
+ * (ref model.py:90-91,104 nn.GRU) and nn.Linear (ref model.py:337).
+ * lda, ldb, ldc >= the stored row extent and any batch strides (0: one operand shared by the
+ * batch; entries of C must not overlap); elements of the allocations outside the logical
+ * matrices are neither read into the result nor written.  beta == 0: C is not read.  m, n or
+ * batch 0: DS2_OK, nothing done; k == 0 with m, n > 0: DS2_UNSUPPORTED_SHAPE.            */
 ds2_status_t ds2_sgemm(int trans_a, int trans_b, int m, int n, int k, float alpha,
                        const float* a, int64_t lda, int64_t stride_a,
                        const float* b, int64_t ldb, int64_t stride_b, float beta,
@@ -144,7 +148,10 @@ ds2_status_t ds2_sgemm(int trans_a, int trans_b, int m, int n, int k, float alph
                        const float* bias, ds2_stream_t stream);
 /* Same with a workspace: when the output grid cannot fill the chip and K is long
  * (weight gradients: M = 3H, N = In, K = T*N), K is split across workgroups and
- * the fp32 partials are reduced in a fixed order (deterministic).           */
+ * the fp32 partials are reduced in a fixed order (deterministic).  The size query is large
+ * enough for any kernel's plan.  A smaller workspace is legal and only slower: one that cannot
+ * hold the plan's split slabs is not used at all (as ds2_sgemm), one that holds the slabs but
+ * not the (m + n) * 4 + 512 bytes of fp16x3 row-scale words after them runs the bf16x6 kernel. */
 size_t ds2_sgemm_workspace_size(int m, int n, int k, int batch);
 ds2_status_t ds2_sgemm_ws(int trans_a, int trans_b, int m, int n, int k, float alpha,
                           const float* a, int64_t lda, int64_t stride_a,
@@ -159,7 +166,8 @@ ds2_status_t ds2_amax(const float* x, int rows, int cols, int64_t ld, unsigned* 
                       unsigned* col_amax, ds2_stream_t stream);
 /* ds2_sgemm_ws (batch 1) with the fp16x3 scales of the logical operand rows supplied by the
  * caller: a_amax[m] = max over k of |op(A)[m][k]|, b_amax[n] = max over k of |op(B)[k][n]|
- * (ds2_amax bits; an upper bound is valid and costs only precision below 2^-17 of it); NULL
+ * (ds2_amax bits; an upper bound is valid and costs only precision below 2^-17 of it: per
+ * element |C - C64| <= 2^-20 (|A||B|) + 2^-38 (a_amax (x) sum_k |B| + sum_k |A| (x) b_amax)); NULL
  * = computed here.  Ignored unless the fp16x3 kernel runs.                               */
 ds2_status_t ds2_sgemm_amax_ws(int trans_a, int trans_b, int m, int n, int k, float alpha,
                                const float* a, int64_t lda, const float* b, int64_t ldb,

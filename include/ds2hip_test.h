@@ -113,6 +113,58 @@ enum {
 ds2_status_t ds2_test_conv2d_plan(int dir, int n, int c_in, int h_in, int w_in, int c_out, int kh,
                                   int kw, int sh, int sw, int ph, int pw, int* out);
 
+/* ------------------------------------------------------------------------ */
+/* ds2_test_sgemm_plan: what ds2_sgemm / ds2_sgemm_ws / ds2_sgemm_amax_ws (kind 0),
+ * ds2_sgemm_bf16_ws (kind 1) or ds2_bgemm_nt (kind 2: trans and batch ignored, ld in bf16
+ * elements) would launch under the current DS2_GEMM_* environment.  Host only, no device
+ * needed (with cus > 0), nothing launched: it calls the function the entry points switch on
+ * (csrc/gemm_host.h gemm_select).  a, b, c, bias: the addresses as integers; only their low
+ * four bits are used, and whether they are 0.  have_ws / ws_bytes: the workspace the call
+ * passes.  amax_given: bit 0 / 1, the caller supplies the row maxima of op(A) / op(B).
+ * cus: the CU count the plan is made for (0: the current device's).  Returns DS2_OK whatever
+ * the call would return; out[14] =
+ *   [0] rung: a DS2_GEMM_* value, a row of DESIGN.md's GEMM dispatch table (NONE: nothing
+ *       launched -- an empty product or a rejected call)
+ *   [1] bm  [2] bn: the tile
+ *   [3] main_wgs: whole-tile workgroups   [4] tail_tile0  [5] tail_tiles
+ *   [6] nsplit  [7] kchunk: the K split of the tail tiles
+ *   [8] grid: workgroups of the GEMM kernel, main_wgs + tail_tiles * batch * nsplit
+ *   [9] [10] workspace bytes the rung uses, low and high 32 bits
+ *   [11] vec: the 16-byte form of the split reduce (bgemm: of the C rows)
+ *   [12] status: what the entry point returns before any launch
+ *   [13] row-maxima passes launched ahead of the GEMM (fp16x3 without caller maxima: 2) */
+enum {
+  DS2_GEMM_NONE = 0,
+  DS2_GEMM_H3_160 = 1,       /* sxgemm2_kernel<TA, TB, false, 160, 2, true>: fp16x3 */
+  DS2_GEMM_H3_128 = 2,       /* sxgemm2_kernel<TA, TB, false, 128, 2, true> */
+  DS2_GEMM_X6_M16_160 = 3,   /* sxgemm2_kernel<TA, TB, false, 160, 3, true>: bf16x6 16x16x32 */
+  DS2_GEMM_X6_M16_128 = 4,   /* sxgemm2_kernel<TA, TB, false, 128, 3, true> */
+  DS2_GEMM_X6_160 = 5,       /* sxgemm2_kernel<TA, TB, false, 160, 3, false>: 32x32x16 */
+  DS2_GEMM_X6_128 = 6,       /* sxgemm2_kernel<TA, TB, false, 128, 3, false> */
+  DS2_GEMM_X6_K_160 = 7,     /* sxgemm2_kernel<TA, TB, true, 160, 3, false>: k checked */
+  DS2_GEMM_X6_K_128 = 8,     /* sxgemm2_kernel<TA, TB, true, 128, 3, false> */
+  DS2_GEMM_F64_160 = 9,      /* sgemm64_kernel<TA, TB, 5, 64, 1>: fp32 MFMA, BK = 64 */
+  DS2_GEMM_F64_128 = 10,     /* sgemm64_kernel<TA, TB, 4, 64, 1> */
+  DS2_GEMM_F16 = 11,         /* sgemm_kernel<TA, TB, VA, VB>: fp32 MFMA, BK = 16 */
+  DS2_GEMM_BF16_STAGED = 12, /* sbgemm_kernel<TA, TB> (ds2_sgemm_bf16_ws) */
+  DS2_GEMM_BF16_DMA = 13,    /* bgemm_nt_kernel<false> (ds2_bgemm_nt) */
+  DS2_GEMM_BF16_DMA_K = 14   /* bgemm_nt_kernel<true>: k checked */
+};
+ds2_status_t ds2_test_sgemm_plan(int kind, int trans_a, int trans_b, int m, int n, int k,
+                                 unsigned long long a, int64_t lda, int64_t stride_a,
+                                 unsigned long long b, int64_t ldb, int64_t stride_b,
+                                 unsigned long long c, int64_t ldc, int64_t stride_c, int batch,
+                                 unsigned long long bias, int have_ws, size_t ws_bytes,
+                                 int amax_given, int cus, int* out);
+
+/* ds2_test_sgemm_cover: runs every workgroup id in [0, grid) through the kernels' own work
+ * decode (csrc/gemm_host.h decode_work / tile_coords; bg_decode for 256 x 256 tiles) on the
+ * host and returns the number of (batch, tile) pairs whose pieces do not partition [0, k)
+ * exactly once plus the number of decoded tiles outside the tile grid (a correct plan: 0);
+ * -1 for arguments no plan has (a non-positive size, grid < main_wgs).          */
+long long ds2_test_sgemm_cover(int m, int n, int k, int batch, int bm, int bn, int main_wgs,
+                               int tail_tile0, int tail_tiles, int nsplit, int kchunk, int grid);
+
 #ifdef __cplusplus
 }
 #endif

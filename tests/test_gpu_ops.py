@@ -32,6 +32,21 @@ def _gemm_mode(monkeypatch, mode):
     monkeypatch.setenv("DS2_GEMM_H3", "1" if mode.startswith("h3") else "0")
 
 
+def _sgemm_rungs(mode, ta, tb, m, n, k):
+    """The rungs (ops.GEMM_RUNGS, DESIGN.md "GEMM dispatch") a tight, 16-byte aligned fp32 call
+    may land on: operands that cannot be staged as float4 go to the BK=16 fp32 kernel whatever
+    the mode; DS2_GEMM_X6=0 to a BK=64 one (the plan's time model picks its width); a K tail
+    (K % 32) to the k-checked bf16x6 form, fp16x3 asked for or not."""
+    if (m if ta else k) % 4 or (k if tb else n) % 4:
+        return ("f16",)
+    if mode.startswith("fp32"):
+        return ("f64_160", "f64_128")
+    wide = "160" if n >= 256 else "128"
+    if k % 32:
+        return ("x6_k_" + wide,)
+    return (("h3_" if mode.startswith("h3") else "x6_m16_") + wide,)
+
+
 @pytest.mark.parametrize("x6", ["1", "0", "h3"])
 @pytest.mark.parametrize("ta,tb", [(0, 0), (0, 1), (1, 0), (1, 1)])
 @pytest.mark.parametrize("m,n,k", [(1, 1, 1), (37, 53, 29), (128, 128, 16), (300, 257, 513),
@@ -42,8 +57,15 @@ def test_sgemm(dev, ta, tb, m, n, k, x6, monkeypatch):
     """ds2_sgemm_ws vs fp64 at 1e-5: the bf16x6 kernel (256 x 160 tiles for N >= 256,
     256 x 128 below; its 16x16x32 form where every stage lies inside K, the 32x32x16 form for
     a K tail), the fp16x3 kernel ("h3", the same tiles on v_mfma_f32_16x16x32_f16 where every
-    stage lies inside K, else the bf16x6 kernel) and the fp32-MFMA kernels (DS2_GEMM_X6=0)."""
-    _gemm_mode(monkeypatch, {"1": "x6", "0": "fp32", "h3": "h3"}[x6])
+    stage lies inside K, else the bf16x6 kernel) and the fp32-MFMA kernels (DS2_GEMM_X6=0).
+    Each case asserts the rung it reaches.  The mode in a case's name is what was asked for,
+    not what runs: of these shapes only (300, 260, 1024) has every stage inside K, so it alone
+    reaches fp16x3 ("h3") and the 16x16x32 form ("1"); the others with float4-stageable operands
+    run the k-checked bf16x6 form in both modes, and (1, 1, 1), (37, 53, 29), (300, 257, 513)
+    and the transposes that make 515 or 257 the contiguous extent the BK=16 fp32 kernel in
+    all three."""
+    mode = {"1": "x6", "0": "fp32", "h3": "h3"}[x6]
+    _gemm_mode(monkeypatch, mode)
     g = torch.Generator().manual_seed(m * 7 + n * 3 + k)
     a = torch.randn(k, m, generator=g) if ta else torch.randn(m, k, generator=g)
     b = torch.randn(n, k, generator=g) if tb else torch.randn(k, n, generator=g)
@@ -52,8 +74,12 @@ def test_sgemm(dev, ta, tb, m, n, k, x6, monkeypatch):
     ref = 0.5 * ((a.t() if ta else a).double() @ (b.t() if tb else b).double()) \
         + 0.25 * c0.double() + bias.double()
     ad, bd, cd = a.to(dev), b.to(dev), c0.to(dev).clone()
-    ops.sgemm(ad, bd, cd, m=m, n=n, k=k, trans_a=bool(ta), trans_b=bool(tb),
-              lda=ad.shape[1], ldb=bd.shape[1], ldc=n, alpha=0.5, beta=0.25, bias=bias.to(dev))
+    args = dict(m=m, n=n, k=k, trans_a=bool(ta), trans_b=bool(tb), lda=ad.shape[1],
+                ldb=bd.shape[1], ldc=n, alpha=0.5, beta=0.25, bias=bias.to(dev))
+    plan = ops.sgemm_plan(ad, bd, cd, **args)
+    assert plan.rung in _sgemm_rungs(mode, ta, tb, m, n, k), plan
+    assert (plan.nsplit > 1) == (k >= 512), plan      # "split-K path": K = 5000, and 513-1024
+    ops.sgemm(ad, bd, cd, **args)
     torch.cuda.synchronize()
     _close(cd, ref, 1e-5, "sgemm")
 
@@ -84,9 +110,15 @@ def test_sgemm_full_rounds_plus_split_tail(dev, ta, tb, mode, monkeypatch):
         buf = torch.empty(ad.numel() + 1, device=dev)
         buf[1:].copy_(ad.reshape(-1))
         ad, a_off = buf, 1
-    ops.sgemm(ad, bd, cd, m=m, n=n, k=k, trans_a=bool(ta), trans_b=bool(tb),
-              lda=lda, ldb=bd.shape[1], ldc=n, alpha=0.5, beta=0.25, bias=bias.to(dev),
-              a_off=a_off)
+    args = dict(m=m, n=n, k=k, trans_a=bool(ta), trans_b=bool(tb), lda=lda, ldb=bd.shape[1],
+                ldc=n, alpha=0.5, beta=0.25, bias=bias.to(dev), a_off=a_off)
+    plan = ops.sgemm_plan(ad, bd, cd, **args)
+    assert plan.rung in (("f16",) if mode == "unaligned" else _sgemm_rungs(mode, ta, tb, m, n, k)), plan
+    assert plan.nsplit > 1 and plan.tail_tiles > 0, plan
+    # whole rounds ahead of the split tail: not for the "-narrow" shapes, whose 30 (58) tiles
+    # are a tail only
+    assert (plan.main_wgs > 0) == (not mode.endswith("narrow")), plan
+    ops.sgemm(ad, bd, cd, **args)
     torch.cuda.synchronize()
     _close(cd, ref, 1e-5, "sgemm main+tail")
 
@@ -233,7 +265,11 @@ def test_sgemm_x6_nonfinite_operands(dev, ta, tb, monkeypatch):
 def test_sgemm_bf16(dev, ta, tb, m, n, k):
     """bf16-operand GEMM (BASELINE cfg4): operands rounded to bf16 (nearest even) on the
     way in, exact products, fp32 accumulation.  Reference: the same bf16 roundings done by
-    torch on the host, multiplied in fp64 -- so only the fp32 summation differs (1e-5)."""
+    torch on the host, multiplied in fp64 -- so only the fp32 summation differs (1e-5).
+    Through ops.sgemm(bf16=True), so K % 8 == 0 runs ds2_bgemm_nt on bf16 copies (K = 64: its
+    unmasked form; 5000 and 2080: the masked last K-tile, split) and the rest the staged
+    kernel ds2_sgemm_bf16_ws (K = 4, 28, 132 unsplit; 516 split in two).  Neither "split-K
+    tail" shape has whole rounds on 256 CUs: 95 and 2 tiles, and 210 for "rounds + tail"."""
     g = torch.Generator().manual_seed(m * 7 + n * 3 + k + 1)
     a = torch.randn(k, m, generator=g) if ta else torch.randn(m, k, generator=g)
     b = torch.randn(n, k, generator=g) if tb else torch.randn(k, n, generator=g)
@@ -243,9 +279,12 @@ def test_sgemm_bf16(dev, ta, tb, m, n, k):
     ref = 0.5 * ((rb(a).t() if ta else rb(a)) @ (rb(b).t() if tb else rb(b))) \
         + 0.25 * c0.double() + bias.double()
     ad, bd, cd = a.to(dev), b.to(dev), c0.to(dev).clone()
-    ops.sgemm(ad, bd, cd, m=m, n=n, k=k, trans_a=bool(ta), trans_b=bool(tb),
-              lda=ad.shape[1], ldb=bd.shape[1], ldc=n, alpha=0.5, beta=0.25, bias=bias.to(dev),
-              bf16=True)
+    args = dict(m=m, n=n, k=k, trans_a=bool(ta), trans_b=bool(tb), lda=ad.shape[1],
+                ldb=bd.shape[1], ldc=n, alpha=0.5, beta=0.25, bias=bias.to(dev), bf16=True)
+    plan = ops.sgemm_plan(ad, bd, cd, **args)
+    assert plan.rung == ("bf16_staged" if k % 8 else "bf16_dma_k" if k % 64 else "bf16_dma"), plan
+    assert (plan.nsplit > 1) == (k >= 516), plan
+    ops.sgemm(ad, bd, cd, **args)
     torch.cuda.synchronize()
     _close(cd, ref, 1e-5, "sgemm bf16")
     # and it is a bf16 product: far from the fp32 one at this scale
@@ -257,13 +296,16 @@ def test_sgemm_bf16(dev, ta, tb, m, n, k):
 
 @pytest.mark.parametrize("m,n,k", [(256, 256, 64), (300, 200, 136), (1000, 520, 1024),
                                    (513, 777, 4104), (2048, 4096, 1312),
-                                   (4096, 1024, 32064 // 4), (64, 1024, 32064)])
+                                   (4096, 1024, 32064 // 4), (64, 1024, 32064),
+                                   (4352, 4096, 136)])
 def test_bgemm_nt(dev, m, n, k):
     """ds2_bgemm_nt (bf16 operands in HBM, the 256 x 256 LDS-DMA ping-pong kernel): partial
     tiles in M and N, K not a multiple of 64 (the masked last K-tile), whole rounds plus a
-    split-K tail, one tile row with deep K.  Reference: the same bf16 values multiplied in
-    fp64 -- only the fp32 summation order differs (1e-5).  ds2_cvt_bf16 (RNE) equals torch's
-    bf16 rounding bit for bit, plain and transposed."""
+    split-K tail ((4352, 4096, 136): 272 tiles, a round of one per CU and 16 tail tiles; the
+    other shapes have at most 128 tiles, a split tail only), one tile row with deep K.
+    Reference: the same bf16 values multiplied in fp64 -- only the fp32 summation order differs
+    (1e-5).  ds2_cvt_bf16 (RNE) equals torch's bf16 rounding bit for bit, plain and
+    transposed."""
     g = torch.Generator().manual_seed(m + n + k)
     a32 = torch.randn(m, k, generator=g).to(dev)
     b32 = torch.randn(k, n, generator=g).to(dev)          # n-contiguous: the transposing copy
@@ -274,6 +316,15 @@ def test_bgemm_nt(dev, m, n, k):
     assert torch.equal(a, a32.to(torch.bfloat16))
     assert torch.equal(bt, b32.t().contiguous().to(torch.bfloat16))
     c = c0.clone()
+    nbytes = _lib.size("ds2_bgemm_workspace_size", m, n, k)
+    plan = ops.gemm_plan("bgemm_nt", m=m, n=n, k=k, a=a.data_ptr(), lda=k, b=bt.data_ptr(), ldb=k,
+                         c=c.data_ptr(), ldc=n, bias=bias.data_ptr(), ws_bytes=nbytes or None)
+    assert plan.rung == ("bf16_dma_k" if k % 64 else "bf16_dma"), plan
+    assert (plan.nsplit > 1) == (k > 64), plan
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    tiles = -(-m // 256) * -(-n // 256)
+    assert plan.main_wgs == (tiles // cus * cus if tiles % cus else 0), plan
+    assert (plan.main_wgs > 0) == ((m, n, k) == (4352, 4096, 136)) or cus != 256, plan
     ops.bgemm_nt(a, bt, c, alpha=0.5, beta=0.25, bias=bias)
     torch.cuda.synchronize()
     ref = 0.5 * (a.double() @ bt.double().t()) + 0.25 * c0.double() + bias.double()

@@ -10,6 +10,9 @@
 // Per-class sums walk a per-utterance class->state list in LDS, so results are
 // deterministic (no float atomics).
 //
+// Forced alignment (ds2_ctc_align): the max-plus form of the alpha scan with one back-pointer
+// byte per (t, s) and a back-trace staged through LDS; see ctc_align_kernel.
+//
 // Greedy: one wave per utterance; argmax (first maximum) per frame, then a
 // ballot/mbcnt compaction of the frames that survive blank/repeat removal
 // (ref decoder.py:165-197).
@@ -38,7 +41,12 @@ struct CtcWs {
   int* cls_pos;      // [n][max_label_len]  label positions grouped by class
 };
 
-// 1) log-softmax of every (t, n) row, one wave per row (C <= 64)
+// 1) log-softmax of every (t, n) row, one wave per row (C <= 64).  kFromMax (the alignment;
+//    the loss keeps v - lse bit for bit): (v - m) - log1p(sum over the classes but the first
+//    maximum), which has no cancellation at |m|: v - lse rounds lse to an ulp of |m| (1e-6 at
+//    12), an absolute error per frame that a peaked row's log-probability (-1e-4) and a score
+//    summed over hundreds of such frames cannot absorb.
+template <bool kFromMax>
 __global__ void ctc_logsoftmax_kernel(const float* __restrict__ acts, int t_max, int n, int c,
                                       float* __restrict__ lp) {
   const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;   // row = t*n + b
@@ -48,9 +56,16 @@ __global__ void ctc_logsoftmax_kernel(const float* __restrict__ acts, int t_max,
   const int b = row - t * n;
   const float v = lane < c ? acts[(int64_t)row * c + lane] : -INFINITY;
   const float m = wave_max(v);
-  const float e = lane < c ? expf(v - m) : 0.f;
-  const float lse = m + logf(wave_sum(e));
-  if (lane < c) lp[((int64_t)b * t_max + t) * c + lane] = v - lse;
+  if constexpr (kFromMax) {
+    const int first = __ffsll(static_cast<long long>(__ballot(v == m))) - 1;
+    const float e = (lane < c && lane != first) ? expf(v - m) : 0.f;
+    const float l1p = log1pf(wave_sum(e));
+    if (lane < c) lp[((int64_t)b * t_max + t) * c + lane] = (v - m) - l1p;
+  } else {
+    const float e = lane < c ? expf(v - m) : 0.f;
+    const float lse = m + logf(wave_sum(e));
+    if (lane < c) lp[((int64_t)b * t_max + t) * c + lane] = v - lse;
+  }
 }
 
 // 2) per utterance: label offset and the class -> label-position lists
@@ -278,6 +293,187 @@ __global__ void ctc_grad_kernel(int t_max, int n, int c, int blank, int zero_inf
       }
     }
     g[lane] = expf(lpk) - acc;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// CTC forced alignment (ds2_ctc_align): the max-plus form of the alpha scan above.  One
+// workgroup per utterance, the same state ownership, log-probability staging and rescaling as
+// ctc_scan_kernel (a uniform shift changes no argmax; the shifts are summed in fp64 for the
+// score).  Per (t, s) one back-pointer byte (0 stay, 1 from s - 1, 2 from s - 2) goes to the
+// workspace.  Tie rule: a predecessor replaces the best so far only if strictly greater, tried
+// in the order stay, s - 1, s - 2; the final state is S - 1 unless v(S - 2) > v(S - 1).
+// Back-trace: a path moves down by at most 2 states per frame, so the kAlignChunk frames
+// that end in state s_hi only visit states [s_hi - 2 kAlignChunk, s_hi]: that window of their
+// back-pointer rows is staged into LDS (in the log-probability stage's place) with every load
+// in flight at once, one lane walks it (an LDS read per frame, no dependent global load), and
+// all threads then write the chunk's states and the spans of the labels it shows.
+constexpr int kAlignChunk = 128;                       // frames of back-pointers per LDS stage
+constexpr int kAlignWinDw = kAlignChunk / 2 + 2;       // dwords of a staged row: 2 K + 1 states
+                                                       // from a 4-byte aligned start
+constexpr int kAlignPer = (kAlignChunk * kAlignWinDw + kScanThreads - 1) / kScanThreads;
+static_assert((kAlignChunk * kAlignWinDw + kAlignChunk + 2) * 4 <= kScanChunk * 64 * 4,
+              "the back-trace stage and its path slice take the log-probability stage's LDS");
+
+__global__ __launch_bounds__(kScanThreads) void ctc_align_kernel(
+    const float* __restrict__ lp_all, int t_max, int c, const int* __restrict__ labels,
+    const int* __restrict__ label_lens, const int* __restrict__ act_lens,
+    const int* __restrict__ offs, int blank, int max_l, int bp_stride,
+    unsigned char* __restrict__ bp_all, int* __restrict__ states_all, int* __restrict__ spans_all,
+    float* __restrict__ scores) {
+  __shared__ float rows[2][kCtcMaxS];
+  __shared__ float wmax[2][kScanThreads / 64];
+  __shared__ int lab_s[kMaxLabel];
+  __shared__ float lpc[kScanChunk * 64];
+  __shared__ int s_cur, s_nxt;         // back-trace: the states at a chunk's last frame and after it
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int L = min(label_lens[b], max_l);   // host: label lengths <= max_l (rows hold 2 max_l + 1)
+  int T = act_lens[b];
+  T = T > t_max ? t_max : (T < 0 ? 0 : T);
+  const int S = 2 * L + 1;
+  const int off_l = offs[b];
+  for (int i = tid; i < L; i += blockDim.x) lab_s[i] = labels[off_l + i];
+  __syncthreads();
+  const float* lp = lp_all + (int64_t)b * t_max * c;
+  unsigned char* bp = bp_all + (int64_t)b * t_max * bp_stride;
+  int* states = states_all + (int64_t)b * t_max;
+  int* spans = spans_all + 2 * (int64_t)off_l;
+  int ls[kScanPer];
+  bool skip[kScanPer];
+#pragma unroll
+  for (int k = 0; k < kScanPer; ++k) {
+    const int st = tid + kScanThreads * k;
+    ls[k] = st < S ? label_at(lab_s, st, blank) : blank;
+    skip[k] = st < S && st >= 2 && ls[k] != blank && ls[k] != label_at(lab_s, st - 2, blank);
+  }
+  int cur = 0;
+  int f1 = 0;                          // frames [f0, f1) staged in lpc
+  int f0 = 0;
+  double off = 0.0;                    // the row maxima subtracted so far (true = stored + off)
+  for (int t = 0; t < T; ++t) {
+    if (t >= f1) {                     // uniform: stage the next chunk of frames
+      f0 = t;
+      f1 = min(T, t + kScanChunk);
+      const int cnt = (f1 - f0) * c;
+      for (int i = tid; i < cnt; i += kScanThreads) lpc[i] = lp[(int64_t)f0 * c + i];
+      __syncthreads();
+    }
+    const float* lpt = lpc + (t - f0) * c;
+    const float* prv = rows[cur ^ 1];
+    float msub = 0.f;                  // the previous row's maximum, subtracted from this row
+    if (t > 0 && (t & (kScanRescale - 1)) == 0) {
+      float m = wmax[cur ^ 1][0];
+#pragma unroll
+      for (int w = 1; w < kScanThreads / 64; ++w) m = fmaxf(m, wmax[cur ^ 1][w]);
+      msub = m == -INFINITY ? 0.f : m;
+      off += msub;
+    }
+    float lm = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < kScanPer; ++k) {
+      const int st = tid + kScanThreads * k;
+      if (st >= S) break;
+      float v;
+      int d = 0;
+      if (t == 0) {
+        v = st <= 1 ? lpt[ls[k]] : -INFINITY;
+      } else {
+        v = prv[st];
+        if (st >= 1) {
+          const float u = prv[st - 1];
+          if (u > v) { v = u; d = 1; }
+        }
+        if (skip[k]) {
+          const float u = prv[st - 2];
+          if (u > v) { v = u; d = 2; }
+        }
+        v = (v == -INFINITY) ? -INFINITY : v + (lpt[ls[k]] - msub);
+      }
+      lm = fmaxf(lm, v);
+      rows[cur][st] = v;
+      bp[(int64_t)t * bp_stride + st] = static_cast<unsigned char>(d);
+    }
+    if ((t & (kScanRescale - 1)) == kScanRescale - 1) {   // uniform
+      lm = wave_max_dpp(lm);
+      if ((tid & 63) == 0) wmax[cur][tid >> 6] = lm;
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+  // the final state and the score; s_cur < 0: no alignment (or no frames)
+  if (tid == 0) {
+    int sf = -1;
+    float sc = (T == 0 && L == 0) ? 0.f : -INFINITY;
+    if (T > 0) {
+      const float* last = rows[cur ^ 1];
+      float v = last[S - 1];
+      sf = S - 1;
+      if (S >= 2 && last[S - 2] > v) { v = last[S - 2]; sf = S - 2; }
+      if (v == -INFINITY) sf = -1;
+      else sc = static_cast<float>((double)v + off);
+    }
+    scores[b] = sc;
+    s_cur = sf;
+    s_nxt = -1;
+  }
+  __syncthreads();                     // also: this workgroup's back-pointer stores are visible
+  const bool feasible = s_cur >= 0;
+  const int t_end = feasible ? T : 0;  // states [t_end, t_max) = -1
+  for (int t = t_end + tid; t < t_max; t += kScanThreads) states[t] = -1;
+  if (!feasible) {
+    if (!(T == 0 && L == 0))
+      for (int i = tid; i < 2 * L; i += kScanThreads) spans[i] = -1;
+    return;
+  }
+  unsigned* win = reinterpret_cast<unsigned*>(lpc);
+  const unsigned char* winb = reinterpret_cast<const unsigned char*>(lpc);
+  int* path = reinterpret_cast<int*>(lpc) + kAlignChunk * kAlignWinDw;   // [nf + 2]
+  const int sw = bp_stride >> 2;       // dwords of a back-pointer row
+  for (int e1 = T; e1 > 0; e1 -= kAlignChunk) {
+    const int e0 = max(0, e1 - kAlignChunk);
+    const int nf = e1 - e0;
+    const int s_hi = s_cur;
+    const int w0 = max(0, s_hi - 2 * kAlignChunk) >> 2;
+    // every load of the chunk issued before the first is stored: addresses are clamped into
+    // the chunk's rows (a clamped dword is never walked), so no load sits behind a branch
+    unsigned wr[kAlignPer];
+#pragma unroll
+    for (int q = 0; q < kAlignPer; ++q) {
+      const int i = tid + kScanThreads * q;
+      const int r = min(i / kAlignWinDw, nf - 1);
+      const int j = i % kAlignWinDw;
+      wr[q] = reinterpret_cast<const unsigned*>(bp + (int64_t)(e0 + r) * bp_stride)[
+          min(w0 + j, sw - 1)];
+    }
+#pragma unroll
+    for (int q = 0; q < kAlignPer; ++q) {
+      const int i = tid + kScanThreads * q;
+      if (i < nf * kAlignWinDw) win[i] = wr[q];
+    }
+    __syncthreads();
+    if (tid == 0) {
+      int s = s_hi;
+      path[nf + 1] = s_nxt;
+      for (int t = e1 - 1; t >= e0; --t) {
+        path[t - e0 + 1] = s;
+        const int d = winb[(t - e0) * (kAlignWinDw * 4) + (s - 4 * w0)];
+        s = t > 0 ? s - min(d, s) : -1;
+      }
+      path[0] = s;                     // the state at frame e0 - 1 (-1 before the first frame)
+      s_nxt = path[1];
+      s_cur = s;
+    }
+    __syncthreads();
+    for (int i = tid; i < nf; i += kScanThreads) {
+      const int s = path[i + 1];
+      states[e0 + i] = s;
+      if (s & 1) {
+        if (path[i] != s) spans[s - 1] = e0 + i;           // 2 * (s >> 1)
+        if (path[i + 2] != s) spans[s] = e0 + i + 1;
+      }
+    }
+    __syncthreads();
   }
 }
 
@@ -1586,7 +1782,7 @@ ds2_status_t ds2_ctc_loss(const float* acts, int t_max, int n, int c, const int*
   int* cls_pos = reinterpret_cast<int*>(p);
   const int rows = t_max * n;
   if (rows > 0)
-    hipLaunchKernelGGL(ctc_logsoftmax_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, acts, t_max,
+    hipLaunchKernelGGL(ctc_logsoftmax_kernel<false>, dim3(cdiv(rows, 4)), dim3(256), 0, st, acts, t_max,
                        n, c, lp);
   hipLaunchKernelGGL(ctc_prep_kernel, dim3(n), dim3(64), 0, st, labels, label_lens, n, c,
                      ml, offs, cls_start, cls_pos);
@@ -1596,6 +1792,50 @@ ds2_status_t ds2_ctc_loss(const float* acts, int t_max, int n, int c, const int*
                      n, c, blank, zero_infinity, act_lens, label_lens, lp, alpha, beta, shift, nll,
                      cls_start, cls_pos, s_max, ml, costs, grads);
   return launch_status("ds2_ctc_loss");
+}
+
+// log-softmax [n][t_max][64], back-pointer bytes [n][t_max][align4(2 L + 1)], then the prep
+// kernel's outputs (label offsets and its class lists, which the alignment does not read)
+static inline size_t align_bp_stride(int max_label_len) {
+  return ((size_t)2 * max_label_len + 1 + 3) & ~(size_t)3;
+}
+
+size_t ds2_ctc_align_workspace_size(int t_max, int n, int max_label_len) {
+  const size_t ml = max_label_len > 0 ? max_label_len : 1;
+  return al256((size_t)n * t_max * 64 * sizeof(float)) +
+         al256((size_t)n * t_max * align_bp_stride(max_label_len)) +
+         al256((size_t)n * sizeof(int)) + al256((size_t)n * 65 * sizeof(int)) +
+         al256((size_t)n * ml * sizeof(int)) + 256;
+}
+
+ds2_status_t ds2_ctc_align(const float* acts, int t_max, int n, int c, const int* labels,
+                           const int* label_lens, const int* act_lens, int max_label_len,
+                           int blank, int* states, int* spans, float* scores, void* ws,
+                           size_t ws_bytes, ds2_stream_t stream) {
+  if (t_max < 0 || n < 0 || c < 1 || c > 64 || blank < 0 || blank >= c) return DS2_INVALID_VALUE;
+  if (max_label_len < 0 || max_label_len > kMaxLabel) return DS2_UNSUPPORTED_SHAPE;
+  if (n == 0) return DS2_OK;
+  if (ws == nullptr || ws_bytes < ds2_ctc_align_workspace_size(t_max, n, max_label_len))
+    return DS2_WORKSPACE_TOO_SMALL;
+  hipStream_t st = as_stream(stream);
+  const int ml = max_label_len > 0 ? max_label_len : 1;
+  const int bp_stride = static_cast<int>(align_bp_stride(max_label_len));
+  char* p = static_cast<char*>(ws);
+  float* lp = reinterpret_cast<float*>(p); p += al256((size_t)n * t_max * 64 * sizeof(float));
+  auto* bp = reinterpret_cast<unsigned char*>(p); p += al256((size_t)n * t_max * bp_stride);
+  int* offs = reinterpret_cast<int*>(p); p += al256((size_t)n * sizeof(int));
+  int* cls_start = reinterpret_cast<int*>(p); p += al256((size_t)n * 65 * sizeof(int));
+  int* cls_pos = reinterpret_cast<int*>(p);
+  const int rows = t_max * n;
+  if (rows > 0)
+    hipLaunchKernelGGL(ctc_logsoftmax_kernel<true>, dim3(cdiv(rows, 4)), dim3(256), 0, st, acts, t_max,
+                       n, c, lp);
+  hipLaunchKernelGGL(ctc_prep_kernel, dim3(n), dim3(64), 0, st, labels, label_lens, n, c,
+                     ml, offs, cls_start, cls_pos);
+  hipLaunchKernelGGL(ctc_align_kernel, dim3(n), dim3(kScanThreads), 0, st, lp, t_max, c, labels,
+                     label_lens, act_lens, offs, blank, max_label_len, bp_stride, bp, states,
+                     spans, scores);
+  return launch_status("ds2_ctc_align");
 }
 
 ds2_status_t ds2_greedy_decode(const float* probs, int n, int t_max, int c, int64_t stride_n,

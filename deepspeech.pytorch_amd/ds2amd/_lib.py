@@ -156,6 +156,9 @@ _PROTOS = {
     "ds2_ctc_workspace_size": (_sz, [_c_int, _c_int, _c_int]),
     "ds2_ctc_loss": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _c_int,
                               _vp, _vp, _vp, _sz, _vp]),
+    "ds2_ctc_align_workspace_size": (_sz, [_c_int, _c_int, _c_int]),
+    "ds2_ctc_align": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _vp,
+                               _vp, _vp, _vp, _sz, _vp]),
     "ds2_greedy_decode": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_i64, _c_i64, _vp, _c_int, _vp,
                                    _vp, _vp, _vp, _vp]),
     "ds2_edit_distance": (_c_int, [_vp, _c_i64, _vp, _vp, _vp, _vp, _c_int, _c_int, _vp, _vp,

@@ -673,6 +673,27 @@ def ctc_loss_raw(acts_tnc, labels, act_lens, label_lens, max_label_len, blank=0,
     return costs, grads
 
 
+def ctc_align_raw(acts_tnc, labels, act_lens, label_lens, max_label_len, blank=0):
+    """Device CTC forced alignment (ds2_ctc_align).  acts [T,N,C] unnormalised float32; labels
+    (concatenated), act_lens [N], label_lens [N] int32 device tensors.
+
+    Returns (states [N,T] int32, spans [sum(label_lens), 2] int32, scores [N] float32)."""
+    acts = _need(acts_tnc, "ctc_align.acts")
+    labels = _need(labels, "ctc_align.labels", _I32)
+    act_lens = _need(act_lens, "ctc_align.act_lens", _I32)
+    label_lens = _need(label_lens, "ctc_align.label_lens", _I32)
+    t, n, c = acts.shape
+    states = torch.empty(n, t, device=acts.device, dtype=_I32)
+    spans = torch.empty(labels.numel(), 2, device=acts.device, dtype=_I32)
+    scores = torch.empty(n, device=acts.device, dtype=_F32)
+    ws = _ws(_lib.size("ds2_ctc_align_workspace_size", t, n, max_label_len), acts.device)
+    _lib.call("ds2_ctc_align", acts.data_ptr(), t, n, c, labels.data_ptr(),
+              label_lens.data_ptr(), act_lens.data_ptr(), int(max_label_len), int(blank),
+              states.data_ptr(), spans.data_ptr(), scores.data_ptr(), ws.data_ptr(), ws.numel(),
+              _stream())
+    return states, spans, scores
+
+
 def greedy_decode_raw(probs: torch.Tensor, sizes: Optional[torch.Tensor], blank: int = 0,
                       want_argmax: bool = False):
     """Device argmax + CTC collapse.  probs [N,T,C] (any strides, fp32).

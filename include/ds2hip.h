@@ -529,6 +529,30 @@ ds2_status_t ds2_ctc_loss(const float* acts, int t_max, int n, int c, const int*
                           int blank, int zero_infinity, float* costs, float* grads, void* ws,
                           size_t ws_bytes, ds2_stream_t stream);
 
+/* CTC forced alignment (Viterbi): the best frame-level alignment of a known transcript.
+ * Inputs, limits (c <= 64, max_label_len <= 1024) and status codes are those of
+ * ds2_ctc_loss; softmax is applied internally.  Per utterance b, with
+ * T = clamp(act_lens[b], 0, t_max), L = label_lens[b] and S = 2 L + 1 extended states
+ * (even s: blank, odd s: labels[s >> 1]), the alignment is the state sequence
+ * s_0 .. s_{T-1} that maximises sum_t log p[t][l'(s_t)] with s_0 in {0, 1}, s_{T-1} in
+ * {S - 2, S - 1} and steps of +0, +1 or +2, the +2 step only onto a non-blank state whose
+ * label differs from the one two states back.
+ * states [n][t_max]: s_t for t < T, -1 for t >= T.
+ * spans  [sum of label_lens][2]: for label i of utterance b (row label offset + i) the
+ *   first frame in state 2 i + 1 and one past the last.
+ * scores [n]: the path's log-probability (0 for T = 0, L = 0).
+ * An infeasible utterance (L + repeats > T) gets score -inf and -1 in all of its states
+ * and spans.
+ * Ties: a predecessor replaces the best so far only if strictly greater, and the
+ * predecessors are tried in the order stay, s - 1, s - 2; the final state is S - 1 unless
+ * v(S - 2) > v(S - 1).  Deterministic: two calls give bit-identical outputs.
+ * Workspace: the log-softmax rows plus one back-pointer byte per (b, t, s).      */
+size_t ds2_ctc_align_workspace_size(int t_max, int n, int max_label_len);
+ds2_status_t ds2_ctc_align(const float* acts, int t_max, int n, int c, const int* labels,
+                           const int* label_lens, const int* act_lens, int max_label_len,
+                           int blank, int* states, int* spans, float* scores, void* ws,
+                           size_t ws_bytes, ds2_stream_t stream);
+
 /* ------------------------------------------------------------------------ */
 /* GreedyDecoder.decode (ref decoder.py:182-197, process_string :165-180):
  * argmax over C (first maximum) of probs[n][t][c] (strides in elements), then

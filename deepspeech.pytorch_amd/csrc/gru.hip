@@ -31,11 +31,15 @@ constexpr int kTraceS0 = 100, kTraceSteps = 16;   // DS2_GRU_STAMPS=2 trace wind
 
 // ---------------------------------------------------------------------------
 // forward step.  KSW = k-steps of W prefetched into registers per wave.
-template <int KSW>
+// ST: step 0 starts from the caller's state (rnn_common.h FwdState).
+template <int KSW, typename... S>
 __global__ __launch_bounds__(GT) void gru_fwd_step_kernel(
     int s, int T, int N, int H, int D, int UB, int BT, const float* __restrict__ xproj,
     const float* __restrict__ wp, const float* __restrict__ b_f, const float* __restrict__ b_r,
-    const int* __restrict__ lens, float* __restrict__ h_all, float* __restrict__ gates) {
+    const int* __restrict__ lens, float* __restrict__ h_all, float* __restrict__ gates,
+    S... sp) {
+  constexpr bool ST = sizeof...(S) != 0;
+  const FwdState st = fwd_state(sp...);
   constexpr int PITCH = KC_FWD + 2;
   __shared__ __attribute__((aligned(16))) float hs[GB * PITCH];
   int ub, d, bt;
@@ -106,6 +110,15 @@ __global__ __launch_bounds__(GT) void gru_fwd_step_kernel(
     gh[g] = v;
   }
   const float* bh = d == 0 ? b_f : b_r;
+  float h_first = 0.f;
+  if constexpr (ST) {
+    if (s == 0) {
+      const float* hp0 = st.hproj0 + (int64_t)n * 3 * H;
+#pragma unroll
+      for (int g = 0; g < 3; ++g) gh[g] += hp0[g * H + j];
+      h_first = st.h0[(int64_t)n * H + j];
+    }
+  }
   const float ghr = gh[0] + bh[j];
   const float ghz = gh[1] + bh[H + j];
   float ghn = gh[2] + bh[2 * H + j];
@@ -114,7 +127,7 @@ __global__ __launch_bounds__(GT) void gru_fwd_step_kernel(
   float hout = 0.f, r = 0.f, z = 0.f, nn = 0.f;
   if (active) {
     const float* xp = xproj + row * 3 * H;
-    const float hp = s > 0 ? h_all[(((int64_t)tp * N + n) * D + d) * H + j] : 0.f;
+    const float hp = s > 0 ? h_all[(((int64_t)tp * N + n) * D + d) * H + j] : h_first;
     r = sigmoidf_(ghr + xp[j]);
     z = sigmoidf_(ghz + xp[H + j]);
     nn = tanhf(xp[2 * H + j] + r * ghn);
@@ -243,13 +256,15 @@ __global__ __launch_bounds__(GT) void gru_bwd_step_kernel(
   dhcur[j] = dh;
 }
 
-template <int KSW>
+template <int KSW, typename... S>
 __global__ __launch_bounds__(GT) void gru_fwd_persist_kernel(
     int T, int N, int H, int D, int UB, int BT, const float* __restrict__ xproj,
     const float* __restrict__ wp, const float* __restrict__ b_f, const float* __restrict__ b_r,
     const int* __restrict__ lens, float* __restrict__ h_all, float* __restrict__ gates,
     unsigned* __restrict__ counters, unsigned* __restrict__ err,
-    unsigned long long* __restrict__ stamps, int trace) {
+    unsigned long long* __restrict__ stamps, int trace, S... sp) {
+  constexpr bool ST = sizeof...(S) != 0;
+  const FwdState st = fwd_state(sp...);
   constexpr int PITCH = KC_FWD + 4;
   __shared__ __attribute__((aligned(16))) float hs[GB * PITCH];
   __shared__ int flag;
@@ -310,6 +325,16 @@ __global__ __launch_bounds__(GT) void gru_fwd_persist_kernel(
   __shared__ float red[GW * GB * RP];
   float g_r = 0.f, g_z = 0.f, g_n = 0.f, g_hn = 0.f;   // gate cache of the previous step
   int64_t g_row = -1;
+  float cin[4] = {0.f, 0.f, 0.f, 0.f};   // ST: hproj0 (r, z, n) and h0, zero after step 0
+  if constexpr (ST) {
+    if (owner) {
+#pragma unroll
+      for (int g = 0; g < 3; ++g) cin[g] = st.hproj0[(int64_t)n * 3 * H + g * H + j];
+      cin[3] = st.h0[(int64_t)n * H + j];
+    }
+#pragma unroll
+    for (int g = 0; g < 4; ++g) settle(cin[g]);
+  }
   for (int s = 0; s < T; ++s) {
     const int t = d == 0 ? s : T - 1 - s;
     const int tp = d == 0 ? t - 1 : t + 1;
@@ -370,6 +395,13 @@ __global__ __launch_bounds__(GT) void gru_fwd_persist_kernel(
         for (int w8 = 0; w8 < GW; ++w8) v += red[(w8 * GB + m) * RP + g * GU + u];
         gh[g] = v;
       }
+      if constexpr (ST) {
+#pragma unroll
+        for (int g = 0; g < 3; ++g) gh[g] += cin[g];
+        if (s == 0) hp = cin[3];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) cin[g] = 0.f;
+      }
       const float ghr = gh[0] + bias_r;
       const float ghz = gh[1] + bias_z;
       float ghn = gh[2] + bias_n;
@@ -425,13 +457,15 @@ __global__ __launch_bounds__(GT) void gru_fwd_persist_kernel(
 // round trip and the producer's drain-before-flag all leave the critical path (5.93 -> 5.51
 // us per step).  The per-producer flag form and a hybrid (flag-polled, sentinel-validated)
 // were measured slower and removed in round 4's pruning; the backward keeps the flags.
-template <int NBW>
+template <int NBW, typename... S>
 __global__ __launch_bounds__(GT) __attribute__((amdgpu_waves_per_eu(2, 2))) void gru_fwd_dop_kernel(
     int T, int N, int H, int D, int UB, int BT, const float* __restrict__ xproj,
     const float* __restrict__ w_f, const float* __restrict__ w_r, const float* __restrict__ b_f,
     const float* __restrict__ b_r, const int* __restrict__ lens, float* __restrict__ h_all,
     float* __restrict__ gates, float* __restrict__ hx, unsigned* __restrict__ counters,
-    unsigned* __restrict__ err, unsigned long long* __restrict__ stamps) {
+    unsigned* __restrict__ err, unsigned long long* __restrict__ stamps, S... sp) {
+  constexpr bool ST = sizeof...(S) != 0;
+  const FwdState st = fwd_state(sp...);
   constexpr int RP = 3 * GU + 1;
   __shared__ float red[GW * GB * RP];
   __shared__ __attribute__((aligned(16))) float tile[GB * GU];
@@ -492,6 +526,17 @@ __global__ __launch_bounds__(GT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
   const int tpos = ((u >> 2) * GB + m) * 4 + (u & 3);
   float g_r = 0.f, g_z = 0.f, g_n = 0.f, g_hn = 0.f, h_own = 0.f;
   int64_t g_row = -1;
+  float cin[3] = {0.f, 0.f, 0.f};   // ST: hproj0 (r, z, n), zero after step 0
+  if constexpr (ST) {
+    if (owner) {
+#pragma unroll
+      for (int g = 0; g < 3; ++g) cin[g] = st.hproj0[(int64_t)n * 3 * H + g * H + j];
+      h_own = st.h0[(int64_t)n * H + j];
+    }
+#pragma unroll
+    for (int g = 0; g < 3; ++g) settle(cin[g]);
+    settle(h_own);
+  }
   for (int s = 0; s < T; ++s) {
     const int t = d == 0 ? s : T - 1 - s;
     const int64_t row = ((int64_t)t * N + n) * D + d;
@@ -628,6 +673,13 @@ __global__ __launch_bounds__(GT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 #pragma unroll
           for (int w8 = 0; w8 < GW; ++w8) v += red[(w8 * GB + m) * RP + g * GU + u];
           gh[g] = v;
+        }
+        if constexpr (ST) {
+#pragma unroll
+          for (int g = 0; g < 3; ++g) {
+            gh[g] += cin[g];
+            cin[g] = 0.f;
+          }
         }
         const float ghr = gh[0] + bias_r;
         const float ghz = gh[1] + bias_z;
@@ -1054,6 +1106,20 @@ static const Instance kFwdDop[] = {
     inst(1, gru_fwd_dop_kernel<1>), inst(2, gru_fwd_dop_kernel<2>), inst(3, gru_fwd_dop_kernel<3>),
     inst(4, gru_fwd_dop_kernel<4>), inst(5, gru_fwd_dop_kernel<5>), inst(6, gru_fwd_dop_kernel<6>),
     inst(7, gru_fwd_dop_kernel<7>), inst(8, gru_fwd_dop_kernel<8>)};
+// the same keys with an initial state (ds2_gru_fwd_state)
+static const Instance kFwdDopSt[] = {
+    inst(1, gru_fwd_dop_kernel<1, FwdState>), inst(2, gru_fwd_dop_kernel<2, FwdState>),
+    inst(3, gru_fwd_dop_kernel<3, FwdState>), inst(4, gru_fwd_dop_kernel<4, FwdState>),
+    inst(5, gru_fwd_dop_kernel<5, FwdState>), inst(6, gru_fwd_dop_kernel<6, FwdState>),
+    inst(7, gru_fwd_dop_kernel<7, FwdState>), inst(8, gru_fwd_dop_kernel<8, FwdState>)};
+static const Instance kFwdPersistSt[] = {
+    inst(8, gru_fwd_persist_kernel<8, FwdState>), inst(16, gru_fwd_persist_kernel<16, FwdState>),
+    inst(25, gru_fwd_persist_kernel<25, FwdState>), inst(32, gru_fwd_persist_kernel<32, FwdState>)};
+static const Instance kFwdStepSt[] = {
+    inst(8, gru_fwd_step_kernel<8, FwdState>),   inst(16, gru_fwd_step_kernel<16, FwdState>),
+    inst(32, gru_fwd_step_kernel<32, FwdState>), inst(48, gru_fwd_step_kernel<48, FwdState>),
+    inst(64, gru_fwd_step_kernel<64, FwdState>), inst(80, gru_fwd_step_kernel<80, FwdState>),
+    inst(96, gru_fwd_step_kernel<96, FwdState>)};
 static const Instance kBwdDop[] = {
     inst(1, gru_bwd_dop_kernel<1>),   inst(2, gru_bwd_dop_kernel<2>),
     inst(3, gru_bwd_dop_kernel<3>),   inst(4, gru_bwd_dop_kernel<4>),
@@ -1193,17 +1259,24 @@ size_t ds2_gru_fwd_workspace_size(int n, int h, int num_dirs) {
   return gru_fwd_layout(RnnShape{0, n, h, num_dirs}).total;
 }
 
+}  // extern "C"
+
 // Kernel choice (forward and backward alike; DESIGN.md "Recurrent dispatch"): where
 // H % 16 == 0 and the grid fits the chip, the XCD-local kernels (gru_xl.hip), then the 16-unit
 // fp16x3 / bf16x6 kernels (gru_split.hip), then the fp32-MFMA direct-operand kernels
 // (DS2_GRU_X6=0 selects them); else the LDS-staged persistent kernels (H % 4 == 0), else one
 // launch per step (also DS2_RNN_PERSISTENT=0).
-ds2_status_t ds2_gru_fwd(int t_max, int n, int h, int num_dirs, const float* xproj,
-                         const float* w_hh_f, const float* w_hh_r, const float* b_hh_f,
-                         const float* b_hh_r, const int* lens, float* h_all, float* gates,
-                         unsigned* err_out, void* ws, size_t ws_bytes, ds2_stream_t stream) {
+// h0, hproj0 (ds2_gru_fwd_state; both NULL or both set): the rung and the instance key are
+// chosen by the shape alone, the state only selects the ST twin of the kernel.
+static ds2_status_t gru_fwd_run(int t_max, int n, int h, int num_dirs, const float* xproj,
+                                const float* w_hh_f, const float* w_hh_r, const float* b_hh_f,
+                                const float* b_hh_r, const int* lens, float* h_all, float* gates,
+                                const float* h0, const float* hproj0, unsigned* err_out, void* ws,
+                                size_t ws_bytes, ds2_stream_t stream) {
   if (t_max < 0 || n < 0 || h < 1 || (num_dirs != 1 && num_dirs != 2)) return DS2_INVALID_VALUE;
   rnn_rec_reset();
+  const bool stateful = h0 != nullptr;
+  if ((hproj0 != nullptr) != stateful || (stateful && num_dirs != 1)) return DS2_INVALID_VALUE;
   if (h > KC_FWD) return DS2_UNSUPPORTED_SHAPE;
   if (t_max == 0 || n == 0) return DS2_OK;
   const RnnShape s = {t_max, n, h, num_dirs};
@@ -1218,14 +1291,18 @@ ds2_status_t ds2_gru_fwd(int t_max, int n, int h, int num_dirs, const float* xpr
   apply_rnn_tune_env();
   int T = t_max, N = n, H = h, D = num_dirs, UB = s.UB(), BT = s.BT();
   const int KS = (h + 3) / 4;
-  const Instance step_fn = pick_instance(kFwdStep, (KS + GW - 1) / GW);
+  const Instance step_fn = stateful ? pick_instance(kFwdStepSt, (KS + GW - 1) / GW)
+                                    : pick_instance(kFwdStep, (KS + GW - 1) / GW);
   if (step_fn.fn == nullptr) return DS2_UNSUPPORTED_SHAPE;
   float* wp = ws_at<float>(ws, L.wp);
   const int grid = mapped_grid(UB * num_dirs, BT);
   const bool persistent = persistent_enabled() && grid <= num_cus() && s.fits32(1);
   ds2_status_t rc = DS2_OK;
+  // the kernels' last argument (empty in the stateless instantiations, which read nothing of it)
+  FwdState fs = {h0, nullptr, hproj0};
   if (persistent && (h % GU) == 0 && UB <= 8 * GW) {
-    const RecFwd a = {xproj, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lens, h_all, nullptr, gates};
+    const RecFwd a = {xproj, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lens, h_all, nullptr, gates,
+                      h0,    nullptr, hproj0};
     Handoff ho = L.ho.at(ws, s, err_out);
     // the XCD-local launch prepares the counters and its part of the ring itself and reports
     // into err_out from the kernel: no fills and no fold launch around it
@@ -1236,8 +1313,9 @@ ds2_status_t ds2_gru_fwd(int t_max, int n, int h, int num_dirs, const float* xpr
       return rc;
     // the dynamic LDS keeps one workgroup per CU (every workgroup gets a whole CU's SIMDs)
     void* args[] = {&T, &N, &H, &D, &UB, &BT, &xproj, &w_hh_f, &w_hh_r, &b_hh_f,
-                    &b_hh_r, &lens, &h_all, &gates, &ho.ring, &ho.ctrs, &ho.err, &ho.stamps};
-    const Instance fn = pick_instance(kFwdDop, (UB + GW - 1) / GW);
+                    &b_hh_r, &lens, &h_all, &gates, &ho.ring, &ho.ctrs, &ho.err, &ho.stamps, &fs};
+    const Instance fn = stateful ? pick_instance(kFwdDopSt, (UB + GW - 1) / GW)
+                                 : pick_instance(kFwdDop, (UB + GW - 1) / GW);
     if (rung("ds2_gru_fwd", ho, false, 0, st, &rc, [&] {
           return launch_fn(fn, DS2_RUNG_DOP, 1, 0, grid, GT, args, kDopPadLds, st);
         }))
@@ -1249,8 +1327,10 @@ ds2_status_t ds2_gru_fwd(int t_max, int n, int h, int num_dirs, const float* xpr
     Handoff ho = L.ho.at(ws, s, err_out, true);
     int trace = stamp_mode() == 2 ? 1 : 0;
     void* args[] = {&T, &N, &H, &D, &UB, &BT, &xproj, &wp, &b_hh_f, &b_hh_r, &lens,
-                    &h_all, &gates, &ho.ctrs, &ho.err, &ho.stamps, &trace};
-    const Instance fn = pick_instance(kFwdPersist, persist_ksw((KS + GW - 1) / GW, KC_FWD));
+                    &h_all, &gates, &ho.ctrs, &ho.err, &ho.stamps, &trace, &fs};
+    const int ksw = persist_ksw((KS + GW - 1) / GW, KC_FWD);
+    const Instance fn =
+        stateful ? pick_instance(kFwdPersistSt, ksw) : pick_instance(kFwdPersist, ksw);
     if (rung("ds2_gru_fwd", ho, true, 0, st, &rc, [&] {
           return launch_fn(fn, DS2_RUNG_LDS_PERSIST, 1, 0, grid, GT, args, 0, st);
         }))
@@ -1259,9 +1339,28 @@ ds2_status_t ds2_gru_fwd(int t_max, int n, int h, int num_dirs, const float* xpr
 
   int step = 0;
   void* args[] = {&step, &T, &N, &H, &D, &UB, &BT, &xproj, &wp, &b_hh_f, &b_hh_r, &lens,
-                  &h_all, &gates};
+                  &h_all, &gates, &fs};
   for (step = 0; step < t_max; ++step) launch_step(step_fn, grid, GT, args, st);
   return launch_status("ds2_gru_fwd");
+}
+
+extern "C" {
+
+ds2_status_t ds2_gru_fwd(int t_max, int n, int h, int num_dirs, const float* xproj,
+                         const float* w_hh_f, const float* w_hh_r, const float* b_hh_f,
+                         const float* b_hh_r, const int* lens, float* h_all, float* gates,
+                         unsigned* err_out, void* ws, size_t ws_bytes, ds2_stream_t stream) {
+  return gru_fwd_run(t_max, n, h, num_dirs, xproj, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lens, h_all,
+                     gates, nullptr, nullptr, err_out, ws, ws_bytes, stream);
+}
+
+ds2_status_t ds2_gru_fwd_state(int t_max, int n, int h, int num_dirs, const float* xproj,
+                               const float* w_hh_f, const float* w_hh_r, const float* b_hh_f,
+                               const float* b_hh_r, const int* lens, float* h_all, float* gates,
+                               const float* h0, const float* hproj0, unsigned* err_out, void* ws,
+                               size_t ws_bytes, ds2_stream_t stream) {
+  return gru_fwd_run(t_max, n, h, num_dirs, xproj, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lens, h_all,
+                     gates, h0, hproj0, err_out, ws, ws_bytes, stream);
 }
 
 size_t ds2_gru_bwd_workspace_size(int n, int h, int num_dirs) {

@@ -105,15 +105,20 @@ __device__ __forceinline__ void pair_split(int pairs, int wave, int& p0, int& np
 // the sentinel-ring hand-off of gru_fwd_dop_kernel (the data is the flag).
 // NG = 1: the one-gate instantiation for supported_rnns['rnn'] (nn.RNN, tanh; model.py:15):
 // gh[16 x 16] = h_{t-1} . W_hh[16 units]^T and h_t = tanh(xproj_t + gh + b_hh), no gate cache.
-template <int NP, bool H3 = false, int NG = 3>
+// ST (GRU only): step 0 starts from the caller's state (rnn_common.h FwdState).
+template <int NP, bool H3 = false, int NG = 3, typename... S>
 __global__ __launch_bounds__(XT) __attribute__((amdgpu_waves_per_eu(1, 1))) void gru_fwd_x6_kernel(
     int T, int N, int H, int D, int UB, int BT, const float* __restrict__ xproj,
     const float* __restrict__ w_f, const float* __restrict__ w_r, const float* __restrict__ b_f,
     const float* __restrict__ b_r, const int* __restrict__ lens, float* __restrict__ h_all,
     float* __restrict__ gates, float* __restrict__ hx, unsigned* __restrict__ counters,
-    unsigned* __restrict__ err, unsigned long long* __restrict__ stamps, int xmode) {
+    unsigned* __restrict__ err, unsigned long long* __restrict__ stamps, int xmode,
+    S... sp) {
+  constexpr bool ST = sizeof...(S) != 0;
+  const FwdState st = fwd_state(sp...);
   static_assert(2 * NP <= 64, "tsame holds a wave's tiles");
   static_assert(NG == 3 || (NG == 1 && H3), "the one-gate form is fp16x3 only");
+  static_assert(!ST || NG == 3, "an initial state: the GRU only");
   constexpr int RP = NG * GU + 1;
   constexpr int NSLOT = kRingSlots;
   __shared__ float red[XW * GB * RP];
@@ -246,6 +251,17 @@ __global__ __launch_bounds__(XT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
   const int tpos = ((u >> 2) * GB + m) * 4 + (u & 3);
   float g_r = 0.f, g_z = 0.f, g_n = 0.f, g_hn = 0.f, h_own = 0.f;
   int64_t g_row = -1;
+  float cin[3] = {0.f, 0.f, 0.f};   // ST: hproj0 (r, z, n), zero after step 0
+  if constexpr (ST) {
+    if (owner) {
+#pragma unroll
+      for (int g = 0; g < 3; ++g) cin[g] = st.hproj0[(int64_t)n * 3 * H + g * H + j];
+      h_own = st.h0[(int64_t)n * H + j];
+    }
+#pragma unroll
+    for (int g = 0; g < 3; ++g) settle(cin[g]);
+    settle(h_own);
+  }
   for (int s = 0; s < T; ++s) {
     const int t = d == 0 ? s : T - 1 - s;
     const int64_t row = ((int64_t)t * N + n) * D + d;
@@ -366,6 +382,13 @@ __global__ __launch_bounds__(XT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 #pragma unroll
         for (int w8 = 0; w8 < XW; ++w8) v += red[(w8 * GB + m) * RP + g * GU + u];
         gh[g] = H3 ? v * unscale[g] : v;
+      }
+      if constexpr (ST) {
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+          gh[g] += cin[g];
+          cin[g] = 0.f;
+        }
       }
       const float ghr = gh[0] + bias_r;
       const float ghz = gh[1] + bias_z;
@@ -1456,6 +1479,15 @@ static const Instance kGruFwdX6[] = {
     inst(3, gru_fwd_x6_kernel<3, false>), inst(4, gru_fwd_x6_kernel<4, false>),
     inst(5, gru_fwd_x6_kernel<5, false>), inst(6, gru_fwd_x6_kernel<6, false>),
     inst(7, gru_fwd_x6_kernel<7, false>)};
+// the GRU's with an initial state (ds2_gru_fwd_state), same keys
+#define DS2_X6_ST(K, H3) inst(K, gru_fwd_x6_kernel<K, H3, 3, FwdState>)
+static const Instance kGruFwdH3St[] = {
+    DS2_X6_ST(1, true), DS2_X6_ST(2, true), DS2_X6_ST(3, true), DS2_X6_ST(4, true),
+    DS2_X6_ST(5, true), DS2_X6_ST(6, true), DS2_X6_ST(7, true)};
+static const Instance kGruFwdX6St[] = {
+    DS2_X6_ST(1, false), DS2_X6_ST(2, false), DS2_X6_ST(3, false), DS2_X6_ST(4, false),
+    DS2_X6_ST(5, false), DS2_X6_ST(6, false), DS2_X6_ST(7, false)};
+#undef DS2_X6_ST
 static const Instance kRnnFwd[] = {
     inst(1, gru_fwd_x6_kernel<1, true, 1>), inst(2, gru_fwd_x6_kernel<2, true, 1>),
     inst(3, gru_fwd_x6_kernel<3, true, 1>), inst(4, gru_fwd_x6_kernel<4, true, 1>),
@@ -1501,14 +1533,15 @@ static bool declines16(int ng, int h) {
   return (h % GU) != 0 || (ng == 3 && env_off("DS2_GRU_X6"));
 }
 
-static Pick16 pick_fwd16(int ng, const RnnShape& s) {
+// st: the GRU's twins with an initial state (the same keys for the same shapes)
+static Pick16 pick_fwd16(int ng, const RnnShape& s, bool st = false) {
   Pick16 p = {{0, nullptr}, -1, 0, false, DS2_RUNG_H3_16};
-  if (declines16(ng, s.h) || (ng != 1 && ng != 3)) return p;
+  if (declines16(ng, s.h) || (ng != 1 && ng != 3) || (st && ng != 3)) return p;
   const int need = ((s.UB() + 1) / 2 + XW - 1) / XW;
   const bool x6 = ng == 3 && env_off("DS2_GRU_H3");
   p.e = ng == 1 ? pick_instance(kRnnFwd, need)
-        : x6    ? pick_instance(kGruFwdX6, need)
-                : pick_instance(kGruFwdH3, need);
+        : x6    ? (st ? pick_instance(kGruFwdX6St, need) : pick_instance(kGruFwdX6, need))
+                : (st ? pick_instance(kGruFwdH3St, need) : pick_instance(kGruFwdH3, need));
   if (x6) p.rung = DS2_RUNG_X6_16;
   if (p.e.fn != nullptr) p.grid = group_grid(s.UB(), s.BT(), s.d, &p.same_xcd);
   return p;
@@ -1540,13 +1573,14 @@ static void apply_knobs() {
 }
 
 bool launch_fwd16(int ng, RnnShape s, RecFwd a, Handoff ho, hipStream_t st) {
-  Pick16 p = pick_fwd16(ng, s);
+  Pick16 p = pick_fwd16(ng, s, a.stateful());
   if (p.e.fn == nullptr) return false;
   apply_knobs();
   int UB = s.UB(), BT = s.BT();
+  FwdState fs = a.state();   // the last argument, empty in the stateless instantiations
   void* args[] = {&s.t, &s.n, &s.h, &s.d, &UB, &BT, &a.xproj, &a.w_hh_f, &a.w_hh_r, &a.b_hh_f,
                   &a.b_hh_r, &a.lens, &a.h_all, &a.gates, &ho.ring, &ho.ctrs, &ho.err,
-                  &ho.stamps, &p.same_xcd};
+                  &ho.stamps, &p.same_xcd, &fs};
   return launch_rec(p.e.fn, Ran{p.rung, p.e.k, 0, 1, p.same_xcd}, dim3(p.grid), dim3(XT), args,
                     ho.lds_pad, st);
 }

@@ -270,14 +270,17 @@ __device__ __forceinline__ int xl_frag_hi(int m, int k) { return (((k >> 3) << 4
 // column tile ct = gate * 2 + unit half, the fp16 hi / lo B fragments of W_hh's rows scaled by
 // 2^e(gate, unit) (the row's max over the whole K).  h (|h| < 1) takes the fixed scale 2^14.
 // TRACE: the instantiation with the stamp sites (DS2_GRU_STAMPS=2); the product ones carry none
-template <int NPW, bool TRACE>
+// ST: step 0 starts from the caller's state (rnn_common.h FwdState)
+template <int NPW, bool TRACE, typename... S>
 __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void gru_fwd_xl_kernel(
     int T, int N, int H, int D, int UBX, int BTX, const float* __restrict__ xproj,
     const float* __restrict__ w_f, const float* __restrict__ w_r, const float* __restrict__ b_f,
     const float* __restrict__ b_r, const int* __restrict__ lens, float* __restrict__ h_all,
     float* __restrict__ gates, float* __restrict__ ring, unsigned* __restrict__ xl,
     unsigned* __restrict__ err, unsigned* __restrict__ err_out,
-    unsigned long long* __restrict__ stamps, int force_global) {
+    unsigned long long* __restrict__ stamps, int force_global, S... sp) {
+  constexpr bool ST = sizeof...(S) != 0;
+  const FwdState st = fwd_state(sp...);
   constexpr int NCT = 6;
   constexpr int RC = 3 * LU + 1;   // reduction row pitch
   __shared__ float red[LW * 16 * RC];
@@ -472,6 +475,17 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
   // step's tile waits whatever its own use, so a longer prefetch distance buys nothing)
   f32x4 xin = io ? load_in(0) : z4v;
   float h_own = 0.f;
+  float cin[3] = {0.f, 0.f, 0.f};   // ST: hproj0 (r, z, n), zero after step 0
+  if constexpr (ST) {
+    if (owner) {
+#pragma unroll
+      for (int gt = 0; gt < 3; ++gt) cin[gt] = st.hproj0[(int64_t)n * 3 * H + gt * H + j];
+      h_own = st.h0[(int64_t)n * H + j];
+    }
+#pragma unroll
+    for (int gt = 0; gt < 3; ++gt) settle(cin[gt]);
+    settle(h_own);
+  }
   for (int s = 0; s < T; ++s) {
     const int t = d == 0 ? s : T - 1 - s;
     f32x4 acc[NCT];
@@ -575,7 +589,17 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     }
     const float xr = pin[m * LU + u], xz = pin[256 + m * LU + u], xn = pin[512 + m * LU + u];
     float hout = 0.f, r = 0.f, z = 0.f, nn = 0.f, ghn = 0.f;
-    if (owner && t < len) {
+    if constexpr (ST) {
+      if (owner && t < len) {
+        ghn = gh[2] * us_n + cin[2] + bias_n;
+        r = sigmoid_fast(gh[0] * us_r + cin[0] + bias_r + xr);
+        z = sigmoid_fast(gh[1] * us_z + cin[1] + bias_z + xz);
+        nn = tanh_fast(xn + r * ghn);
+        hout = (h_own - nn) * z + nn;
+      }
+#pragma unroll
+      for (int gt = 0; gt < 3; ++gt) cin[gt] = 0.f;
+    } else if (owner && t < len) {
       ghn = gh[2] * us_n + bias_n;
       r = sigmoid_fast(gh[0] * us_r + bias_r + xr);
       z = sigmoid_fast(gh[1] * us_z + bias_z + xz);
@@ -1120,6 +1144,9 @@ size_t gru_xl_ctr_words() { return 520; }
   {inst(2, K<1, __VA_ARGS__>), inst(4, K<3, __VA_ARGS__>), inst(7, K<6, __VA_ARGS__>)}
 static const Instance kFwdXl[2][3] = {DS2_XL_TABLE(gru_fwd_xl_kernel, false),
                                       DS2_XL_TABLE(gru_fwd_xl_kernel, true)};
+// with an initial state (ds2_gru_fwd_state), same keys
+static const Instance kFwdXlSt[2][3] = {DS2_XL_TABLE(gru_fwd_xl_kernel, false, FwdState),
+                                        DS2_XL_TABLE(gru_fwd_xl_kernel, true, FwdState)};
 static const Instance kBwdXl[2][3] = {DS2_XL_TABLE(gru_bwd_xl_kernel, false, false),
                                       DS2_XL_TABLE(gru_bwd_xl_kernel, false, true)};
 // the same with the row-maximum partials of dgates_x
@@ -1156,15 +1183,17 @@ bool launch_gru_fwd_xl(RnnShape s, RecFwd a, Handoff ho, hipStream_t st) {
   apply_spin_limit_env();
   apply_rnn_tune_env();
   int UBX = s.h / LU, BTX = s.BT(LB), FG = xl_force_global();
-  const Instance fn = pick_instance(kFwdXl[ho.stamps != nullptr], (UBX + LW - 1) / LW);
+  const Instance fn = pick_instance((a.stateful() ? kFwdXlSt : kFwdXl)[ho.stamps != nullptr],
+                                    (UBX + LW - 1) / LW);
   if (fn.fn == nullptr) return false;
+  FwdState fs = a.state();   // the last argument, empty in the stateless instantiations
   if (!xl_prepare(ho.ctrs, ho.ctr_bytes, nullptr, 0, ho.ring,
                   gru_xl_ring_bytes(s.n, s.h, s.d, false), st))
     return false;
   unsigned* xl = ho.err + 1;
   void* args[] = {&s.t, &s.n, &s.h, &s.d, &UBX, &BTX, &a.xproj, &a.w_hh_f, &a.w_hh_r, &a.b_hh_f,
                   &a.b_hh_r, &a.lens, &a.h_all, &a.gates, &ho.ring, &xl, &ho.err, &ho.err_out,
-                  &ho.stamps, &FG};
+                  &ho.stamps, &FG, &fs};
   return launch_rec(fn.fn, Ran{DS2_RUNG_XCD_LOCAL, fn.k, 0, 0, 1}, dim3(8 * UBX), dim3(LT), args,
                     ho.lds_pad, st);
 }

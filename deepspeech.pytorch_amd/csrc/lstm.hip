@@ -60,12 +60,15 @@ __device__ __forceinline__ float lstm_cell_bwd(float dh, float dc_carry, float g
 
 // ---------------------------------------------------------------------------
 // forward step (one launch per time step)
-template <int KSW>
+// ST: step 0 starts from the caller's state (rnn_common.h FwdState).
+template <int KSW, typename... S>
 __global__ __launch_bounds__(GT) void lstm_fwd_step_kernel(
     int s, int T, int N, int H, int D, int UB, int BT, const float* __restrict__ xproj,
     const float* __restrict__ wp, const float* __restrict__ b_f, const float* __restrict__ b_r,
     const int* __restrict__ lens, float* __restrict__ h_all, float* __restrict__ c_all,
-    float* __restrict__ gates, float* __restrict__ cs) {
+    float* __restrict__ gates, float* __restrict__ cs, S... sp) {
+  constexpr bool ST = sizeof...(S) != 0;
+  const FwdState st = fwd_state(sp...);
   constexpr int PITCH = LKC_FWD + 2;
   __shared__ __attribute__((aligned(16))) float hs[GB * PITCH];
   int ub, d, bt;
@@ -136,7 +139,14 @@ __global__ __launch_bounds__(GT) void lstm_fwd_step_kernel(
     }
     const float* bh = d == 0 ? b_f : b_r;
     const float* xp = xproj + row * 4 * H;
-    const float cp = s > 0 ? cs[((s + 1) & 1) * plane + cidx] : 0.f;
+    float cp = s > 0 ? cs[((s + 1) & 1) * plane + cidx] : 0.f;
+    if constexpr (ST) {
+      if (s == 0) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) gh[g] += st.hproj0[(int64_t)n * 4 * H + g * H + j];
+        cp = st.c0[(int64_t)n * H + j];
+      }
+    }
     o = lstm_cell(gh[0] + bh[j] + xp[j], gh[1] + bh[H + j] + xp[H + j],
                   gh[2] + bh[2 * H + j] + xp[2 * H + j], gh[3] + bh[3 * H + j] + xp[3 * H + j],
                   cp);
@@ -252,13 +262,15 @@ __global__ __launch_bounds__(GT) void lstm_bwd_step_kernel(
 // BiLSTM-1024 at batch 64 = 512 workgroups) runs as ONE launch of 32-sample workgroups
 // instead of two consecutive launches (the dependent steps, not the MFMAs, set the pace);
 // the reduction tile then aliases the staged rows.
-template <int KSW, int BTS>
+template <int KSW, int BTS, typename... S>
 __global__ __launch_bounds__(GT) void lstm_fwd_persist_kernel(
     int T, int N, int H, int D, int UB, int BT, const float* __restrict__ xproj,
     const float* __restrict__ wp, const float* __restrict__ b_f, const float* __restrict__ b_r,
     const int* __restrict__ lens, float* __restrict__ h_all, float* __restrict__ c_all,
     float* __restrict__ gates, unsigned* __restrict__ counters, unsigned* __restrict__ err,
-    int n_base) {
+    int n_base, S... sp) {
+  constexpr bool ST = sizeof...(S) != 0;
+  const FwdState st = fwd_state(sp...);
   constexpr int PITCH = LKC_FWD + 4;
   constexpr int RB = GB * BTS;         // samples per workgroup
   constexpr int HSF = RB * PITCH, REDF = GW * RB * LRP;
@@ -305,6 +317,17 @@ __global__ __launch_bounds__(GT) void lstm_fwd_persist_kernel(
   for (int g = 0; g < 4; ++g) settle(bias[g]);
   settle(len);
   float c = 0.f;
+  float cin[4] = {0.f, 0.f, 0.f, 0.f};   // ST: hproj0 (i, f, g, o), zero after step 0
+  if constexpr (ST) {
+    if (owner) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) cin[g] = st.hproj0[(int64_t)n * 4 * H + g * H + j];
+      c = st.c0[(int64_t)n * H + j];
+    }
+#pragma unroll
+    for (int g = 0; g < 4; ++g) settle(cin[g]);
+    settle(c);
+  }
   LstmFwdOut prev{0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   int64_t prev_row = -1;
   for (int s = 0; s < T; ++s) {
@@ -361,8 +384,13 @@ __global__ __launch_bounds__(GT) void lstm_fwd_persist_kernel(
 #pragma unroll
           for (int w8 = 0; w8 < GW; ++w8) v += red[(w8 * RB + m) * LRP + g * GU + u];
           gh[g] = v + bias[g] + xg[g];
+          if constexpr (ST) gh[g] += cin[g];
         }
         o = lstm_cell(gh[0], gh[1], gh[2], gh[3], c);
+      }
+      if constexpr (ST) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) cin[g] = 0.f;
       }
       c = o.c;
       __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, o.h), h_rs,
@@ -539,13 +567,16 @@ __global__ __launch_bounds__(GT) void lstm_bwd_persist_kernel(
 // of lane (r, q) from block 2p, 4..7 from 2p + 1, the 16 B the lane loads from each tile),
 // W_hh rows (gate, unit) scaled by their own 2^e, h (|h| < 1) by 2^14; three products per
 // pair instead of sixteen v_mfma_f32_16x16x4_f32 (each 4x the cycles of one f16 product).
-template <int NBW, int HM, int BTS, bool H3 = false>
+template <int NBW, int HM, int BTS, bool H3 = false, typename... S>
 __global__ __launch_bounds__(GT) __attribute__((amdgpu_waves_per_eu(2, 2))) void lstm_fwd_dop_kernel(
     int T, int N, int H, int D, int UB, int BT, const float* __restrict__ xproj,
     const float* __restrict__ w_f, const float* __restrict__ w_r, const float* __restrict__ b_f,
     const float* __restrict__ b_r, const int* __restrict__ lens, float* __restrict__ h_all,
     float* __restrict__ c_all, float* __restrict__ gates, float* __restrict__ hx,
-    unsigned* __restrict__ counters, unsigned* __restrict__ err, int n_base, int xg) {
+    unsigned* __restrict__ counters, unsigned* __restrict__ err, int n_base, int xg,
+    S... sp) {
+  constexpr bool ST = sizeof...(S) != 0;
+  const FwdState st = fwd_state(sp...);
   constexpr int RB = GB * BTS;
   __shared__ float red[GW * RB * LRP];
   __shared__ __attribute__((aligned(16))) float tile[RB * GU];
@@ -652,6 +683,17 @@ __global__ __launch_bounds__(GT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
   // this thread's slot in its batch tile's transposed tile: (q = u >> 2, r = m % 16, c = u & 3)
   const int tpos = (m >> 4) * GB * GU + ((u >> 2) * GB + (m & 15)) * 4 + (u & 3);
   float c = 0.f;
+  float cin[4] = {0.f, 0.f, 0.f, 0.f};   // ST: hproj0 (i, f, g, o), zero after step 0
+  if constexpr (ST) {
+    if (owner) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) cin[g] = st.hproj0[(int64_t)n * 4 * H + g * H + j];
+      c = st.c0[(int64_t)n * H + j];
+    }
+#pragma unroll
+    for (int g = 0; g < 4; ++g) settle(cin[g]);
+    settle(c);
+  }
   LstmFwdOut prev{0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   int64_t prev_row = -1;
   for (int s = 0; s < T; ++s) {
@@ -740,8 +782,13 @@ __global__ __launch_bounds__(GT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 #pragma unroll
             for (int w8 = 0; w8 < GW; ++w8) v += red[(w8 * RB + m) * LRP + g * GU + u];
             gh[g] = (H3 ? v * unscale[g] : v) + bias[g] + xg[g];
+            if constexpr (ST) gh[g] += cin[g];
           }
           o = lstm_cell(gh[0], gh[1], gh[2], gh[3], c);
+        }
+        if constexpr (ST) {
+#pragma unroll
+          for (int g = 0; g < 4; ++g) cin[g] = 0.f;
         }
         c = o.c;
         hout = o.h;
@@ -811,6 +858,21 @@ static const Instance kFwdDop[2][2][4] = {
       inst(4, lstm_fwd_dop_kernel<4, 1, 1, true>), inst(8, lstm_fwd_dop_kernel<8, 0, 1, true>)},
      {inst(1, lstm_fwd_dop_kernel<1, 1, 2, true>), inst(2, lstm_fwd_dop_kernel<2, 1, 2, true>),
       inst(4, lstm_fwd_dop_kernel<4, 1, 2, true>), inst(8, lstm_fwd_dop_kernel<8, 0, 2, true>)}}};
+// ... and with an initial state (ds2_lstm_fwd_state): the same keys
+#define DS2_LFD(H3, B)                                                                    \
+  {inst(1, lstm_fwd_dop_kernel<1, 1, B, H3, FwdState>), inst(2, lstm_fwd_dop_kernel<2, 1, B, H3, FwdState>), \
+   inst(4, lstm_fwd_dop_kernel<4, 1, B, H3, FwdState>), inst(8, lstm_fwd_dop_kernel<8, 0, B, H3, FwdState>)}
+static const Instance kFwdDopSt[2][2][4] = {{DS2_LFD(false, 1), DS2_LFD(false, 2)},
+                                            {DS2_LFD(true, 1), DS2_LFD(true, 2)}};
+#undef DS2_LFD
+static const Instance kFwdPersistSt[2][4] = {
+    {inst(8, lstm_fwd_persist_kernel<8, 1, FwdState>), inst(16, lstm_fwd_persist_kernel<16, 1, FwdState>),
+     inst(25, lstm_fwd_persist_kernel<25, 1, FwdState>), inst(32, lstm_fwd_persist_kernel<32, 1, FwdState>)},
+    {inst(8, lstm_fwd_persist_kernel<8, 2, FwdState>), inst(16, lstm_fwd_persist_kernel<16, 2, FwdState>),
+     inst(25, lstm_fwd_persist_kernel<25, 2, FwdState>), inst(32, lstm_fwd_persist_kernel<32, 2, FwdState>)}};
+static const Instance kFwdStepSt[] = {inst(8, lstm_fwd_step_kernel<8, FwdState>),
+                                      inst(16, lstm_fwd_step_kernel<16, FwdState>),
+                                      inst(32, lstm_fwd_step_kernel<32, FwdState>)};
 // LDS-staged persistent forward [BTS - 1], K = k-steps per wave
 static const Instance kFwdPersist[2][4] = {
     {inst(8, lstm_fwd_persist_kernel<8, 1>), inst(16, lstm_fwd_persist_kernel<16, 1>),
@@ -927,16 +989,25 @@ size_t ds2_lstm_fwd_workspace_size(int n, int h, int num_dirs) {
   return lstm_fwd_layout(RnnShape{0, n, h, num_dirs}).total;
 }
 
+}  // extern "C"
+
 // Ladder (DESIGN.md "Recurrent dispatch"): the direct-operand persistent kernels (H % 16 == 0;
 // fp16x3, or fp32 MFMA with DS2_LSTM_H3=0), the LDS-staged persistent kernels (H % 4 == 0),
 // one launch per step (also DS2_RNN_PERSISTENT=0).
-ds2_status_t ds2_lstm_fwd(int t_max, int n, int h, int num_dirs, const float* xproj,
-                          const float* w_hh_f, const float* w_hh_r, const float* b_hh_f,
-                          const float* b_hh_r, const int* lens, float* h_all, float* c_all,
-                          float* gates, unsigned* err_out, void* ws, size_t ws_bytes,
-                          ds2_stream_t stream) {
+// h0, c0, hproj0 (ds2_lstm_fwd_state; all NULL or all set): the rung and the instance key are
+// chosen by the shape alone, the state only selects the ST twin of the kernel.
+static ds2_status_t lstm_fwd_run(int t_max, int n, int h, int num_dirs, const float* xproj,
+                                 const float* w_hh_f, const float* w_hh_r, const float* b_hh_f,
+                                 const float* b_hh_r, const int* lens, float* h_all, float* c_all,
+                                 float* gates, const float* h0, const float* c0,
+                                 const float* hproj0, unsigned* err_out, void* ws,
+                                 size_t ws_bytes, ds2_stream_t stream) {
   if (t_max < 0 || n < 0 || h < 1 || (num_dirs != 1 && num_dirs != 2)) return DS2_INVALID_VALUE;
   rnn_rec_reset();
+  const bool stateful = h0 != nullptr;
+  if ((c0 != nullptr) != stateful || (hproj0 != nullptr) != stateful ||
+      (stateful && num_dirs != 1))
+    return DS2_INVALID_VALUE;
   if (h > LKC_FWD) return DS2_UNSUPPORTED_SHAPE;
   if (t_max == 0 || n == 0) return DS2_OK;
   const RnnShape s = {t_max, n, h, num_dirs};
@@ -950,10 +1021,13 @@ ds2_status_t ds2_lstm_fwd(int t_max, int n, int h, int num_dirs, const float* xp
   apply_spin_limit_env();
   int T = t_max, N = n, H = h, D = num_dirs, UB = s.UB(), BT = s.BT();
   const int KS = (h + 3) / 4;
-  const Instance step_fn = pick_instance(kFwdStep, (KS + GW - 1) / GW);
+  const Instance step_fn = stateful ? pick_instance(kFwdStepSt, (KS + GW - 1) / GW)
+                                    : pick_instance(kFwdStep, (KS + GW - 1) / GW);
   if (step_fn.fn == nullptr) return DS2_UNSUPPORTED_SHAPE;
   float* wp = ws_at<float>(ws, L.wp);
   float* cs = ws_at<float>(ws, L.cs);
+  // the kernels' last argument (empty in the stateless instantiations, which read nothing of it)
+  FwdState fs = {h0, c0, hproj0};
   const Handoff ho = {ws_at<float>(ws, L.ring), ws_at<unsigned>(ws, L.ctrs), L.ctr_bytes,
                       nullptr, err_out, nullptr, kDopPadLds};
   const int bts = lstm_bts(UB, D, BT);
@@ -966,7 +1040,7 @@ ds2_status_t ds2_lstm_fwd(int t_max, int n, int h, int num_dirs, const float* xp
   if (persistent && (h % GU) == 0 && UB <= 8 * GW) {
     const int nbw = (UB + GW - 1) / GW;
     const int h3 = env_off("DS2_LSTM_H3") ? 0 : 1;
-    const Instance fn = pick_instance(kFwdDop[h3][bts - 1], nbw);
+    const Instance fn = pick_instance((stateful ? kFwdDopSt : kFwdDop)[h3][bts - 1], nbw);
     const size_t ring_fill = nbw > 4 ? 0 : L.ring_bytes;   // the sentinel ring (HM = 1)
     if (fn.fn != nullptr &&
         for_each_chunk("ds2_lstm_fwd", ho, D, BTW, ct, ring_fill, st, &rc,
@@ -976,7 +1050,7 @@ ds2_status_t ds2_lstm_fwd(int t_max, int n, int h, int num_dirs, const float* xp
                          const int grid = group_grid(UB, bt, D, &XG);
                          void* args[] = {&T, &N, &H, &D, &UB, &bt, &xproj, &w_hh_f, &w_hh_r,
                                          &b_hh_f, &b_hh_r, &lens, &h_all, &c_all, &gates, &c.ring,
-                                         &c.ctrs, &c.err, &NB, &XG};
+                                         &c.ctrs, &c.err, &NB, &XG, &fs};
                          return launch_fn(fn, h3 ? DS2_RUNG_DOP_H3 : DS2_RUNG_DOP, bts, XG, grid,
                                           GT, args, kDopPadLds, st);
                        }))
@@ -986,13 +1060,14 @@ ds2_status_t ds2_lstm_fwd(int t_max, int n, int h, int num_dirs, const float* xp
                      dim3(256), 0, st, w_hh_f, w_hh_r, h, num_dirs, UB, KS, wp);
   const int kp = persist_ksw((KS + GW - 1) / GW, LKC_FWD);
   if (persistent && (h % 4) == 0 && kp > 0 && kp <= 32) {
-    const Instance fn = pick_instance(kFwdPersist[bts - 1], kp);
+    const Instance fn = pick_instance((stateful ? kFwdPersistSt : kFwdPersist)[bts - 1], kp);
     if (fn.fn != nullptr &&
         for_each_chunk("ds2_lstm_fwd", ho, D, BTW, ct, 0, st, &rc,
                        [&](int b0, int bt, Handoff c) {
                          int NB = b0 * GB * bts;
                          void* args[] = {&T, &N, &H, &D, &UB, &bt, &xproj, &wp, &b_hh_f, &b_hh_r,
-                                         &lens, &h_all, &c_all, &gates, &c.ctrs, &c.err, &NB};
+                                         &lens, &h_all, &c_all, &gates, &c.ctrs, &c.err, &NB,
+                                         &fs};
                          return launch_fn(fn, DS2_RUNG_LDS_PERSIST, bts, 0,
                                           mapped_grid(UB * D, bt), GT, args, 0, st);
                        }))
@@ -1001,9 +1076,30 @@ ds2_status_t ds2_lstm_fwd(int t_max, int n, int h, int num_dirs, const float* xp
   const int grid = mapped_grid(UB * D, BT);
   int step = 0;
   void* args[] = {&step, &T, &N, &H, &D, &UB, &BT, &xproj, &wp, &b_hh_f, &b_hh_r, &lens,
-                  &h_all, &c_all, &gates, &cs};
+                  &h_all, &c_all, &gates, &cs, &fs};
   for (step = 0; step < t_max; ++step) launch_step(step_fn, grid, GT, args, st);
   return launch_status("ds2_lstm_fwd");
+}
+
+extern "C" {
+
+ds2_status_t ds2_lstm_fwd(int t_max, int n, int h, int num_dirs, const float* xproj,
+                          const float* w_hh_f, const float* w_hh_r, const float* b_hh_f,
+                          const float* b_hh_r, const int* lens, float* h_all, float* c_all,
+                          float* gates, unsigned* err_out, void* ws, size_t ws_bytes,
+                          ds2_stream_t stream) {
+  return lstm_fwd_run(t_max, n, h, num_dirs, xproj, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lens, h_all,
+                      c_all, gates, nullptr, nullptr, nullptr, err_out, ws, ws_bytes, stream);
+}
+
+ds2_status_t ds2_lstm_fwd_state(int t_max, int n, int h, int num_dirs, const float* xproj,
+                                const float* w_hh_f, const float* w_hh_r, const float* b_hh_f,
+                                const float* b_hh_r, const int* lens, float* h_all, float* c_all,
+                                float* gates, const float* h0, const float* c0,
+                                const float* hproj0, unsigned* err_out, void* ws,
+                                size_t ws_bytes, ds2_stream_t stream) {
+  return lstm_fwd_run(t_max, n, h, num_dirs, xproj, w_hh_f, w_hh_r, b_hh_f, b_hh_r, lens, h_all,
+                      c_all, gates, h0, c0, hproj0, err_out, ws, ws_bytes, stream);
 }
 
 size_t ds2_lstm_bwd_workspace_size(int n, int h, int num_dirs) {

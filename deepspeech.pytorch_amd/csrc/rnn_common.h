@@ -56,6 +56,22 @@ __global__ void pack_bwd_kernel(const float* __restrict__ w_f, const float* __re
   }
 }
 
+// The initial state of a forward recurrence (ds2_gru_fwd_state, ds2_lstm_fwd_state; one
+// direction): h0, c0 [N][H] and hproj0 = h0 . W_hh^T [N][G H] (no bias).  It is the LAST
+// parameter of every forward kernel -- a parameter PACK `S... sp`, empty in the instantiations
+// the stateless entry points launch (their arguments and code stay what they were) and
+// <FwdState> in their twins (ST = sizeof...(S) != 0; the host passes the struct as the last
+// entry of every argument array, which the runtime does not read for an empty pack).  With ST
+// only step 0 differs: it still skips the W_hh product, its owner threads add hproj0 to the
+// (zero) reduced gate sums and start from h_prev = h0 (c_prev = c0).  The kernels read the
+// state ONCE, before the step loop, into owner registers (`cin`, zeroed after step 0), so no
+// state pointer is live across the loop.
+struct FwdState {
+  const float *h0, *c0, *hproj0;
+};
+__device__ __forceinline__ FwdState fwd_state() { return FwdState{nullptr, nullptr, nullptr}; }
+__device__ __forceinline__ FwdState fwd_state(FwdState s) { return s; }
+
 // Stage rows [n0, n0+16) x cols [kc0, kc1) of a row-major matrix (row stride ld,
 // valid rows < N) into hs[m][pitch], zero-filled.  8-byte accesses.
 __device__ __forceinline__ void stage_rows(const float* __restrict__ src, int64_t ld, int N,

@@ -99,6 +99,10 @@ struct RecFwd {
   float* h_all;
   float* c_all;   // LSTM only
   float* gates;   // nullable (no cache: inference, the one-gate RNN)
+  // the initial state (ds2_*_fwd_state): all NULL, or all set (c0: LSTM only) with one direction
+  const float *h0 = nullptr, *c0 = nullptr, *hproj0 = nullptr;
+  bool stateful() const { return h0 != nullptr; }
+  FwdState state() const { return FwdState{h0, c0, hproj0}; }
 };
 struct RecBwd {
   const float* dy;

@@ -7,5 +7,5 @@ of libds2hip.so (include/ds2hip.h).
 """
 from . import _lib  # noqa: F401
 
-__all__ = ["model", "decoder", "ctc", "data_loader", "optim", "trainer", "ops"]
+__all__ = ["model", "decoder", "ctc", "data_loader", "optim", "trainer", "ops", "streaming"]
 __version__ = "0.1.0"

@@ -94,6 +94,8 @@ _PROTOS = {
     "ds2_gru_cache_floats": (_sz, [_c_int, _c_int, _c_int, _c_int]),
     "ds2_gru_fwd": (_c_int, [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                              _vp, _vp, _vp, _sz, _vp]),
+    "ds2_gru_fwd_state": (_c_int, [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ds2_gru_bwd_workspace_size": (_sz, [_c_int, _c_int, _c_int]),
     "ds2_gru_bwd_grid": (_c_int, [_c_int, _c_int, _c_int]),
     "ds2_lstm_bwd_grid": (_c_int, [_c_int, _c_int, _c_int]),
@@ -137,6 +139,8 @@ _PROTOS = {
     "ds2_lstm_fwd_workspace_size": (_sz, [_c_int, _c_int, _c_int]),
     "ds2_lstm_fwd": (_c_int, [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                               _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ds2_lstm_fwd_state": (_c_int, [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ds2_lstm_bwd_workspace_size": (_sz, [_c_int, _c_int, _c_int]),
     "ds2_lstm_bwd": (_c_int, [_c_int, _c_int, _c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp,
                               _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -209,3 +209,51 @@ class GreedyDecoder(Decoder):
             strings.append([self._row_string(ids[b, :k])])
             offsets.append([torch.from_numpy(offs[b, :k].astype(np.int32))])
         return strings, offsets
+
+
+class StreamingGreedyDecoder(GreedyDecoder):
+    """Greedy CTC decoding of probabilities that arrive in chunks (ds2amd.streaming).
+
+    ``feed(probs [N, k, C]) -> (strings_delta, offsets_delta)``: what the k new frames add, per
+    stream a one-element list as GreedyDecoder.decode returns; offsets are absolute output-frame
+    indices.  The last frame of each call is carried and put in front of the next window of
+    ds2_greedy_decode, so a label repeated across a chunk edge collapses as it would inside
+    one; the carried frame's own re-emission (offset 0 of the window) is dropped.  ``text()``
+    returns everything decoded so far."""
+
+    def __init__(self, labels, blank_index=0):
+        super().__init__(labels, blank_index)
+        self._carry = None       # [N, 1, C]: the last frame seen
+        self._seen = 0           # frames decoded so far
+        self._text = None
+
+    def feed(self, probs):
+        if not probs.is_cuda:
+            raise RuntimeError("ds2amd StreamingGreedyDecoder.feed runs on the GPU (HIP kernel)")
+        n, k, _ = probs.shape
+        if self._text is None:
+            self._text = [''] * n
+        if k == 0:
+            return [['']] * n, [[torch.zeros(0, dtype=torch.int32)] for _ in range(n)]
+        lead = 0 if self._carry is None else 1
+        window = probs if lead == 0 else torch.cat([self._carry, probs], 1)
+        ids, offs, counts = self.decode_ids(window)
+        ids, offs, counts = ids.cpu().numpy(), offs.cpu().numpy(), counts.cpu().numpy()
+        strings, offsets = [], []
+        for b in range(n):
+            c = int(counts[b])
+            row, off = ids[b, :c], offs[b, :c]
+            if lead:
+                keep = off > 0           # offset 0 is the carried frame, emitted by the last call
+                row, off = row[keep], off[keep]
+            s = self._row_string(row)
+            self._text[b] += s
+            strings.append([s])
+            offsets.append([torch.from_numpy((off - lead + self._seen).astype(np.int32))])
+        self._carry = probs[:, -1:].detach().clone()
+        self._seen += k
+        return strings, offsets
+
+    def text(self):
+        """Per stream, the string decoded so far."""
+        return list(self._text or [])

@@ -1549,6 +1549,98 @@ class LSTMLayerFn(torch.autograd.Function):
         return (dx, None, None, None, *grads)
 
 
+def _state_call(kind, x, lens, weights, state):
+    """ds2_{gru,lstm}_fwd_state on one unidirectional layer, inference only.  state: () for the
+    zero state (NULL pointers: the stateless kernels), else (h0,) / (h0, c0) [N, H].  Returns
+    (h_all [T, N, H], c_all or None)."""
+    g_mult = 3 if kind == "gru" else 4
+    if len(weights) != 4:
+        raise ValueError(f"{kind}_forward_state: one direction's (w_ih, w_hh, b_ih, b_hh), "
+                         f"got {len(weights)} tensors")
+    if any(s is None for s in state) and any(s is not None for s in state):
+        raise ValueError(f"{kind}_forward_state: give the whole state or none of it")
+    state = tuple(s for s in state if s is not None)
+    tensors = (x, *weights, *state)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        raise RuntimeError(f"{kind}_forward_state is inference only: an input requires grad "
+                           "(call it under torch.no_grad(), on detached tensors)")
+    x = _need(x.detach(), kind + " x")
+    lens = _full_lens(lens, x.shape[1], x.device) if isinstance(lens, int) else \
+        _need(lens, kind + " lens", _I32)
+    w_ih, w_hh, b_ih, b_hh = (_need(w.detach(), kind + " weight") for w in weights)
+    t, n, _ = x.shape
+    h = w_hh.shape[1]
+    g = g_mult * h
+    dev = x.device
+    h_all = torch.empty(t, n, h, device=dev, dtype=_F32)
+    c_all = torch.empty(t, n, h, device=dev, dtype=_F32) if kind == "lstm" else None
+    if t == 0 or n == 0:
+        return h_all, c_all
+    xproj, _ = _rnn_input_proj(x, (w_ih, w_hh, b_ih, b_hh), 1, g)
+    hproj0 = None
+    if state:
+        state = tuple(_need(s.detach(), kind + " state") for s in state)
+        for s in state:
+            if tuple(s.shape) != (n, h):
+                raise ValueError(f"{kind}_forward_state: state {tuple(s.shape)} != {(n, h)}")
+        # hproj0 = h0 @ W_hh^T, no bias: the kernels add b_hh themselves
+        hproj0 = torch.empty(n, g, device=dev, dtype=_F32)
+        sgemm(state[0], w_hh, hproj0, m=n, n=g, k=h, trans_b=True, lda=h, ldb=h, ldc=g)
+    ws = _ws(_lib.size(f"ds2_{kind}_fwd_workspace_size", n, h, 1), dev)
+    outs = (h_all.data_ptr(),) + ((c_all.data_ptr(),) if kind == "lstm" else ())
+    st = tuple(_p(s) for s in state) if state else (None,) * (g_mult - 2)
+    _lib.call(f"ds2_{kind}_fwd_state", t, n, h, 1, xproj.data_ptr(), w_hh.data_ptr(), None,
+              b_hh.data_ptr(), None, lens.data_ptr(), *outs, None, *st, _p(hproj0),
+              rnn_status_word(dev).data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    return h_all, c_all
+
+
+_FULL_LENS = {}
+
+
+def _full_lens(t: int, n: int, device) -> torch.Tensor:
+    """[n] int32 lengths all equal to t, kept per (t, n, device): lock-step streams ask for the
+    same few counts at every chunk."""
+    key = (int(t), int(n), str(device))
+    v = _FULL_LENS.get(key)
+    if v is None:
+        if len(_FULL_LENS) > 256:
+            _FULL_LENS.clear()
+        v = _FULL_LENS[key] = torch.full((n,), int(t), dtype=_I32, device=device)
+    return v
+
+
+def _last_rows(all_t, lens, prev):
+    """Row len - 1 of [T, N, H] per sample, on the device; a sample with len = 0 keeps `prev`
+    (zeros when there was no state).  lens an int (every sample that long): a view, no launch."""
+    t, n, h = all_t.shape
+    if t == 0 or (isinstance(lens, int) and lens == 0):
+        return prev.clone() if prev is not None else all_t.new_zeros(n, h)
+    if isinstance(lens, int):
+        return all_t[lens - 1]
+    idx = (lens.long() - 1).clamp_(min=0).view(1, n, 1).expand(1, n, h)
+    last = all_t.gather(0, idx)[0]
+    keep = prev if prev is not None else torch.zeros_like(last)
+    return torch.where((lens > 0).view(n, 1), last, keep)
+
+
+def gru_forward_state(x, lens, weights, h0=None):
+    """One unidirectional GRU layer from the hidden state h0 [N, H] (None: zeros), inference
+    only: (y [T, N, H], h_last [N, H]) with h_last the state after each sample's last valid
+    step, so that feeding consecutive chunks of a sequence with the carried h_last equals one
+    call on the whole.  x [T, N, In], lens [N] int32 (valid steps of THIS chunk; or an int:
+    every sample that long, and h_last is then a view of y's row), weights
+    (w_ih, w_hh, b_ih, b_hh).  The recurrence kernel is chosen by the shape as GRULayerFn's."""
+    h_all, _ = _state_call("gru", x, lens, weights, (h0,))
+    return h_all, _last_rows(h_all, lens, h0)
+
+
+def lstm_forward_state(x, lens, weights, h0=None, c0=None):
+    """gru_forward_state for an LSTM layer: (y, h_last, c_last) from the state (h0, c0)."""
+    h_all, c_all = _state_call("lstm", x, lens, weights, (h0, c0))
+    return h_all, _last_rows(h_all, lens, h0), _last_rows(c_all, lens, c0)
+
+
 class LookaheadFn(torch.autograd.Function):
     """Lookahead conv (model.py:140-177) on [T, N, H], optionally fused with the
     Hardtanh(lo, hi) that follows it in DeepSpeech (model.py:329-333)."""

@@ -397,6 +397,21 @@ ds2_status_t ds2_gru_fwd(int t_max, int n, int h, int num_dirs, const float* xpr
                          const float* w_hh_f, const float* w_hh_r, const float* b_hh_f,
                          const float* b_hh_r, const int* lens, float* h_all, float* gates,
                          unsigned* err_out, void* ws, size_t ws_bytes, ds2_stream_t stream);
+/* ds2_gru_fwd from an initial hidden state (chunked / streaming inference of a unidirectional
+ * layer).  The two state arguments stand between `gates` and `err_out`:
+ *   h0     : [N][H]    the state before step 0
+ *   hproj0 : [N][3H]   h0 @ W_hh^T WITHOUT b_hh -- the caller's GEMM, as xproj is
+ * Only step 0 differs from ds2_gru_fwd: it adds hproj0 where the in-kernel W_hh product of the
+ * later steps stands and takes h_prev = h0.  The kernel is chosen by the shape exactly as
+ * without a state, and the workspace is ds2_gru_fwd_workspace_size's.  Both NULL: exactly
+ * ds2_gru_fwd.  One of the two NULL, or a state with num_dirs != 1: DS2_INVALID_VALUE, nothing
+ * launched.  A sample's final state is row len - 1 of h_all (rows t >= len are 0 as before);
+ * len = 0 leaves no row to read.                                                          */
+ds2_status_t ds2_gru_fwd_state(int t_max, int n, int h, int num_dirs, const float* xproj,
+                               const float* w_hh_f, const float* w_hh_r, const float* b_hh_f,
+                               const float* b_hh_r, const int* lens, float* h_all, float* gates,
+                               const float* h0, const float* hproj0, unsigned* err_out, void* ws,
+                               size_t ws_bytes, ds2_stream_t stream);
 size_t ds2_gru_bwd_workspace_size(int n, int h, int num_dirs);
 /* dy: [T][N][dy_dirs][H]; dy_dirs = 1: gradient of the direction-summed output
  * (model.py:107), dy_dirs = num_dirs: per-direction output gradient.
@@ -464,6 +479,17 @@ ds2_status_t ds2_lstm_fwd(int t_max, int n, int h, int num_dirs, const float* xp
                           const float* b_hh_r, const int* lens, float* h_all, float* c_all,
                           float* gates, unsigned* err_out, void* ws, size_t ws_bytes,
                           ds2_stream_t stream);
+/* ds2_lstm_fwd from an initial state, as ds2_gru_fwd_state: between `gates` and `err_out`
+ * stand h0 [N][H], c0 [N][H] and hproj0 [N][4H] = h0 @ W_hh^T (no bias).  All three NULL:
+ * exactly ds2_lstm_fwd; a partial set, or a state with num_dirs != 1: DS2_INVALID_VALUE,
+ * nothing launched.  The final state is row len - 1 of h_all and of c_all (a caller that
+ * carries on passes a c_all buffer).                                                      */
+ds2_status_t ds2_lstm_fwd_state(int t_max, int n, int h, int num_dirs, const float* xproj,
+                                const float* w_hh_f, const float* w_hh_r, const float* b_hh_f,
+                                const float* b_hh_r, const int* lens, float* h_all, float* c_all,
+                                float* gates, const float* h0, const float* c0,
+                                const float* hproj0, unsigned* err_out, void* ws,
+                                size_t ws_bytes, ds2_stream_t stream);
 size_t ds2_lstm_bwd_workspace_size(int n, int h, int num_dirs);
 /* dy as for ds2_gru_bwd.  dgates: [T][N][D][4H] gradient wrt the gate
  * pre-activations (= wrt xproj and wrt W_hh h + b_hh).                       */

@@ -22,6 +22,9 @@ static inline bool make_dims(ConvDims& g, int n, int c_in, int h_in, int w_in, i
   if (n < 0 || c_in < 1 || h_in < 1 || w_in < 1 || c_out < 1 || kh < 1 || kw < 1 || sh < 1 ||
       sw < 1 || ph < 0 || pw < 0)
     return false;
+  // a kernel larger than the padded input: the division below truncates toward zero and would
+  // give one output row / column for a deficit smaller than the stride
+  if (h_in + 2 * ph < kh || w_in + 2 * pw < kw) return false;
   g = ConvDims{n, c_in, h_in, w_in, c_out, kh, kw, sh, sw, ph, pw, 0, 0};
   g.ho = (h_in + 2 * ph - kh) / sh + 1;
   g.wo = (w_in + 2 * pw - kw) / sw + 1;

@@ -191,7 +191,15 @@ ds2_status_t ds2_sgemm_bf16_ws(int trans_a, int trans_b, int m, int n, int k, fl
  * by MaskConv model.py:63-79 when out_lens != NULL: output columns w >= out_lens[n]
  * are written as 0.  Width-stride-1 convolutions (conv2) run as direct
  * convolutions from LDS input patches and need the workspace (re-laid-out
- * filter taps); others (conv1) run as an implicit GEMM and ignore it.        */
+ * filter taps); others (conv1) run as an implicit GEMM and ignore it.
+ * Alignment: x, w, bias, dy, y, dx, dw and dbias need 4 bytes only (every kernel reads and
+ * writes them one float at a time; the fp16x3 sample maximum takes 16-byte loads only where a
+ * sample starts 16-byte aligned); the workspace must be 256-byte aligned (its sections are
+ * read with 16-byte loads at offsets that are multiples of 256).  out_lens[n] <= 0 gives an
+ * all-zero sample, out_lens[n] >= the output width masks nothing.  n == 0: DS2_OK, nothing
+ * launched; a size or stride < 1, a negative padding, or a kernel larger than the padded input
+ * (no output row or column): DS2_INVALID_VALUE; a workspace smaller than the plan of the call
+ * needs (never more than the size query): DS2_WORKSPACE_TOO_SMALL, nothing launched.       */
 size_t ds2_conv2d_workspace_size(int n, int c_in, int h_in, int w_in, int c_out, int kh, int kw,
                                  int sh, int sw, int ph, int pw);
 ds2_status_t ds2_conv2d_fwd(const float* x, const float* w, const float* bias, float* y,

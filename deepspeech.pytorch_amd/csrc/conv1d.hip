@@ -500,15 +500,6 @@ __global__ __launch_bounds__(256) void c1_general_kernel(const float* __restrict
   }
 }
 
-template <int MODE>
-ds2_status_t launch_general(const float* a, const float* b, const float* bias, float* c,
-                            const C1Dims& d, int64_t M, int64_t NN, int64_t K, hipStream_t st,
-                            const char* where) {
-  const dim3 grid(cdiv(NN, 64), cdiv(M, 64));
-  hipLaunchKernelGGL((c1_general_kernel<MODE>), grid, dim3(256), 0, st, a, b, bias, c, d, M, NN, K);
-  return launch_status(where);
-}
-
 // ---------------------------------------------------------------------------
 // host side
 bool dims_ok(int t, int n, int ci, int co, int k, int s, int p) {
@@ -549,15 +540,115 @@ size_t fwd_ws_fast(int t, int n, int ci, int co, int k, int t_out) {
          al256((size_t)(co > ci ? co : ci) * 4);
 }
 
-// forward, or dgrad as the forward of dy on the flipped weights (flip != 0: d describes
-// that convolution: ci = the real Cout, co = the real Cin, p = k - 1 - p)
+// the head of the wgrad workspace: ds2_colsum's (dbias) or, k = 1, ds2_sgemm_ws's
+size_t wgrad_ws_head(int ci, int co, int k, int s, int p, int64_t rows) {
+  size_t head = ds2_colsum_workspace_size((int)rows, co);
+  if (is_gemm(k, s, p)) {
+    const size_t g = ds2_sgemm_workspace_size(co, ci, (int)rows, 1);
+    if (g > head) head = g;
+  }
+  return head;
+}
+size_t wgrad_ws(int ci, int co, int k, int s, int p, int64_t rows) {
+  int kchunk = 0;
+  const int ns = wgrad_split(ci, co, k, rows, &kchunk);
+  return al256(wgrad_ws_head(ci, co, k, s, p, rows)) + al256((size_t)ci * 4) +
+         al256((size_t)co * 4) + al256((size_t)ns * co * ci * k * 4) + 256;
+}
+
+// What one call launches: the one place that chooses.  The entry points (and the test hook
+// ds2_test_conv1d_plan) switch on it; the values of `path` are the DS2_C1_* of ds2hip_test.h.
+struct C1Plan {
+  ds2_status_t status;   // != DS2_OK: returned before anything else is looked at
+  int path;              // DS2_C1_NONE with DS2_OK: an empty call
+  C1Dims d;              // the convolution the kernel computes (dgrad on the implicit GEMM: the
+                         // forward of dy on the flipped weights, ci / co swapped, p = k - 1 - p)
+  int stages;            // implicit GEMM: k pad32(d.ci) / 32
+  unsigned gx, gy, gz;   // grid of the convolution kernel (GEMM: ds2_sgemm_ws's own plan, 0)
+  int nsplit, kchunk;    // wgrad slabs
+  size_t ws_bytes;       // checked before anything is launched; 0: NULL is taken
+  int amax_passes;       // c1_rowmax_kernel / c1_colmax_kernel launches
+};
+
+// dir 0 forward, 1 dgrad, 2 wgrad; x_addr: the address of the gathered activations (forward: x,
+// dgrad: dy), which decides the float4 loader; amax_given: the caller supplies their maxima
+C1Plan c1_plan(int dir, int t, int n, int ci, int co, int k, int s, int p, uintptr_t x_addr,
+               bool amax_given) {
+  C1Plan pl{};
+  pl.path = DS2_C1_NONE;
+  pl.status = DS2_INVALID_VALUE;
+  if (!dims_ok(t, n, ci, co, k, s, p)) return pl;
+  const bool empty = t == 0 || n == 0;
+  if (dir != 2 && empty) {
+    pl.status = DS2_OK;
+    return pl;
+  }
+  if (t + 2 * p - k < 0 && !empty) return pl;
+  const int to = empty ? 0 : out_len(t, k, s, p);
+  const int64_t rows = (int64_t)to * n;
+  pl.status = DS2_UNSUPPORTED_SHAPE;
+  if (!fits_int((int64_t)co * ci * k)) return pl;
+  if (dir == 2 ? !fits_int(rows) : !fits_int((int64_t)k * (dir == 0 ? ci : co))) return pl;
+  if (!fits_int((int64_t)t * n)) return pl;
+  pl.status = DS2_OK;
+  if (empty) return pl;   // wgrad of an empty batch: the outputs are overwritten with zeros
+  pl.d = C1Dims{t, n, ci, co, k, s, p, to};
+  const bool fast = fast_enabled();
+  if (dir == 2) {
+    pl.ws_bytes = wgrad_ws(ci, co, k, s, p, rows);
+    if (fast && is_gemm(k, s, p)) {
+      pl.path = DS2_C1_GEMM;
+    } else if (fast && fast_wgrad(ci, co)) {
+      pl.path = DS2_C1_WGRAD_H3;
+      pl.nsplit = wgrad_split(ci, co, k, rows, &pl.kchunk);
+      pl.gx = cdiv((int64_t)k * ci, CT), pl.gy = cdiv(co, CT), pl.gz = pl.nsplit;
+      pl.amax_passes = amax_given ? 1 : 2;
+    } else {
+      pl.path = DS2_C1_GENERAL;
+      pl.gx = cdiv((int64_t)ci * k, 64), pl.gy = cdiv(co, 64), pl.gz = 1;
+    }
+    return pl;
+  }
+  if (fast && is_gemm(k, s, p)) {
+    pl.path = DS2_C1_GEMM;   // ds2_sgemm_ws takes any workspace, NULL included
+    return pl;
+  }
+  if (fast && (dir == 0 ? fast_fwd(ci, co, k) : fast_dgrad(ci, co, k, s, p))) {
+    if (dir == 1) pl.d = C1Dims{to, n, co, ci, k, 1, k - 1 - p, t};
+    const C1Dims& d = pl.d;
+    const int cip = pad32(d.ci);
+    const int tm = d.t_in > d.t_out ? d.t_in : d.t_out;
+    pl.path = d.ci % 4 == 0 && (x_addr & 15) == 0 ? DS2_C1_IGEMM_VEC : DS2_C1_IGEMM_SCALAR;
+    pl.stages = d.k * (cip / CK);
+    pl.gx = cdiv(d.co, CT), pl.gy = cdiv((int64_t)d.t_out * d.n, CT), pl.gz = 1;
+    pl.ws_bytes = al256((size_t)d.co * d.k * cip * 4) + al256((size_t)tm * d.n * 4) +
+                  al256((size_t)d.co * 4);
+    pl.amax_passes = amax_given && dir == 0 ? 1 : 2;
+    return pl;
+  }
+  pl.path = DS2_C1_GENERAL;
+  pl.gx = cdiv(dir == 0 ? co : ci, 64), pl.gy = cdiv((dir == 0 ? rows : (int64_t)t * n), 64), pl.gz = 1;
+  return pl;
+}
+
+template <int MODE>
+ds2_status_t launch_general(const float* a, const float* b, const float* bias, float* c,
+                            const C1Plan& pl, int64_t M, int64_t NN, int64_t K, hipStream_t st,
+                            const char* where) {
+  const dim3 grid(pl.gx, pl.gy);   // cdiv(NN, 64), cdiv(M, 64)
+  hipLaunchKernelGGL((c1_general_kernel<MODE>), grid, dim3(256), 0, st, a, b, bias, c, pl.d, M, NN, K);
+  return launch_status(where);
+}
+
+// forward, or dgrad as the forward of dy on the flipped weights (flip != 0: pl.d describes
+// that convolution).  The workspace holds pl.ws_bytes (checked by the caller).
 ds2_status_t run_igemm(const float* x, const float* w, const float* bias, float* y,
-                       const C1Dims& d, int flip, const unsigned* x_rmax_in, void* ws,
-                       size_t ws_bytes, hipStream_t st, const char* where) {
+                       const C1Plan& pl, int flip, const unsigned* x_rmax_in, void* ws,
+                       hipStream_t st, const char* where) {
+  const C1Dims& d = pl.d;
   const int cip = pad32(d.ci);
   const int tm = d.t_in > d.t_out ? d.t_in : d.t_out;
   const size_t b_w = al256((size_t)d.co * d.k * cip * 4), b_r = al256((size_t)tm * d.n * 4);
-  if (ws == nullptr || ws_bytes < b_w + b_r + al256((size_t)d.co * 4)) return DS2_WORKSPACE_TOO_SMALL;
   char* base = static_cast<char*>(ws);
   float* wr = reinterpret_cast<float*>(base);
   const unsigned* x_rmax = x_rmax_in != nullptr ? x_rmax_in : reinterpret_cast<unsigned*>(base + b_w);
@@ -572,10 +663,8 @@ ds2_status_t run_igemm(const float* x, const float* w, const float* bias, float*
   if (x_rmax_in == nullptr)   // else: the producer of x left its row maxima
     hipLaunchKernelGGL(c1_rowmax_kernel, dim3(cdiv(xr, 4)), dim3(256), 0, st, x, xr, d.ci,
                        reinterpret_cast<unsigned*>(base + b_w));
-  const int64_t M = (int64_t)d.t_out * d.n;
-  const dim3 grid(cdiv(d.co, CT), cdiv(M, CT));
-  const bool vec = d.ci % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
-  if (vec)
+  const dim3 grid(pl.gx, pl.gy);
+  if (pl.path == DS2_C1_IGEMM_VEC)
     hipLaunchKernelGGL((c1_igemm_kernel<true>), grid, dim3(256), 0, st, x, wr, bias, y, x_rmax,
                        w_rmax, d, cip);
   else
@@ -682,6 +771,7 @@ extern "C" {
 
 size_t ds2_conv1d_workspace_size(int t, int n, int c_in, int c_out, int k, int s, int p) {
   if (!dims_ok(t, n, c_in, c_out, k, s, p)) return 0;
+  if (t + 2 * p - k < 0 && t != 0 && n != 0) return 0;   // the entry points reject the shape
   const int to = out_len(t, k, s, p);
   size_t b = fwd_ws_fast(t, n, c_in, c_out, k, to);
   if (is_gemm(k, s, p) && fits_int((int64_t)t * n)) {
@@ -704,64 +794,54 @@ ds2_status_t ds2_conv1d_fwd_amax(const float* x, const float* w, const float* bi
                                  int t, int n, int c_in, int c_out, int k, int s, int p,
                                  const unsigned* x_row_amax, void* ws, size_t ws_bytes,
                                  ds2_stream_t stream) {
-  if (!dims_ok(t, n, c_in, c_out, k, s, p)) return DS2_INVALID_VALUE;
-  if (t == 0 || n == 0) return DS2_OK;
-  if (t + 2 * p - k < 0) return DS2_INVALID_VALUE;
-  const int to = out_len(t, k, s, p);
-  const int64_t M = (int64_t)to * n;
-  if (!fits_int((int64_t)t * n) || !fits_int((int64_t)k * c_in) || !fits_int((int64_t)c_out * c_in * k))
-    return DS2_UNSUPPORTED_SHAPE;
+  const C1Plan pl = c1_plan(0, t, n, c_in, c_out, k, s, p, reinterpret_cast<uintptr_t>(x),
+                            x_row_amax != nullptr);
+  if (pl.status != DS2_OK || pl.path == DS2_C1_NONE) return pl.status;
   if (x == nullptr || w == nullptr || y == nullptr) return DS2_INVALID_VALUE;
-  const C1Dims d{t, n, c_in, c_out, k, s, p, to};
+  if (pl.ws_bytes != 0 && (ws == nullptr || ws_bytes < pl.ws_bytes)) return DS2_WORKSPACE_TOO_SMALL;
+  const int64_t M = (int64_t)pl.d.t_out * n;
   hipStream_t st = as_stream(stream);
-  if (fast_enabled()) {
-    if (is_gemm(k, s, p))
+  switch (pl.path) {
+    case DS2_C1_GEMM:
       return ds2_sgemm_ws(0, 1, (int)M, c_out, c_in, 1.f, x, c_in, 0, w, c_in, 0, 0.f, y, c_out, 0, 1,
                           bias, ws, ws_bytes, stream);
-    if (fast_fwd(c_in, c_out, k)) return run_igemm(x, w, bias, y, d, 0, x_row_amax, ws, ws_bytes, st, "ds2_conv1d_fwd");
+    case DS2_C1_IGEMM_VEC:
+    case DS2_C1_IGEMM_SCALAR:
+      return run_igemm(x, w, bias, y, pl, 0, x_row_amax, ws, st, "ds2_conv1d_fwd");
+    default:
+      return launch_general<0>(x, w, bias, y, pl, M, c_out, (int64_t)k * c_in, st, "ds2_conv1d_fwd");
   }
-  return launch_general<0>(x, w, bias, y, d, M, c_out, (int64_t)k * c_in, st, "ds2_conv1d_fwd");
 }
 
 ds2_status_t ds2_conv1d_dgrad(const float* dy, const float* w, float* dx, int t, int n, int c_in,
                               int c_out, int k, int s, int p, void* ws, size_t ws_bytes,
                               ds2_stream_t stream) {
-  if (!dims_ok(t, n, c_in, c_out, k, s, p)) return DS2_INVALID_VALUE;
-  if (t == 0 || n == 0) return DS2_OK;
-  if (t + 2 * p - k < 0) return DS2_INVALID_VALUE;
-  const int to = out_len(t, k, s, p);
-  if (!fits_int((int64_t)t * n) || !fits_int((int64_t)k * c_out) || !fits_int((int64_t)c_out * c_in * k))
-    return DS2_UNSUPPORTED_SHAPE;
+  const C1Plan pl = c1_plan(1, t, n, c_in, c_out, k, s, p, reinterpret_cast<uintptr_t>(dy), false);
+  if (pl.status != DS2_OK || pl.path == DS2_C1_NONE) return pl.status;
   if (dy == nullptr || w == nullptr || dx == nullptr) return DS2_INVALID_VALUE;
+  if (pl.ws_bytes != 0 && (ws == nullptr || ws_bytes < pl.ws_bytes)) return DS2_WORKSPACE_TOO_SMALL;
   const int64_t M = (int64_t)t * n;
   hipStream_t st = as_stream(stream);
-  if (fast_enabled()) {
-    if (is_gemm(k, s, p))
+  switch (pl.path) {
+    case DS2_C1_GEMM:
       return ds2_sgemm_ws(0, 0, (int)M, c_in, c_out, 1.f, dy, c_out, 0, w, c_in, 0, 0.f, dx, c_in, 0,
                           1, nullptr, ws, ws_bytes, stream);
-    if (fast_dgrad(c_in, c_out, k, s, p)) {
-      const C1Dims f{to, n, c_out, c_in, k, 1, k - 1 - p, t};
-      return run_igemm(dy, w, nullptr, dx, f, 1, nullptr, ws, ws_bytes, st, "ds2_conv1d_dgrad");
-    }
+    case DS2_C1_IGEMM_VEC:
+    case DS2_C1_IGEMM_SCALAR:
+      return run_igemm(dy, w, nullptr, dx, pl, 1, nullptr, ws, st, "ds2_conv1d_dgrad");
+    default:
+      return launch_general<1>(dy, w, nullptr, dx, pl, M, c_in, (int64_t)k * c_out, st,
+                               "ds2_conv1d_dgrad");
   }
-  const C1Dims d{t, n, c_in, c_out, k, s, p, to};
-  return launch_general<1>(dy, w, nullptr, dx, d, M, c_in, (int64_t)k * c_out, st, "ds2_conv1d_dgrad");
 }
 
 size_t ds2_conv1d_wgrad_workspace_size(int t, int n, int c_in, int c_out, int k, int s, int p) {
   if (!dims_ok(t, n, c_in, c_out, k, s, p)) return 0;
+  if (t + 2 * p - k < 0 && t != 0 && n != 0) return 0;   // the entry point rejects the shape
   const int to = out_len(t, k, s, p);
   const int64_t rows = (int64_t)to * n;
   if (!fits_int(rows)) return 0;
-  size_t head = ds2_colsum_workspace_size((int)rows, c_out);
-  if (is_gemm(k, s, p)) {
-    const size_t g = ds2_sgemm_workspace_size(c_out, c_in, (int)rows, 1);
-    if (g > head) head = g;
-  }
-  int kchunk = 0;
-  const int ns = wgrad_split(c_in, c_out, k, rows, &kchunk);
-  return al256(head) + al256((size_t)c_in * 4) + al256((size_t)c_out * 4) +
-         al256((size_t)ns * c_out * c_in * k * 4) + 256;
+  return wgrad_ws(c_in, c_out, k, s, p, rows);
 }
 
 ds2_status_t ds2_conv1d_wgrad(const float* dy, const float* x, float* dw, float* dbias, int t, int n,
@@ -775,39 +855,30 @@ ds2_status_t ds2_conv1d_wgrad_amax(const float* dy, const float* x, float* dw, f
                                    int n, int c_in, int c_out, int k, int s, int p,
                                    const unsigned* x_col_amax, void* ws, size_t ws_bytes,
                                    ds2_stream_t stream) {
-  if (!dims_ok(t, n, c_in, c_out, k, s, p)) return DS2_INVALID_VALUE;
-  if (t + 2 * p - k < 0 && t != 0 && n != 0) return DS2_INVALID_VALUE;
-  if (!fits_int((int64_t)c_out * c_in * k)) return DS2_UNSUPPORTED_SHAPE;
+  const C1Plan pl = c1_plan(2, t, n, c_in, c_out, k, s, p, 0, x_col_amax != nullptr);
+  if (pl.status != DS2_OK) return pl.status;
   hipStream_t st = as_stream(stream);
-  const int to = (t == 0 || n == 0) ? 0 : out_len(t, k, s, p);
-  const int64_t rows = (int64_t)to * n;
-  if (!fits_int(rows) || !fits_int((int64_t)t * n)) return DS2_UNSUPPORTED_SHAPE;
-  if (rows == 0) {   // an empty batch: the outputs are overwritten with the empty sum
+  if (pl.path == DS2_C1_NONE) {   // an empty batch: the outputs are overwritten with the empty sum
     if ((dw != nullptr && hipMemsetAsync(dw, 0, (size_t)c_out * c_in * k * 4, st) != hipSuccess) ||
         (dbias != nullptr && hipMemsetAsync(dbias, 0, (size_t)c_out * 4, st) != hipSuccess))
       return launch_status("ds2_conv1d_wgrad");
     return DS2_OK;
   }
   if (dy == nullptr || x == nullptr || dw == nullptr) return DS2_INVALID_VALUE;
-  if (ws == nullptr || ws_bytes < ds2_conv1d_wgrad_workspace_size(t, n, c_in, c_out, k, s, p))
-    return DS2_WORKSPACE_TOO_SMALL;
-  size_t head = ds2_colsum_workspace_size((int)rows, c_out);
-  if (is_gemm(k, s, p)) {
-    const size_t g = ds2_sgemm_workspace_size(c_out, c_in, (int)rows, 1);
-    if (g > head) head = g;
-  }
-  head = al256(head);
+  if (ws == nullptr || ws_bytes < pl.ws_bytes) return DS2_WORKSPACE_TOO_SMALL;
+  const C1Dims& d = pl.d;
+  const int64_t rows = (int64_t)d.t_out * n;
+  const size_t head = al256(wgrad_ws_head(c_in, c_out, k, s, p, rows));
   char* base = static_cast<char*>(ws);
   if (dbias != nullptr) {
     const ds2_status_t e = ds2_colsum(dy, (int)rows, c_out, c_out, dbias, 0, base, head, stream);
     if (e != DS2_OK) return e;
   }
-  const C1Dims d{t, n, c_in, c_out, k, s, p, to};
-  if (fast_enabled()) {
-    if (is_gemm(k, s, p))
+  switch (pl.path) {
+    case DS2_C1_GEMM:
       return ds2_sgemm_ws(1, 0, c_out, c_in, (int)rows, 1.f, dy, c_out, 0, x, c_in, 0, 0.f, dw, c_in,
                           0, 1, nullptr, base, head, stream);
-    if (fast_wgrad(c_in, c_out)) {
+    case DS2_C1_WGRAD_H3: {
       unsigned* x_cmax = reinterpret_cast<unsigned*>(base + head);
       unsigned* dy_cmax = reinterpret_cast<unsigned*>(base + head + al256((size_t)c_in * 4));
       float* part = reinterpret_cast<float*>(base + head + al256((size_t)c_in * 4) +
@@ -819,19 +890,29 @@ ds2_status_t ds2_conv1d_wgrad_amax(const float* dy, const float* x, float* dw, f
                            t * n, c_in, x_cmax);
       hipLaunchKernelGGL(c1_colmax_kernel, dim3(cdiv(rows, 128)), dim3(256), 0, st, dy, (int)rows,
                          c_out, dy_cmax);
-      int kchunk = 0;
-      const int ns = wgrad_split(c_in, c_out, k, rows, &kchunk);
-      const dim3 grid(cdiv((int64_t)k * c_in, CT), cdiv(c_out, CT), ns);
-      hipLaunchKernelGGL(c1_wgrad_kernel, grid, dim3(256), 0, st, dy, x, part, dy_cmax,
-                         x_col_amax != nullptr ? x_col_amax : x_cmax, d, kchunk);
+      hipLaunchKernelGGL(c1_wgrad_kernel, dim3(pl.gx, pl.gy, pl.gz), dim3(256), 0, st, dy, x, part,
+                         dy_cmax, x_col_amax != nullptr ? x_col_amax : x_cmax, d, pl.kchunk);
       const int64_t tot = (int64_t)c_out * c_in * k;
-      hipLaunchKernelGGL(c1_wgrad_reduce_kernel, dim3(ew_grid(tot)), dim3(256), 0, st, part, ns,
-                         c_out, c_in, k, dw);
+      hipLaunchKernelGGL(c1_wgrad_reduce_kernel, dim3(ew_grid(tot)), dim3(256), 0, st, part,
+                         pl.nsplit, c_out, c_in, k, dw);
       return launch_status("ds2_conv1d_wgrad");
     }
+    default:
+      return launch_general<2>(dy, x, nullptr, dw, pl, c_out, (int64_t)c_in * k, rows, st,
+                               "ds2_conv1d_wgrad");
   }
-  return launch_general<2>(dy, x, nullptr, dw, d, c_out, (int64_t)c_in * k, rows, st,
-                           "ds2_conv1d_wgrad");
+}
+
+ds2_status_t ds2_test_conv1d_plan(int dir, int t, int n, int c_in, int c_out, int k, int s, int p,
+                                  unsigned long long x_addr, int* out) {
+  if (dir < 0 || dir > 6 || (dir & 3) == 3 || out == nullptr) return DS2_INVALID_VALUE;
+  const C1Plan pl = c1_plan(dir & 3, t, n, c_in, c_out, k, s, p, (uintptr_t)x_addr, (dir & 4) != 0);
+  if (pl.status != DS2_OK) return pl.status;
+  const int vals[10] = {pl.path, pl.stages, (int)pl.gx, (int)pl.gy, (int)pl.gz, pl.nsplit, pl.kchunk,
+                        static_cast<int>(pl.ws_bytes & 0xffffffffu),
+                        static_cast<int>((uint64_t)pl.ws_bytes >> 32), pl.amax_passes};
+  for (int i = 0; i < 10; ++i) out[i] = vals[i];
+  return DS2_OK;
 }
 
 ds2_status_t ds2_nct_to_tnc(const float* x, int n, int c, int t, float* y, ds2_stream_t stream) {

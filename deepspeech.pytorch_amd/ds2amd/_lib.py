@@ -124,6 +124,7 @@ _PROTOS = {
     "ds2_test_beam_stamps": (_c_int, [_vp]),
     "ds2_test_rnn_last_launch": (_c_int, [_vp]),
     "ds2_test_conv2d_plan": (_c_int, [_c_int] * 12 + [_vp]),
+    "ds2_test_conv1d_plan": (_c_int, [_c_int] * 8 + [_c_u64, _vp]),
     "ds2_test_sgemm_plan": (_c_int, [_c_int] * 6 + [_c_u64, _c_i64, _c_i64] * 3
                             + [_c_int, _c_u64, _c_int, _sz, _c_int, _c_int, _vp]),
     "ds2_test_sgemm_cover": (ctypes.c_longlong, [_c_int] * 12),

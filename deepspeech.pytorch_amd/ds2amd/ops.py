@@ -420,6 +420,29 @@ def _conv1d_dims(x_shape, w_shape, stride, padding):
     return (t, n, ci, co, k, int(stride), int(padding))
 
 
+# the DS2_C1_* paths of include/ds2hip_test.h (DESIGN.md "Conv1d dispatch")
+CONV1D_PATHS = ("none", "gemm", "igemm_vec", "igemm_scalar", "wgrad_h3", "general")
+Conv1dPlan = collections.namedtuple("Conv1dPlan",
+                                    "path stages gx gy gz nsplit kchunk ws_bytes amax_passes")
+
+
+def conv1d_plan(direction, x_shape, w_shape, stride, padding, addr=0,
+                amax_given=False) -> Conv1dPlan:
+    """What conv1d_fwd ("fwd"), conv1d_dgrad ("dgrad") or conv1d_wgrad ("wgrad") launches for
+    x [T, N, Cin] and w [Cout, Cin, k] under the current DS2_CONV1D: the library's own plan,
+    host only (no device, nothing launched).  addr: the address of x (forward) or dy (dgrad),
+    which decides the float4 loader; amax_given: the caller supplies x's maxima.  Raises
+    Ds2Error where the entry point returns DS2_INVALID_VALUE or DS2_UNSUPPORTED_SHAPE."""
+    t, n, ci = x_shape
+    co, _, k = w_shape
+    out = (ctypes.c_int * 10)()
+    _lib.call("ds2_test_conv1d_plan",
+              ("fwd", "dgrad", "wgrad").index(direction) + (4 if amax_given else 0), t, n, ci, co,
+              k, int(stride), int(padding), int(addr), ctypes.addressof(out))
+    v = list(out)
+    return Conv1dPlan(CONV1D_PATHS[v[0]], *v[1:7], (v[8] << 32) | (v[7] & 0xffffffff), v[9])
+
+
 def conv1d_fwd(x, weight, bias, stride: int, padding: int, x_row_amax=None):
     """nn.Conv1d on time-major activations: x [T, N, Cin] -> [T_out, N, Cout]; weight
     [Cout, Cin, k] in torch's layout (ds2_conv1d_fwd_amax).  x_row_amax: x's row maxima

@@ -228,8 +228,20 @@ ds2_status_t ds2_conv2d_wgrad(const float* dy, const float* x, float* dw, float*
  * weights are re-laid into the workspace and the operand scales computed there per call);
  * k = 1, s = 1, p = 0 runs on ds2_sgemm_ws; shapes the implicit GEMM declines (channel
  * counts below 16, dgrad with s > 1) and DS2_CONV1D=0 run general fp32 FMA kernels.
- * t == 0 or n == 0: DS2_OK, nothing launched; negative sizes, k or s < 1 and t_out <= 0:
- * DS2_INVALID_VALUE.  One workspace size serves forward and dgrad.               */
+ * t == 0 or n == 0: DS2_OK, nothing launched; negative sizes, k or s < 1 and t_out <= 0
+ * (t + 2 p - k < 0): DS2_INVALID_VALUE, and the size queries return 0.  One workspace size
+ * serves forward and dgrad.
+ * Alignment: x, w, bias, dy, y, dx, dw and dbias need 4 bytes only.  The implicit GEMM reads
+ * the activations it gathers (x; dy in dgrad) with 16-byte loads only where their address is
+ * 16-byte aligned and their channel count a multiple of 4, one float at a time otherwise;
+ * every other kernel of the family reads and writes the caller's arrays one float at a time.
+ * The workspace must be 256-byte aligned (its sections are read with 16-byte loads); what it
+ * holds on entry does not matter.  Caller-supplied maxima (the _amax entries) need 4 bytes.
+ * Workspace: every call checks for what the kernel it chose uses, never more than the size
+ * query, and returns DS2_WORKSPACE_TOO_SMALL before anything is launched.  NULL is taken by
+ * forward and dgrad where they run the general kernels or ds2_sgemm_ws (k = 1, s = 1, p = 0: a
+ * smaller workspace is only slower there), and by every empty call; ds2_conv1d_wgrad always
+ * needs its size query's bytes unless the batch is empty.                       */
 size_t ds2_conv1d_workspace_size(int t, int n, int c_in, int c_out, int k, int s, int p);
 ds2_status_t ds2_conv1d_fwd(const float* x, const float* w, const float* bias, float* y, int t,
                             int n, int c_in, int c_out, int k, int s, int p, void* ws,

@@ -114,6 +114,34 @@ ds2_status_t ds2_test_conv2d_plan(int dir, int n, int c_in, int h_in, int w_in, 
                                   int kw, int sh, int sw, int ph, int pw, int* out);
 
 /* ------------------------------------------------------------------------ */
+/* ds2_test_conv1d_plan: what ds2_conv1d_fwd (dir 0), ds2_conv1d_dgrad (1) or ds2_conv1d_wgrad
+ * (2) would launch for the shape under the current DS2_CONV1D.  Host only, no device needed,
+ * nothing launched: it calls the function the entry points switch on (csrc/conv1d.hip
+ * c1_plan).  dir + 4: the same for ds2_conv1d_fwd_amax / ds2_conv1d_wgrad_amax with the
+ * maxima supplied (dgrad: no such entry, as dir 1).  x_addr: the address of the gathered
+ * activations (forward: x, dgrad: dy; ignored by wgrad); only its low four bits are used.
+ * Returns DS2_INVALID_VALUE or DS2_UNSUPPORTED_SHAPE exactly where the entry point does before
+ * it looks at a pointer.  out[10] =
+ *   [0] path: a DS2_C1_* value, a row of DESIGN.md's Conv1d dispatch table (NONE: an empty
+ *       call: forward and dgrad launch nothing, wgrad zero-fills dw and dbias)
+ *   [1] stages of the implicit GEMM, k * pad32(channels of the gathered operand) / 32; else 0
+ *   [2] [3] [4] grid x, y, z of the convolution kernel (GEMM: 0, ds2_sgemm_ws plans its own)
+ *   [5] nsplit  [6] kchunk: the slabs of the fp16x3 wgrad's K = t_out n (else 0)
+ *   [7] [8] workspace bytes the entry point checks for before it launches, low and high 32
+ *       bits (never more than the size query); 0: the path takes NULL
+ *   [9] row-maxima (implicit GEMM) or column-maxima (WGRAD_H3) passes launched            */
+enum {
+  DS2_C1_NONE = 0,
+  DS2_C1_GEMM = 1,          /* k = 1, s = 1, p = 0: ds2_sgemm_ws */
+  DS2_C1_IGEMM_VEC = 2,     /* c1_igemm_kernel<true>: float4 loads of the activations */
+  DS2_C1_IGEMM_SCALAR = 3,  /* c1_igemm_kernel<false> */
+  DS2_C1_WGRAD_H3 = 4,      /* c1_wgrad_kernel + c1_wgrad_reduce_kernel */
+  DS2_C1_GENERAL = 5        /* c1_general_kernel<dir> */
+};
+ds2_status_t ds2_test_conv1d_plan(int dir, int t, int n, int c_in, int c_out, int k, int s, int p,
+                                  unsigned long long x_addr, int* out);
+
+/* ------------------------------------------------------------------------ */
 /* ds2_test_sgemm_plan: what ds2_sgemm / ds2_sgemm_ws / ds2_sgemm_amax_ws (kind 0),
  * ds2_sgemm_bf16_ws (kind 1) or ds2_bgemm_nt (kind 2: trans and batch ignored, ld in bf16
  * elements) would launch under the current DS2_GEMM_* environment.  Host only, no device

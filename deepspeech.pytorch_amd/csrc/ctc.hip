@@ -1844,6 +1844,9 @@ ds2_status_t ds2_greedy_decode(const float* probs, int n, int t_max, int c, int6
                                ds2_stream_t stream) {
   if (n < 0 || t_max < 0 || c < 1 || blank < 0 || blank >= c) return DS2_INVALID_VALUE;
   if (n == 0) return DS2_OK;
+  if (out_counts == nullptr) return DS2_INVALID_VALUE;
+  if (t_max > 0 && (probs == nullptr || out_ids == nullptr || out_offsets == nullptr))
+    return DS2_INVALID_VALUE;
   hipLaunchKernelGGL(greedy_kernel, dim3(cdiv(n, 4)), dim3(256), 0, as_stream(stream), probs, n,
                      t_max, c, stride_n, stride_t, sizes, blank, out_ids, out_offsets, out_counts,
                      argmax_out);

@@ -203,6 +203,7 @@ ds2_status_t ds2_lookahead_bwd(const float* dy, const float* y, float lo, float 
       return launch_status("ds2_lookahead_bwd");
     return DS2_OK;
   }
+  if (dy == nullptr || w == nullptr || (dw != nullptr && x == nullptr)) return DS2_INVALID_VALUE;
   const int64_t cols = (int64_t)n * h;
   if ((int64_t)t * cols * 4 >= (1ll << 31) - 64) return DS2_UNSUPPORTED_SHAPE;
   const int tiles = cdiv(t, LA_TT);

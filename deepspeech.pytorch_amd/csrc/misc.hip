@@ -450,6 +450,7 @@ ds2_status_t ds2_dirsum(const float* h_all, int rows, int num_dirs, int h, float
   if (rows < 0 || num_dirs < 1 || h < 0) return DS2_INVALID_VALUE;
   int64_t total = (int64_t)rows * h;
   if (total == 0) return DS2_OK;
+  if (h_all == nullptr || y == nullptr) return DS2_INVALID_VALUE;
   hipLaunchKernelGGL(dirsum_kernel, dim3(grid_for(total, 256)), dim3(256), 0, as_stream(stream),
                      h_all, (int64_t)rows, num_dirs, h, y);
   return launch_status("ds2_dirsum");
@@ -464,6 +465,7 @@ ds2_status_t ds2_colsum(const float* x, int rows, int cols, int64_t ld, float* o
                         int accumulate, void* ws, size_t ws_bytes, ds2_stream_t stream) {
   if (rows < 0 || cols < 0 || ld < cols) return DS2_INVALID_VALUE;
   if (cols == 0) return DS2_OK;
+  if (out == nullptr || (rows > 0 && x == nullptr)) return DS2_INVALID_VALUE;
   if (ws == nullptr || ws_bytes < ds2_colsum_workspace_size(rows, cols))
     return DS2_WORKSPACE_TOO_SMALL;
   int chunks = rows / 64;
@@ -485,6 +487,7 @@ ds2_status_t ds2_softmax_tnc(const float* logits, int t_max, int n, int c, float
   if (t_max < 0 || n < 0 || c < 1 || c > 64) return DS2_UNSUPPORTED_SHAPE;
   int rows = t_max * n;
   if (rows == 0) return DS2_OK;
+  if (logits == nullptr || probs == nullptr) return DS2_INVALID_VALUE;
   hipLaunchKernelGGL(softmax_tnc_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, as_stream(stream),
                      logits, t_max, n, c, probs);
   return launch_status("ds2_softmax_tnc");
@@ -495,6 +498,7 @@ ds2_status_t ds2_softmax_tnc_bwd(const float* probs, const float* dprobs, int t_
   if (t_max < 0 || n < 0 || c < 1 || c > 64) return DS2_UNSUPPORTED_SHAPE;
   int rows = t_max * n;
   if (rows == 0) return DS2_OK;
+  if (probs == nullptr || dprobs == nullptr || dlogits == nullptr) return DS2_INVALID_VALUE;
   hipLaunchKernelGGL(softmax_tnc_bwd_kernel, dim3(cdiv(rows, 4)), dim3(256), 0,
                      as_stream(stream), probs, dprobs, t_max, n, c, dlogits, accumulate);
   return launch_status("ds2_softmax_tnc_bwd");
@@ -573,6 +577,7 @@ ds2_status_t ds2_nan_guard(float* x, int64_t numel, int zero_nans, int* flag,
                            unsigned char* mask, ds2_stream_t stream) {
   if (numel < 0 || flag == nullptr) return DS2_INVALID_VALUE;
   if (numel == 0) return DS2_OK;
+  if (x == nullptr) return DS2_INVALID_VALUE;
   hipLaunchKernelGGL(nan_guard_kernel, dim3(grid_for(numel, 256)), dim3(256), 0,
                      as_stream(stream), x, numel, zero_nans, flag, mask);
   return launch_status("ds2_nan_guard");
@@ -580,7 +585,7 @@ ds2_status_t ds2_nan_guard(float* x, int64_t numel, int zero_nans, int* flag,
 
 ds2_status_t ds2_zero_masked(float* x, const unsigned char* mask, int64_t numel, const int* flag,
                              ds2_stream_t stream) {
-  if (numel < 0 || (numel > 0 && mask == nullptr)) return DS2_INVALID_VALUE;
+  if (numel < 0 || (numel > 0 && (mask == nullptr || x == nullptr))) return DS2_INVALID_VALUE;
   if (numel == 0) return DS2_OK;
   hipLaunchKernelGGL(zero_masked_kernel, dim3(grid_for(numel, 256)), dim3(256), 0,
                      as_stream(stream), x, mask, numel, flag);
@@ -591,6 +596,7 @@ ds2_status_t ds2_scale_by_device_scalar(float* x, int64_t numel, const float* sc
                                         ds2_stream_t stream) {
   if (numel < 0 || scalar == nullptr) return DS2_INVALID_VALUE;
   if (numel == 0) return DS2_OK;
+  if (x == nullptr) return DS2_INVALID_VALUE;
   hipLaunchKernelGGL(scale_kernel, dim3(grid_for(numel, 256)), dim3(256), 0, as_stream(stream),
                      x, numel, scalar);
   return launch_status("ds2_scale_by_device_scalar");

@@ -539,7 +539,12 @@ ds2_status_t ds2_lookahead_fwd(const float* x, int t, int n, int h, const float*
                                int clamp, float lo, float hi, float* y, ds2_stream_t stream);
 /* Backward: y = the clamped forward output (or NULL when not clamped: dz = dy,
  * else dz = dy where lo < y < hi).  dx (or NULL) overwritten; dw (or NULL)
- * overwritten, deterministic.                                                 */
+ * overwritten, deterministic (exact zeros when t == 0 or n == 0).  The workspace is
+ * needed for dw only.  A NULL dy or w, or a NULL x when dw is asked for, is
+ * DS2_INVALID_VALUE.  ds2_dirsum, ds2_colsum, ds2_softmax_tnc[_bwd], ds2_greedy_decode,
+ * ds2_nan_guard, ds2_zero_masked and ds2_scale_by_device_scalar likewise refuse, before
+ * they launch, a NULL data pointer they would dereference, and return DS2_OK whatever
+ * the pointers when there is no work.                                           */
 size_t ds2_lookahead_bwd_workspace_size(int t, int n, int h, int context);
 ds2_status_t ds2_lookahead_bwd(const float* dy, const float* y, float lo, float hi,
                                const float* x, int t, int n, int h, const float* w, int context,
@@ -623,8 +628,11 @@ ds2_status_t ds2_greedy_decode(const float* probs, int n, int t_max, int c, int6
  * Decoder.cer / .wer) over id sequences: a = decoded ids [n][a_stride] with a_lens,
  * b = reference ids flat with b_offsets / b_lens.  out[4*i .. 4*i+3] = {word
  * distance, char distance (spaces removed), max(#reference words, 1),
- * max(#reference non-space chars, 1)}.  Sequences longer than 2048 ids / 1024 words
- * set *err != 0 and distance -1 (err must be zeroed by the caller).           */
+ * max(#reference non-space chars, 1)}.  The limits count what the distances run over:
+ * a sequence with more than 2048 non-space ids or more than 1024 words (either side) sets
+ * *err != 0 and both of its pair's distances to -1, with the two reference counts still
+ * right; spaces do not count, so a longer raw sequence is accepted.  The other pairs of
+ * the launch are scored as usual.  err must be zeroed by the caller.          */
 ds2_status_t ds2_edit_distance(const int* a_ids, int64_t a_stride, const int* a_lens,
                                const int* b_ids, const int* b_offsets, const int* b_lens, int n,
                                int space_id, int* out, int* err, ds2_stream_t stream);

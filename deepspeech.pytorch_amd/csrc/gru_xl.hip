@@ -134,12 +134,37 @@ __device__ __forceinline__ bool xl_group_local(unsigned* xtab, int ub, int UBX, 
   return *lds_word != 0;
 }
 
-__device__ __forceinline__ void xl_store(u32x4 v, __amdgpu_buffer_rsrc_t rs, int off, bool local) {
+// voff: the lane's byte offset (loop-invariant where it can be), soff: the wave-uniform part
+__device__ __forceinline__ void xl_store(u32x4 v, __amdgpu_buffer_rsrc_t rs, int voff, int soff,
+                                         bool local) {
   if (local)
-    __builtin_amdgcn_raw_buffer_store_b128(v, rs, off, 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b128(v, rs, voff, soff, 0);
   else
-    __builtin_amdgcn_raw_buffer_store_b128(v, rs, off, 0, kSc1);
+    __builtin_amdgcn_raw_buffer_store_b128(v, rs, voff, soff, kSc1);
 }
+
+// The waves' partial sums on their way to the owners.  An accumulator register holds the hi
+// products' row m (< 8) in lane L < 32 and the lo products' row m + 8 in lane L + 32, and the
+// owner adds exactly that pair first -- so the producing wave adds it (the same add, the same
+// bits) before anything is written: one 32-lane swap per pair of registers (a: unit half 0, b:
+// unit half 1) leaves a's pair in the two operands of lanes 0-31 and b's in those of lanes
+// 32-63.  Half the LDS bytes written, half the reads per owner.
+__device__ __forceinline__ float xl_fold(float a, float b) {
+  const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, a),
+                                                  __builtin_bit_cast(unsigned, b), false, false);
+  // (the elements into scalars first: a bit cast applied to r[1] directly reads element 0)
+  const unsigned r0 = r[0], r1 = r[1];
+  return __builtin_bit_cast(float, r0) + __builtin_bit_cast(float, r1);
+}
+// Folded partials in LDS: [wave][gate] blocks of 8 sample rows x 32 units, the unit's bit 4
+// flipped in rows 4-7 (a wave writes rows i and 4 + i of 16 + 16 units at once: 32 banks).
+// Where a lane writes its value of row 4 ((lane >> 4) & 1) + i: xl_fold_at(lane) + 32 i
+__device__ __forceinline__ int xl_fold_at(int lane) {
+  const int hi4 = (lane >> 4) & 1;
+  return hi4 * 128 + (((lane & 15) + 16 * (lane >> 5)) ^ (16 * hi4));
+}
+// where the owner of (sample m, unit u) reads it
+__device__ __forceinline__ int xl_fold_own(int m, int u) { return m * 32 + (u ^ ((m >> 2) << 4)); }
 
 // max of v over the lane's half of the wave (lanes 0-31 / 32-63: one sample's 32 units), in
 // every lane: four DPP steps inside each row of 16 (quad swaps, half-row and row mirrors),
@@ -282,8 +307,7 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
   constexpr bool ST = sizeof...(S) != 0;
   const FwdState st = fwd_state(sp...);
   constexpr int NCT = 6;
-  constexpr int RC = 3 * LU + 1;   // reduction row pitch
-  __shared__ float red[LW * 16 * RC];
+  __shared__ float red[LW * 3 * 256];   // folded partials (xl_fold_at); the start-up row maxima
   __shared__ __attribute__((aligned(16))) _Float16 stg[64 * 8];
   __shared__ float unsc[3 * LU];
   __shared__ __attribute__((aligned(16))) float pin[3 * 256];    // xproj (r, z, n) [gate][sample][unit]
@@ -416,14 +440,18 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
   settle(bias_z);
   settle(bias_n);
   const int shi = xl_frag_hi(m, u), slo = shi + 64;   // this owner's stg slots (lo: row + 8)
+  const int fold_at = xl_fold_at(lane), fold_own = xl_fold_own(m, u);
   // The step's HBM traffic (xproj in; h_all, gates out) goes through LDS, issued by waves 1-3
   // only: wave 0 publishes, and its drain before the publish would otherwise wait for those
   // loads and stores (vmcnt counts in order).  Inputs are loaded one step ahead, after the
   // wave's hand-off loop (so they never sit in front of its tile loads); outputs of step s are
   // stored during step s + 1.  io float4 q: sample q / 24, gate (q % 24) / 8, units 4 (q % 8).
-  // Addresses are set up once: each io float4 has a fixed row pointer advanced by a fixed
-  // stride per step (per-step 64-bit index arithmetic and lane-divergent branches cost ~1 us
-  // of VALU latency at one wave per SIMD); masked lanes load from a valid address.
+  // Addresses are set up once: each io float4 has a running row pointer that one add per step
+  // advances by a signed loop-invariant stride, negative in the reverse direction (per-step
+  // 64-bit index arithmetic -- a 64-bit multiply is four quarter-rate instructions -- and
+  // lane-divergent branches cost ~1 us of VALU latency at one wave per SIMD); masked lanes load
+  // from a valid address.  load_in and store_out are therefore called once per step, in step
+  // order.
   const bool io = wave != 0;
   const int q = io ? (int)threadIdx.x - 64 : 0;
   const int qm = q / 24, qg = (q % 24) >> 3, q4 = (q & 7) * 4;
@@ -431,7 +459,9 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
   const bool qv = io && qn < N;
   const int qlen = slen[qm];
   const float* xq = xproj + ((int64_t)qn * D + d) * 3 * H + qg * H + ub * LU + q4;
-  const int64_t xstep = (int64_t)N * D * 3 * H;
+  const int t_first = d == 0 ? 0 : T - 1;
+  const int64_t xstep = d == 0 ? (int64_t)N * D * 3 * H : -(int64_t)N * D * 3 * H;
+  const float* xp = kAblFixT ? xq : xq + t_first * ((int64_t)N * D * 3 * H);
   const f32x4 z4v = f32x4{0.f, 0.f, 0.f, 0.f};
   // the load (from a valid address when masked) and, separately, whether step st has a row:
   // the zero select happens when the value is staged -- a select right after the load would
@@ -441,8 +471,9 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     return !kAblLoads && qv && tt < qlen;
   };
   auto load_in = [&](int st) __attribute__((always_inline)) {
-    const int tt = d == 0 ? st : T - 1 - st;
-    return *reinterpret_cast<const f32x4*>(in_ok(st) ? xq + (kAblFixT ? 0 : tt) * xstep : xproj);
+    const f32x4 v = *reinterpret_cast<const f32x4*>(in_ok(st) ? xp : xproj);
+    if (!kAblFixT) xp += xstep;
+    return v;
   };
   // outputs: float4 idx = q + 192 k (< 320): sample idx / 40, field (idx % 40) / 8 (h, r, z,
   // n, W_hn h + b_hn), units 4 (idx % 8)
@@ -463,13 +494,18 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
       ob[k] = gates + ((int64_t)sn * D + d) * 4 * H + (f - 1) * H + ub * LU + o4;
       ostr[k] = (int64_t)N * D * 4 * H;
     }
+    ob[k] += t_first * ostr[k];
+    if (d != 0) ostr[k] = -ostr[k];
   }
-  auto store_out = [&](int st) __attribute__((always_inline)) {   // pout (step st) -> h_all, gates
-    const int tt = d == 0 ? st : T - 1 - st;
-#pragma unroll
-    for (int k = 0; k < 2; ++k)
-      if (ov[k])
-        *reinterpret_cast<f32x4*>(ob[k] + tt * ostr[k]) = *reinterpret_cast<const f32x4*>(pout + osrc[k]);
+  // pout -> h_all, gates, the rows of step 0 at the first call and of the next step at each
+  // call after it: both LDS reads, one wait, the stores
+  auto store_out = [&]() __attribute__((always_inline)) {
+    const f32x4 v0 = *reinterpret_cast<const f32x4*>(pout + osrc[0]);
+    const f32x4 v1 = *reinterpret_cast<const f32x4*>(pout + osrc[1]);
+    if (ov[0]) *reinterpret_cast<f32x4*>(ob[0]) = v0;
+    if (ov[1]) *reinterpret_cast<f32x4*>(ob[1]) = v1;
+    ob[0] += ostr[0];
+    ob[1] += ostr[1];
   };
   // one step ahead (vmcnt counts in order: a load still in flight would hold back the next
   // step's tile waits whatever its own use, so a longer prefetch distance buys nothing)
@@ -562,32 +598,43 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     }
     if (io) {
       if (s + 1 < T) xin = load_in(s + 1);
-      if (!kAblStores && s > 0) store_out(s - 1);
+      if (!kAblStores && s > 0) store_out();
     }
     trace_at(s, 3);
-    // the wave's partial: rows 4 (lane >> 4) + i (0-7 hi products, 8-15 lo products) of
-    // columns ct * 16 + (lane & 15) = gate * 32 + unit
+    // the wave's partial: acc[ct][i] is row 4 (lane >> 4) + i (0-7 hi products, 8-15 lo
+    // products) of column ct * 16 + (lane & 15) = gate * 32 + unit; hi + lo folded (xl_fold)
 #pragma unroll
-    for (int ct = 0; ct < NCT; ++ct)
+    for (int gt = 0; gt < 3; ++gt)
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        red[(wave * 16 + (lane >> 4) * 4 + i) * RC + ct * 16 + (lane & 15)] = acc[ct][i];
+        red[(wave * 3 + gt) * 256 + fold_at + 32 * i] = xl_fold(acc[2 * gt][i], acc[2 * gt + 1][i]);
     __syncthreads();
-    if (failed) {
-      xl_poison(cold, s, T, d != 0, d, 1, 1);
-      return;
-    }
+    // One batch of LDS reads.  The failure word (set, if at all, in front of the barrier above)
+    // rides along and is branched on at the publish barrier: read and tested right here it was
+    // an LDS round trip of its own in front of the first partial, every step.  A failed step's
+    // gate math runs on whatever the tiles held; nothing of it leaves the workgroup.  The
+    // partials and inputs come in the order the gate math wants them: r, whose sigmoid feeds the
+    // tanh, then W_hn h, then z.
+    const int fail = failed;
+    float pr[3][LW];
+#pragma unroll
+    for (int w4 = 0; w4 < LW; ++w4) pr[0][w4] = red[(w4 * 3 + 0) * 256 + fold_own];
+    const float xr = pin[m * LU + u];
+#pragma unroll
+    for (int w4 = 0; w4 < LW; ++w4) pr[2][w4] = red[(w4 * 3 + 2) * 256 + fold_own];
+    const float xn = pin[512 + m * LU + u];
+#pragma unroll
+    for (int w4 = 0; w4 < LW; ++w4) pr[1][w4] = red[(w4 * 3 + 1) * 256 + fold_own];
+    const float xz = pin[256 + m * LU + u];
     trace_at(s, 4);
-    float gh[3];
+    float gh[3];   // per gate ((((0 + p0) + p1) + p2) + p3), p = a wave's hi + lo
 #pragma unroll
     for (int gt = 0; gt < 3; ++gt) {
       float v = 0.f;
 #pragma unroll
-      for (int w4 = 0; w4 < LW; ++w4)
-        v += red[(w4 * 16 + m) * RC + gt * LU + u] + red[(w4 * 16 + m + 8) * RC + gt * LU + u];
+      for (int w4 = 0; w4 < LW; ++w4) v += pr[gt][w4];
       gh[gt] = v;
     }
-    const float xr = pin[m * LU + u], xz = pin[256 + m * LU + u], xn = pin[512 + m * LU + u];
     float hout = 0.f, r = 0.f, z = 0.f, nn = 0.f, ghn = 0.f;
     if constexpr (ST) {
       if (owner && t < len) {
@@ -618,19 +665,25 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
       stg[shi] = hi;
       stg[slo] = (_Float16)(v - (float)hi);
     }
+    // the publish slots' offsets do not depend on the step's data: scalars, ready before the
+    // barrier; the lane's part (lane * 16) is loop-invariant
+    const int pub_at = ((s % LSLOTS) * slot_floats + grp_off + ub * 256) * 4;
+    const int sen_at = (((s + 2) % LSLOTS) * slot_floats + grp_off + ub * 256) * 4;
     __syncthreads();
+    if (fail) {   // a wave's tile timed out: poison what is left, publish nothing
+      xl_poison(cold, s, T, d != 0, d, 1, 1);
+      return;
+    }
     if (wave == 0) {
-      const int toff = (grp_off + ub * 256 + lane * 4) * 4;
       const u32x4 v = desentinel(*reinterpret_cast<const u32x4*>(stg + lane * 8));
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // last step's sentinel store first
-      xl_store(v, x_rs, (s % LSLOTS) * slot_floats * 4 + toff, local);
-      xl_store(u32x4{kSentinel, kSentinel, kSentinel, kSentinel}, x_rs,
-               ((s + 2) % LSLOTS) * slot_floats * 4 + toff, local);
+      xl_store(v, x_rs, lane * 16, pub_at, local);
+      xl_store(u32x4{kSentinel, kSentinel, kSentinel, kSentinel}, x_rs, lane * 16, sen_at, local);
     }
     trace_at(s, 5);
   }
   __syncthreads();
-  if (io && !kAblStores) store_out(T - 1);
+  if (io && !kAblStores) store_out();
 }
 
 // ---------------------------------------------------------------------------------------
@@ -655,9 +708,8 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     unsigned* __restrict__ err_out, unsigned long long* __restrict__ stamps,
     double* __restrict__ dbp, unsigned* __restrict__ camax, float* __restrict__ rowp,
     int force_global) {
-  constexpr int RC = LU + 1;
   constexpr int LWP = 3;     // records in flight per wave beside the one multiplied
-  __shared__ __attribute__((aligned(8))) float red[LW * 16 * RC > 4 * LB * LU * 2 ? LW * 16 * RC : 4 * LB * LU * 2];
+  __shared__ __attribute__((aligned(8))) float red[4 * LB * LU * 2];   // folded partials (xl_fold_at); the epilogue's sums
   __shared__ __attribute__((aligned(16))) _Float16 stg[3 * 64 * 8];
   __shared__ __attribute__((aligned(16))) float stsc[LB];
   __shared__ float colmx[LW * LU];
@@ -786,6 +838,7 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
   __syncthreads();
   const int len = slen[m];
   const int shi = xl_frag_hi(m, u), slo = shi + 64;
+  const int fold_at = xl_fold_at(lane), fold_own = xl_fold_own(m, u);
   // The step's HBM traffic through LDS, issued by waves 1-3 only (as in the forward): wave 0
   // publishes, and its drain may not queue behind HBM loads or stores (vmcnt counts in order).
   // Every wave polls the flags of its own producers; an io wave's poll comes after it staged
@@ -944,16 +997,16 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
       trace_at(s, 2);
     }
     trace_at(s, 3);
+    // acc[c][i]: row 4 (lane >> 4) + i of unit 16 c + (lane & 15); hi + lo folded (xl_fold)
 #pragma unroll
-    for (int c = 0; c < 2; ++c)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        red[(wave * 16 + (lane >> 4) * 4 + i) * RC + 16 * c + (lane & 15)] = acc[c][i];
+    for (int i = 0; i < 4; ++i) red[wave * 256 + fold_at + 32 * i] = xl_fold(acc[0][i], acc[1][i]);
     __syncthreads();
-    if (flag == 0) {
-      xl_poison(cold, s, T, d == 0, d, 3, 3);
-      return;
-    }
+    // one batch of LDS reads; the flag word (cleared, if at all, in front of the barrier above)
+    // rides along and is branched on at the publish barrier, as the forward's failure word
+    const int flag_v = flag;
+    float pr[LW];
+#pragma unroll
+    for (int w4 = 0; w4 < LW; ++w4) pr[w4] = red[w4 * 256 + fold_own];
     const float dyv = pin[m * LU + u], g_r = pin[256 + m * LU + u], g_z = pin[512 + m * LU + u];
     const float g_n = pin[768 + m * LU + u], g_hn = pin[1024 + m * LU + u];
     const float hp = pin[1280 + m * LU + u];
@@ -964,31 +1017,23 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
       if (t < len) {
         float carry = 0.f;
         if (s > 0) {
-          float rec = 0.f;
+          float rec = 0.f;   // (((0 + p0) + p1) + p2) + p3, p = a wave's hi + lo
 #pragma unroll
-          for (int w4 = 0; w4 < LW; ++w4)
-            rec += red[(w4 * 16 + m) * RC + u] + red[(w4 * 16 + m + 8) * RC + u];
+          for (int w4 = 0; w4 < LW; ++w4) rec += pr[w4];
           carry = dh_prev * z_prev + rec * unscale;
         }
         dh = dyv + carry;
         zc = g_z;
-        dan = dh * (1.f - zc) * (1.f - g_n * g_n);
+        // (1 - n^2 as one fma, written out: left to the compiler's contraction the choice
+        // between it and a multiply + subtract follows the surrounding code, and the bits with it)
+        dan = dh * (1.f - zc) * __builtin_fmaf(-g_n, g_n, 1.f);
         daz = dh * (hp - g_n) * zc * (1.f - zc);
         dar = dan * g_hn * g_r * (1.f - g_r);
         dghn = dan * g_r;
       }
       dh_prev = dh;
       z_prev = zc;
-      sb_r += dar; sb_z += daz; sb_n += dan; sb_hn += dghn;
-      cm_r = fmaxf(cm_r, fabsf(dar));
-      cm_z = fmaxf(cm_z, fabsf(daz));
-      cm_n = fmaxf(cm_n, fabsf(dan));
-      cm_hn = fmaxf(cm_hn, fabsf(dghn));
     }
-    pout[m * LU + u] = dar;
-    pout[256 + m * LU + u] = daz;
-    pout[512 + m * LU + u] = dan;
-    pout[768 + m * LU + u] = dghn;
     {
       // the row's scale: max over the sample's 32 units x 3 gates (32 consecutive lanes)
       const float mx = half_wave_max(fmaxf(fmaxf(fabsf(dar), fabsf(daz)), fabsf(dghn)));
@@ -1004,14 +1049,55 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
       stg[1024 + slo] = (_Float16)(vn - (float)hn);
       if (u == 0) stsc[m] = __builtin_ldexpf(1.f, -e);
     }
+    // (the record's fragments first: dgx / dgh are only stored during the next step)
+    pout[m * LU + u] = dar;
+    pout[256 + m * LU + u] = daz;
+    pout[512 + m * LU + u] = dan;
+    pout[768 + m * LU + u] = dghn;
+    // What neither the record nor its flag needs -- the fp64 bias-gradient sums, the column
+    // maxima, the ROWS row maximum -- runs behind the publish barrier: on wave 0 between the
+    // record's stores and their drain, in the shadow of that round trip.
+    auto off_chain = [&]() __attribute__((always_inline)) {
+      if (owner) {
+        sb_r += dar; sb_z += daz; sb_n += dan; sb_hn += dghn;
+        cm_r = fmaxf(cm_r, fabsf(dar));
+        cm_z = fmaxf(cm_z, fabsf(daz));
+        cm_n = fmaxf(cm_n, fabsf(dan));
+        cm_hn = fmaxf(cm_hn, fabsf(dghn));
+      }
+      if (ROWS) {
+        // max over the sample's 32 units x 3 gates of dgx (32 consecutive lanes); 0 where t >= len
+        const float rm = half_wave_max(fmaxf(fmaxf(fabsf(dar), fabsf(daz)), fabsf(dan)));
+        if (u == 0) rowmx[(s & 1) * LB + m] = rm;
+      }
+    };
+    const int so = ((s & 1) * slot_floats + grp_off + ub * LRB) * 4;   // scalar, before the barrier
     __syncthreads();
+    if (flag_v == 0) {   // a wave's flag wait timed out: poison what is left, publish nothing
+      xl_poison(cold, s, T, d == 0, d, 3, 3);
+      return;
+    }
     if (wave == 0) {
-      const int so = ((s & 1) * slot_floats + grp_off + ub * LRB) * 4;
+      // the record out of LDS in one batch, then its stores under one test of `local` (a test
+      // per store made each of the four an LDS round trip of its own: read, wait, store)
+      u32x4 rv[3];
 #pragma unroll
-      for (int k = 0; k < 3; ++k)
-        xl_store(*reinterpret_cast<const u32x4*>(stg + k * 512 + lane * 8), x_rs,
-                 so + k * 1024 + lane * 16, local);
-      if (lane < 2) xl_store(*reinterpret_cast<const u32x4*>(stsc + lane * 4), x_rs, so + 3072 + lane * 16, local);
+      for (int k = 0; k < 3; ++k) rv[k] = *reinterpret_cast<const u32x4*>(stg + k * 512 + lane * 8);
+      const u32x4 sv = *reinterpret_cast<const u32x4*>(stsc + (lane & 1) * 4);
+      if (local) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) xl_store(rv[k], x_rs, lane * 16, so + k * 1024, true);
+        if (lane < 2) xl_store(sv, x_rs, lane * 16, so + 3072, true);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) xl_store(rv[k], x_rs, lane * 16, so + k * 1024, false);
+        if (lane < 2) xl_store(sv, x_rs, lane * 16, so + 3072, false);
+      }
+    } else {
+      trace_at(s, 5);
+    }
+    off_chain();
+    if (wave == 0) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       if (lane == 0) {
         const unsigned fv = (unsigned)s + 1;
@@ -1020,12 +1106,7 @@ __global__ __launch_bounds__(LT) __attribute__((amdgpu_waves_per_eu(1, 1))) void
         else
           __builtin_amdgcn_raw_buffer_store_b32(fv, f_rs, (g * 32 + ub) * 4, 0, kSc1);
       }
-    }
-    trace_at(s, 5);
-    if (ROWS) {
-      // max over the sample's 32 units x 3 gates of dgx (32 consecutive lanes); 0 where t >= len
-      const float rm = half_wave_max(fmaxf(fmaxf(fabsf(dar), fabsf(daz)), fabsf(dan)));
-      if (u == 0) rowmx[(s & 1) * LB + m] = rm;
+      trace_at(s, 5);
     }
   }
   __syncthreads();

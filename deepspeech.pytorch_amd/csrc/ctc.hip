@@ -748,6 +748,28 @@ static unsigned long long* g_beam_stamps = nullptr;
 
 constexpr int LM_MAX_ORDER = 6;
 
+// The search over a stream (ds2_ctc_beam_stream_*): what survives from frame to frame, kept
+// in global memory between launches.  Per stream one record of 32-bit words -- a header
+// {BEAM_STREAM_MAGIC, beam_width, max_frames, entries in the beam, trie nodes in use, frames
+// consumed, 0, 0}, then per-entry arrays of E = beam_width rounded up to 4 entries each: node,
+// last char, pb, pnb, the node's parent, its best char log-prob, the prefix length, the LM's
+// dictionary state and cached word score, and its LM_MAX_ORDER - 1 history words -- followed
+// (after all records) by the trie arena of ds2_ctc_beam_decode's workspace layout, sized for
+// max_frames frames.  The kernel only trusts a record whose header names the beam_width and
+// max_frames it was launched with and whose counters fit the arena.
+constexpr int BEAM_STREAM_MAGIC = 0x42534D31;
+constexpr int BEAM_STREAM_HDR = 8;
+constexpr int BEAM_STREAM_PER_ENTRY = 9 + (LM_MAX_ORDER - 1);
+struct BeamStream {
+  int* rec;            // [n][rec_words]
+  int64_t rec_words;
+  int* out_frames;     // [n] frames consumed so far per stream, or null
+  int max_frames;
+  int out_cap;         // row stride of out_ids / out_ts
+};
+
+__host__ __device__ inline int beam_stream_entries(int beam) { return (beam + 3) & ~3; }
+
 __device__ __forceinline__ unsigned lm_hash(const int* k) {
   unsigned h = 2166136261u;
 #pragma unroll
@@ -946,7 +968,12 @@ __device__ __forceinline__ float wave_min(float v) {
   return v;
 }
 
-template <int BM, int CM, bool LM>
+// STREAM = true is the same search over one chunk of a stream: the beam comes from the
+// stream's record (BeamStream) instead of the root seed, char frames are counted from the
+// frames the stream consumed before, and the beam goes back to the record after the chunk;
+// the ranking and back-tracking run only where the caller passed outputs, and leave the
+// record alone.
+template <int BM, int CM, bool LM, bool STREAM = false>
 __global__ __launch_bounds__(64) void ctc_beam_kernel(
     const float* __restrict__ probs, int t_max, int C, int64_t stride_n, int64_t stride_t,
     const int* __restrict__ sizes, int blank, int beam, int cutoff_top_n, double cutoff_prob,
@@ -954,7 +981,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(
     int* __restrict__ node_ts, float* __restrict__ node_lpc, int* __restrict__ node_cnt,
     int* __restrict__ node_fc, int* __restrict__ node_ns, unsigned long long* __restrict__ node_km,
     int64_t node_cap, int* __restrict__ out_ids, int* __restrict__ out_ts, int* __restrict__ out_lens,
-    float* __restrict__ out_scores, BeamLm L) {
+    float* __restrict__ out_scores, BeamLm L, BeamStream S) {
   constexpr int EPL = (BM + 63) / 64;   // beam entries per lane
   // more candidates than 12 key bits and one wave's registers hold (the wide instantiation)
   constexpr bool WIDE = BM * CM > 4096;
@@ -1033,7 +1060,45 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(
   if (stamps != nullptr && t < BEAM_NSTAMP_T && lane == 0)                  \
     stamps[t * BEAM_NSTAMP_P + (ph)] = __builtin_amdgcn_s_memtime();
 
-  if (lane == 0) {
+  int t0 = 0;   // frames this stream consumed in earlier launches
+  int* rec = nullptr;
+  [[maybe_unused]] int rec_e = 0;
+  [[maybe_unused]] bool rec_ok = false;
+  if constexpr (STREAM) {
+    rec = S.rec + (int64_t)n * S.rec_words;
+    rec_e = beam_stream_entries(beam);
+    const int h_nb = rec[3], h_nodes = rec[4], h_t0 = rec[5];
+    rec_ok = rec[0] == BEAM_STREAM_MAGIC && rec[1] == beam && rec[2] == S.max_frames &&
+             h_nb >= 0 && h_nb <= beam && h_t0 >= 0 && h_t0 <= S.max_frames && h_nodes >= 1 &&
+             (int64_t)h_nodes <= (int64_t)h_t0 * beam + 1 &&
+             (int64_t)S.max_frames * beam + 1 <= node_cap;
+    // every frame adds at most `beam` nodes: within max_frames frames the arena holds them
+    t0 = rec_ok ? h_t0 : 0;
+    size = rec_ok ? min(size, S.max_frames - t0) : 0;
+    const int nb0 = rec_ok ? h_nb : 0;
+    const int* re = rec + BEAM_STREAM_HDR;
+    for (int e = lane; e < nb0; e += 64) {
+      b_node[0][e] = re[e];
+      b_last[0][e] = re[rec_e + e];
+      b_pb[0][e] = __int_as_float(re[2 * rec_e + e]);
+      b_pnb[0][e] = __int_as_float(re[3 * rec_e + e]);
+      b_par[0][e] = re[4 * rec_e + e];
+      b_lpc[0][e] = __int_as_float(re[5 * rec_e + e]);
+      b_len[0][e] = re[6 * rec_e + e];
+      if constexpr (LM) {
+        b_dst[0][e] = re[7 * rec_e + e];
+        b_lms[0][e] = __int_as_float(re[8 * rec_e + e]);
+        // the root's history is "<s>" throughout, whichever LM the stream is fed with (the
+        // initialiser does not know it)
+        for (int h = 0; h < LM_MAX_ORDER - 1; ++h)
+          b_hist[0][e][h] = re[e] == 0 ? L.start : re[9 * rec_e + e * (LM_MAX_ORDER - 1) + h];
+      }
+    }
+    if (lane == 0) {
+      s_nb = nb0;
+      s_nodes = rec_ok ? h_nodes : 1;
+    }
+  } else if (lane == 0) {
     b_node[0][0] = 0; b_last[0][0] = -1; b_pb[0][0] = 0.f; b_pnb[0][0] = -INFINITY;
     b_par[0][0] = -1; b_lpc[0][0] = -INFINITY; b_len[0][0] = 0;
     par[0] = -1; chr[0] = -1; tst[0] = -1; lpcv[0] = -INFINITY;
@@ -1051,6 +1116,14 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(
   unsigned long long km_next[EPL];   // children masks of the beam's entries' nodes (prefetched)
 #pragma unroll
   for (int q = 0; q < EPL; ++q) km_next[q] = 0ull;   // the root starts childless
+  if constexpr (STREAM) {
+#pragma unroll
+    for (int q = 0; q < EPL; ++q) {
+      const int e = lane + 64 * q;
+      if (e < s_nb)
+        km_next[q] = __hip_atomic_load(km + b_node[0][e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
   for (int t = 0; t < size; ++t) {
     const int nb = s_nb;
     if (nb == 0) break;
@@ -1221,7 +1294,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(
               if (lp[last_i] > b_lpc[cur][i]) {
                 b_lpc[cur][i] = lp[last_i];
                 lpcv[nd] = lp[last_i];
-                tst[nd] = t;
+                tst[nd] = t0 + t;
               }
             }
           }
@@ -1317,7 +1390,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(
       const int x = trie_alive_child(fc, ns, chr, cnt, b_node[cur][i], c, node_cap);
       if (x > 0 && lp[c] > lpcv[x]) {
         lpcv[x] = lp[c];
-        tst[x] = t;
+        tst[x] = t0 + t;
       }
     }
     BEAM_STAMP(4)
@@ -1441,7 +1514,7 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(
             const int p = b_node[cur][i];
             par[nd] = p;
             chr[nd] = c;
-            tst[nd] = t;
+            tst[nd] = t0 + t;
             lpcv[nd] = lp[c];
             cnt[nd] = 1;
             fc[nd] = -1;
@@ -1504,8 +1577,37 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(
     cur = nxt;
   }
 #undef BEAM_STAMP
-  // ---- final ranking and back-tracking (one lane per returned path)
   const int nb = s_nb;
+  if constexpr (STREAM) {
+    // the beam goes back to its record (a chunk without valid frames leaves it as it is)
+    if (rec_ok && size > 0) {
+      int* re = rec + BEAM_STREAM_HDR;
+      for (int e = lane; e < nb; e += 64) {
+        re[e] = b_node[cur][e];
+        re[rec_e + e] = b_last[cur][e];
+        re[2 * rec_e + e] = __float_as_int(b_pb[cur][e]);
+        re[3 * rec_e + e] = __float_as_int(b_pnb[cur][e]);
+        re[4 * rec_e + e] = b_par[cur][e];
+        re[5 * rec_e + e] = __float_as_int(b_lpc[cur][e]);
+        re[6 * rec_e + e] = b_len[cur][e];
+        if constexpr (LM) {
+          re[7 * rec_e + e] = b_dst[cur][e];
+          re[8 * rec_e + e] = __float_as_int(b_lms[cur][e]);
+          for (int h = 0; h < LM_MAX_ORDER - 1; ++h)
+            re[9 * rec_e + e * (LM_MAX_ORDER - 1) + h] = b_hist[cur][e][h];
+        }
+      }
+      if (lane == 0) {
+        rec[3] = nb;
+        rec[4] = s_nodes;
+        rec[5] = t0 + size;
+      }
+    }
+    if (lane == 0 && S.out_frames != nullptr) S.out_frames[n] = rec_ok ? t0 + size : -1;
+    if (out_lens == nullptr) return;   // no read-out asked for
+  }
+  // ---- final ranking and back-tracking (one lane per returned path)
+  const int ocap = STREAM ? S.out_cap : t_max;   // row stride of out_ids / out_ts
 #pragma unroll
   for (int q = 0; q < EPL; ++q) {
     const int e = lane + 64 * q;
@@ -1526,11 +1628,12 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(
       if (i != e && beam_better(score[i], (b_last[cur][i] + 1) * 4096 + i, s0, key0)) ++rank;
     if (rank < top_paths) {
       const int len = b_len[cur][e];
-      int* ids = out_ids + ((int64_t)n * top_paths + rank) * t_max;
-      int* tsp = out_ts + ((int64_t)n * top_paths + rank) * t_max;
+      int* ids = out_ids + ((int64_t)n * top_paths + rank) * ocap;
+      int* tsp = out_ts + ((int64_t)n * top_paths + rank) * ocap;
       int pos = len;
       for (int nd = b_node[cur][e]; nd > 0 && pos > 0; nd = par[nd]) {
         --pos;
+        if (STREAM && pos >= ocap) continue;   // a caller whose out_cap understates its feeds
         ids[pos] = chr[nd];
         tsp[pos] = tst[nd];
       }
@@ -1541,6 +1644,38 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(
   for (int r = nb + lane; r < top_paths; r += 64) {   // fewer prefixes than paths asked for
     out_lens[n * top_paths + r] = 0;
     out_scores[n * top_paths + r] = -INFINITY;
+  }
+}
+
+// a stream's record and trie as the whole-utterance kernel seeds them: the root-only beam
+__global__ __launch_bounds__(64) void ctc_beam_stream_init_kernel(
+    int* __restrict__ rec_all, int64_t rec_words, int beam, int max_frames,
+    int* __restrict__ node_parent, int* __restrict__ node_ch, int* __restrict__ node_ts,
+    float* __restrict__ node_lpc, int* __restrict__ node_cnt, int* __restrict__ node_fc,
+    int* __restrict__ node_ns, unsigned long long* __restrict__ node_km, int64_t node_cap) {
+  const int n = blockIdx.x;
+  const int lane = threadIdx.x;
+  int* rec = rec_all + (int64_t)n * rec_words;
+  for (int64_t i = lane; i < rec_words; i += 64) rec[i] = 0;
+  __syncthreads();
+  if (lane == 0) {
+    const int E = beam_stream_entries(beam);
+    int* re = rec + BEAM_STREAM_HDR;
+    rec[0] = BEAM_STREAM_MAGIC; rec[1] = beam; rec[2] = max_frames;
+    rec[3] = 1; rec[4] = 1; rec[5] = 0;
+    re[0] = 0;                                       // node: the root
+    re[E] = -1;                                      // last char
+    re[2 * E] = __float_as_int(0.f);                 // pb
+    re[3 * E] = __float_as_int(-INFINITY);           // pnb
+    re[4 * E] = -1;                                  // parent
+    re[5 * E] = __float_as_int(-INFINITY);           // best char log-prob
+    re[6 * E] = 0;                                   // length
+    re[7 * E] = 0;                                   // dictionary state: the start
+    re[8 * E] = __float_as_int(0.f);                 // cached word score
+    // the root's history ("<s>" throughout) is the LM's: the feed kernel supplies it on load
+    const int64_t o = (int64_t)n * node_cap;
+    node_parent[o] = -1; node_ch[o] = -1; node_ts[o] = -1; node_lpc[o] = -INFINITY;
+    node_cnt[o] = 1; node_fc[o] = -1; node_ns[o] = -1; node_km[o] = 0ull;
   }
 }
 
@@ -1860,6 +1995,31 @@ size_t ds2_ctc_beam_workspace_size(int n, int t_max, int beam) {
   return 7 * al256((size_t)n * cap * 4) + al256((size_t)n * cap * 8) + 256;
 }
 
+// the trie arena of n utterances of up to t_max frames inside a workspace of that size
+struct BeamArena {
+  int *par, *chr, *tst;
+  float* lpc;
+  int *cnt, *fc, *ns;
+  unsigned long long* km;
+  int64_t cap;   // nodes per utterance
+};
+
+static BeamArena beam_arena(void* ws, int n, int t_max, int beam_width) {
+  BeamArena a;
+  a.cap = (int64_t)t_max * beam_width + 1;
+  char* w = static_cast<char*>(ws);
+  const size_t plane = al256((size_t)n * a.cap * 4);
+  a.par = reinterpret_cast<int*>(w);
+  a.chr = reinterpret_cast<int*>(w + plane);
+  a.tst = reinterpret_cast<int*>(w + 2 * plane);
+  a.lpc = reinterpret_cast<float*>(w + 3 * plane);
+  a.cnt = reinterpret_cast<int*>(w + 4 * plane);
+  a.fc = reinterpret_cast<int*>(w + 5 * plane);
+  a.ns = reinterpret_cast<int*>(w + 6 * plane);
+  a.km = reinterpret_cast<unsigned long long*>(w + 7 * plane);
+  return a;
+}
+
 static ds2_status_t beam_decode(const float* probs, int n, int t_max, int c, int64_t stride_n,
                                 int64_t stride_t, const int* sizes, int blank, int beam_width,
                                 int cutoff_top_n, double cutoff_prob, int top_paths,
@@ -1876,17 +2036,7 @@ static ds2_status_t beam_decode(const float* probs, int n, int t_max, int c, int
   if (n == 0) return DS2_OK;
   if (ws == nullptr || ws_bytes < ds2_ctc_beam_workspace_size(n, t_max, beam_width))
     return DS2_WORKSPACE_TOO_SMALL;
-  const int64_t cap = (int64_t)t_max * beam_width + 1;
-  char* w = static_cast<char*>(ws);
-  const size_t plane = al256((size_t)n * cap * 4);
-  int* par = reinterpret_cast<int*>(w);
-  int* chr = reinterpret_cast<int*>(w + plane);
-  int* tst = reinterpret_cast<int*>(w + 2 * plane);
-  float* lpc = reinterpret_cast<float*>(w + 3 * plane);
-  int* ncnt = reinterpret_cast<int*>(w + 4 * plane);
-  int* nfc = reinterpret_cast<int*>(w + 5 * plane);
-  int* nns = reinterpret_cast<int*>(w + 6 * plane);
-  auto* nkm = reinterpret_cast<unsigned long long*>(w + 7 * plane);
+  const BeamArena a = beam_arena(ws, n, t_max, beam_width);
   BeamLm L{};
   if (lm != nullptr) L = *lm;
   L.stamps = g_beam_stamps;
@@ -1899,9 +2049,106 @@ static ds2_status_t beam_decode(const float* probs, int n, int t_max, int c, int
                              : ctc_beam_kernel<BEAM_WIDE, BEAM_WIDE_C, false>);
   hipLaunchKernelGGL(kern, dim3(n), dim3(64), 0, as_stream(stream), probs, t_max, c,
                      stride_n, stride_t, sizes, blank, beam_width, cutoff_top_n, cutoff_prob,
-                     top_paths, par, chr, tst, lpc, ncnt, nfc, nns, nkm, cap, out_ids, out_offsets, out_lens,
-                     out_scores, L);
+                     top_paths, a.par, a.chr, a.tst, a.lpc, a.cnt, a.fc, a.ns, a.km, a.cap, out_ids,
+                     out_offsets, out_lens, out_scores, L, BeamStream{});
   return launch_status(what);
+}
+
+// ---- the search over a stream: [n records][trie arena for max_frames frames]
+static inline size_t beam_stream_rec_words(int beam_width) {
+  return BEAM_STREAM_HDR + (size_t)BEAM_STREAM_PER_ENTRY * beam_stream_entries(beam_width);
+}
+
+static inline bool beam_stream_dims_ok(int n, int max_frames, int beam_width) {
+  return n >= 1 && max_frames >= 1 && beam_width >= 1 && beam_width <= BEAM_WIDE &&
+         (int64_t)max_frames * beam_width + 1 <= INT32_MAX;   // node indices are ints
+}
+
+size_t ds2_ctc_beam_stream_state_size(int n, int max_frames, int beam_width) {
+  if (!beam_stream_dims_ok(n, max_frames, beam_width)) return 0;
+  return al256((size_t)n * beam_stream_rec_words(beam_width) * 4) +
+         ds2_ctc_beam_workspace_size(n, max_frames, beam_width);
+}
+
+ds2_status_t ds2_ctc_beam_stream_init(void* state, size_t state_bytes, int n, int max_frames,
+                                      int beam_width, ds2_stream_t stream) {
+  if (!beam_stream_dims_ok(n, max_frames, beam_width) || state == nullptr ||
+      (reinterpret_cast<uintptr_t>(state) & 255) != 0 ||
+      state_bytes < ds2_ctc_beam_stream_state_size(n, max_frames, beam_width))
+    return DS2_INVALID_VALUE;
+  const size_t rw = beam_stream_rec_words(beam_width);
+  const BeamArena a = beam_arena(static_cast<char*>(state) + al256((size_t)n * rw * 4), n,
+                                 max_frames, beam_width);
+  hipLaunchKernelGGL(ctc_beam_stream_init_kernel, dim3(n), dim3(64), 0, as_stream(stream),
+                     static_cast<int*>(state), (int64_t)rw, beam_width, max_frames, a.par, a.chr,
+                     a.tst, a.lpc, a.cnt, a.fc, a.ns, a.km, a.cap);
+  return launch_status("ds2_ctc_beam_stream_init");
+}
+
+static ds2_status_t beam_stream_feed(const float* probs, int n, int t_chunk, int c,
+                                     int64_t stride_n, int64_t stride_t, const int* sizes,
+                                     int blank, int beam_width, int cutoff_top_n,
+                                     double cutoff_prob, int top_paths, int max_frames,
+                                     int t_done, int out_cap, int* out_ids, int* out_offsets,
+                                     int* out_lens, float* out_scores, int* out_frames,
+                                     void* state, size_t state_bytes, const BeamLm* lm,
+                                     ds2_stream_t stream, const char* what) {
+  if (n < 0 || t_chunk < 0 || c < 1 || blank < 0 || blank >= c || beam_width < 1 ||
+      top_paths < 1 || top_paths > beam_width || cutoff_top_n < 1 || max_frames < 1 ||
+      t_done < 0)
+    return DS2_INVALID_VALUE;
+  const bool small = c <= BEAM_SMALL_C && beam_width <= BEAM_SMALL;
+  const bool large = !small && c <= BEAM_LARGE_C && beam_width <= BEAM_LARGE;
+  if (!small && !large && (c > BEAM_WIDE_C || beam_width > BEAM_WIDE))
+    return DS2_UNSUPPORTED_SHAPE;
+  const int n_out = (out_ids != nullptr) + (out_offsets != nullptr) + (out_lens != nullptr) +
+                    (out_scores != nullptr);
+  if (n_out != 0 && n_out != 4) return DS2_INVALID_VALUE;
+  const bool readout = n_out == 4;
+  if ((int64_t)t_done + t_chunk > max_frames) return DS2_INVALID_VALUE;
+  if (readout && out_cap < t_done + t_chunk) return DS2_INVALID_VALUE;
+  if (n == 0 || (t_chunk == 0 && !readout)) return DS2_OK;
+  if (!beam_stream_dims_ok(n, max_frames, beam_width) || state == nullptr ||
+      (reinterpret_cast<uintptr_t>(state) & 255) != 0 ||
+      state_bytes < ds2_ctc_beam_stream_state_size(n, max_frames, beam_width))
+    return DS2_INVALID_VALUE;
+  if (t_chunk > 0 && probs == nullptr) return DS2_INVALID_VALUE;
+  BeamStream S;
+  S.rec = static_cast<int*>(state);
+  S.rec_words = (int64_t)beam_stream_rec_words(beam_width);
+  S.out_frames = out_frames;
+  S.max_frames = max_frames;
+  S.out_cap = out_cap;
+  const BeamArena a = beam_arena(static_cast<char*>(state) + al256((size_t)n * S.rec_words * 4),
+                                 n, max_frames, beam_width);
+  BeamLm L{};
+  if (lm != nullptr) L = *lm;
+  L.stamps = nullptr;
+  auto kern = lm != nullptr
+                  ? (small   ? ctc_beam_kernel<BEAM_SMALL, BEAM_SMALL_C, true, true>
+                     : large ? ctc_beam_kernel<BEAM_LARGE, BEAM_LARGE_C, true, true>
+                             : ctc_beam_kernel<BEAM_WIDE, BEAM_WIDE_C, true, true>)
+                  : (small   ? ctc_beam_kernel<BEAM_SMALL, BEAM_SMALL_C, false, true>
+                     : large ? ctc_beam_kernel<BEAM_LARGE, BEAM_LARGE_C, false, true>
+                             : ctc_beam_kernel<BEAM_WIDE, BEAM_WIDE_C, false, true>);
+  hipLaunchKernelGGL(kern, dim3(n), dim3(64), 0, as_stream(stream), probs, t_chunk, c,
+                     stride_n, stride_t, sizes, blank, beam_width, cutoff_top_n, cutoff_prob,
+                     top_paths, a.par, a.chr, a.tst, a.lpc, a.cnt, a.fc, a.ns, a.km, a.cap, out_ids,
+                     out_offsets, out_lens, out_scores, L, S);
+  return launch_status(what);
+}
+
+ds2_status_t ds2_ctc_beam_stream_feed(const float* probs, int n, int t_chunk, int c,
+                                      int64_t stride_n, int64_t stride_t, const int* sizes,
+                                      int blank, int beam_width, int cutoff_top_n,
+                                      double cutoff_prob, int top_paths, int max_frames,
+                                      int t_done, int out_cap, int* out_ids, int* out_offsets,
+                                      int* out_lens, float* out_scores, int* out_frames,
+                                      void* state, size_t state_bytes, ds2_stream_t stream) {
+  return beam_stream_feed(probs, n, t_chunk, c, stride_n, stride_t, sizes, blank, beam_width,
+                          cutoff_top_n, cutoff_prob, top_paths, max_frames, t_done, out_cap,
+                          out_ids, out_offsets, out_lens, out_scores, out_frames, state,
+                          state_bytes, nullptr, stream, "ds2_ctc_beam_stream_feed");
 }
 
 ds2_status_t ds2_ctc_beam_decode(const float* probs, int n, int t_max, int c, int64_t stride_n,
@@ -1915,23 +2162,17 @@ ds2_status_t ds2_ctc_beam_decode(const float* probs, int n, int t_max, int c, in
                      out_scores, ws, ws_bytes, nullptr, stream, "ds2_ctc_beam_decode");
 }
 
-ds2_status_t ds2_ctc_beam_decode_lm(const float* probs, int n, int t_max, int c, int64_t stride_n,
-                                    int64_t stride_t, const int* sizes, int blank, int beam_width,
-                                    int cutoff_top_n, double cutoff_prob, int top_paths,
-                                    int space_id, int lm_order, int start_id, int lm_vocab,
-                                    double alpha, double beta, const int* dict_next,
-                                    const void* dict_mask, const int* dict_word, int dict_states,
-                                    int dict_cols, const int* lm_table, int64_t lm_slots,
-                                    int* out_ids, int* out_offsets, int* out_lens,
-                                    float* out_scores, void* ws, size_t ws_bytes,
-                                    ds2_stream_t stream) {
+// the LM arguments of the _lm entry points, checked and gathered; false = DS2_INVALID_VALUE
+static bool beam_lm_args(int c, int blank, int space_id, int lm_order, int start_id, int lm_vocab,
+                         double alpha, double beta, const int* dict_next, const void* dict_mask,
+                         const int* dict_word, int dict_states, int dict_cols,
+                         const int* lm_table, int64_t lm_slots, BeamLm& L) {
   if (space_id < 0 || space_id >= c || space_id == blank || lm_order < 1 ||
       lm_order > LM_MAX_ORDER || start_id < 0 || start_id >= lm_vocab || dict_states < 2 ||
       dict_cols != c || dict_next == nullptr ||
       dict_mask == nullptr || dict_word == nullptr || lm_table == nullptr || lm_slots < 1 ||
       (lm_slots & (lm_slots - 1)) != 0 || lm_slots > (int64_t(1) << 31) || c > 64)
-    return DS2_INVALID_VALUE;
-  BeamLm L;
+    return false;
   L.dnext = dict_next;
   L.dmask = static_cast<const unsigned long long*>(dict_mask);
   L.dword = dict_word;
@@ -1944,9 +2185,48 @@ ds2_status_t ds2_ctc_beam_decode_lm(const float* probs, int n, int t_max, int c,
   L.space = space_id;
   L.alpha = alpha;
   L.beta = beta;
+  L.stamps = nullptr;
+  return true;
+}
+
+ds2_status_t ds2_ctc_beam_decode_lm(const float* probs, int n, int t_max, int c, int64_t stride_n,
+                                    int64_t stride_t, const int* sizes, int blank, int beam_width,
+                                    int cutoff_top_n, double cutoff_prob, int top_paths,
+                                    int space_id, int lm_order, int start_id, int lm_vocab,
+                                    double alpha, double beta, const int* dict_next,
+                                    const void* dict_mask, const int* dict_word, int dict_states,
+                                    int dict_cols, const int* lm_table, int64_t lm_slots,
+                                    int* out_ids, int* out_offsets, int* out_lens,
+                                    float* out_scores, void* ws, size_t ws_bytes,
+                                    ds2_stream_t stream) {
+  BeamLm L;
+  if (!beam_lm_args(c, blank, space_id, lm_order, start_id, lm_vocab, alpha, beta, dict_next,
+                    dict_mask, dict_word, dict_states, dict_cols, lm_table, lm_slots, L))
+    return DS2_INVALID_VALUE;
   return beam_decode(probs, n, t_max, c, stride_n, stride_t, sizes, blank, beam_width,
                      cutoff_top_n, cutoff_prob, top_paths, out_ids, out_offsets, out_lens,
                      out_scores, ws, ws_bytes, &L, stream, "ds2_ctc_beam_decode_lm");
+}
+
+ds2_status_t ds2_ctc_beam_stream_feed_lm(const float* probs, int n, int t_chunk, int c,
+                                         int64_t stride_n, int64_t stride_t, const int* sizes,
+                                         int blank, int beam_width, int cutoff_top_n,
+                                         double cutoff_prob, int top_paths, int space_id,
+                                         int lm_order, int start_id, int lm_vocab, double alpha,
+                                         double beta, const int* dict_next, const void* dict_mask,
+                                         const int* dict_word, int dict_states, int dict_cols,
+                                         const int* lm_table, int64_t lm_slots, int max_frames,
+                                         int t_done, int out_cap, int* out_ids, int* out_offsets,
+                                         int* out_lens, float* out_scores, int* out_frames,
+                                         void* state, size_t state_bytes, ds2_stream_t stream) {
+  BeamLm L;
+  if (!beam_lm_args(c, blank, space_id, lm_order, start_id, lm_vocab, alpha, beta, dict_next,
+                    dict_mask, dict_word, dict_states, dict_cols, lm_table, lm_slots, L))
+    return DS2_INVALID_VALUE;
+  return beam_stream_feed(probs, n, t_chunk, c, stride_n, stride_t, sizes, blank, beam_width,
+                          cutoff_top_n, cutoff_prob, top_paths, max_frames, t_done, out_cap,
+                          out_ids, out_offsets, out_lens, out_scores, out_frames, state,
+                          state_bytes, &L, stream, "ds2_ctc_beam_stream_feed_lm");
 }
 
 ds2_status_t ds2_test_beam_stamps(unsigned long long* buf) {

@@ -177,6 +177,17 @@ _PROTOS = {
                                         _c_int, _c_int, ctypes.c_double, ctypes.c_double, _vp, _vp,
                                         _vp, _c_int, _c_int, _vp, _c_i64, _vp, _vp, _vp, _vp, _vp,
                                         _sz, _vp]),
+    "ds2_ctc_beam_stream_state_size": (_sz, [_c_int, _c_int, _c_int]),
+    "ds2_ctc_beam_stream_init": (_c_int, [_vp, _sz, _c_int, _c_int, _c_int, _vp]),
+    "ds2_ctc_beam_stream_feed": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_i64, _c_i64, _vp, _c_int,
+                                          _c_int, _c_int, ctypes.c_double, _c_int, _c_int, _c_int,
+                                          _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ds2_ctc_beam_stream_feed_lm": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_i64, _c_i64, _vp,
+                                             _c_int, _c_int, _c_int, ctypes.c_double, _c_int,
+                                             _c_int, _c_int, _c_int, _c_int, ctypes.c_double,
+                                             ctypes.c_double, _vp, _vp, _vp, _c_int, _c_int, _vp,
+                                             _c_i64, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp,
+                                             _vp, _vp, _sz, _vp]),
     "ds2_comm_id_bytes": (_sz, []),
     "ds2_comm_get_unique_id": (_c_int, [_vp]),
     "ds2_comm_init": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int]),

@@ -153,6 +153,113 @@ class BeamCTCDecoder(Decoder):
         return strings, offsets
 
 
+class StreamingBeamCTCDecoder(BeamCTCDecoder):
+    """BeamCTCDecoder over probabilities that arrive in chunks (ds2amd.streaming): the beam,
+    its LM state and its prefix trie stay on the device between calls
+    (ds2_ctc_beam_stream_feed[_lm]), so a feed costs its own frames only, and after the last
+    chunk the result is ``BeamCTCDecoder.decode`` of the concatenated frames, whatever the
+    partition.
+
+    ``feed(probs [N, k, C], sizes=None, partial=True) -> (strings, offsets)``: the current
+    ``top_paths`` best hypotheses of every stream *in full* (not a delta: the beam may revise
+    earlier characters), strings[n][p] / offsets[n][p] best first, offsets in absolute output
+    frames; ``sizes`` (int [N]) are this chunk's valid frames per stream, k == 0 is allowed,
+    and ``partial=False`` skips the read-out and returns None.  ``finish()`` returns every beam
+    in ``decode``'s format, ``text()`` the best string per stream, ``reset()`` starts new
+    utterances in the same buffers.  The stream count is fixed by the first ``feed``.
+
+    ``max_frames`` bounds the output frames of one utterance (3000: 60 s of audio); the trie
+    is allocated once for it, 36 bytes x max_frames x beam_width per stream (10.8 MB at the
+    default beam of 100).  Feeding past it raises ValueError."""
+
+    def __init__(self, labels, lm_path=None, alpha=0, beta=0, cutoff_top_n=40, cutoff_prob=1.0,
+                 beam_width=100, num_processes=4, blank_index=0, max_frames=3000, top_paths=1):
+        super().__init__(labels, lm_path=lm_path, alpha=alpha, beta=beta,
+                         cutoff_top_n=cutoff_top_n, cutoff_prob=cutoff_prob,
+                         beam_width=beam_width, num_processes=num_processes,
+                         blank_index=blank_index)
+        if self.beam_width < 1 or max_frames < 1 or max_frames * self.beam_width >= 2 ** 31 - 1:
+            raise ValueError("ds2amd.StreamingBeamCTCDecoder: beam_width >= 1 and "
+                             "1 <= max_frames, max_frames * beam_width < 2^31 - 1 "
+                             f"(got beam_width={beam_width}, max_frames={max_frames})")
+        if not 1 <= top_paths <= self.beam_width:
+            raise ValueError("ds2amd.StreamingBeamCTCDecoder: 1 <= top_paths <= beam_width "
+                             f"(got top_paths={top_paths}, beam_width={beam_width})")
+        self.max_frames = int(max_frames)
+        self.top_paths = int(top_paths)
+        self.frames_fed = 0         # the host's count: frames given to feed() so far
+        self._state = None
+        self._n = None
+        self._dev = None
+
+    def _feed_raw(self, probs, sizes, top_paths, readout):
+        kw = dict(readout=readout, blank=self.blank_index, cutoff_top_n=self.cutoff_top_n,
+                  cutoff_prob=self.cutoff_prob)
+        if self.scorer is not None:
+            return ops.ctc_beam_stream_feed_lm_raw(self._state, probs, sizes, self.beam_width,
+                                                   top_paths, self.scorer, self.max_frames,
+                                                   self.frames_fed, **kw)
+        return ops.ctc_beam_stream_feed_raw(self._state, probs, sizes, self.beam_width, top_paths,
+                                            self.max_frames, self.frames_fed, **kw)
+
+    def _strings(self, raw):
+        ids, offs, lens = (x.cpu().numpy() for x in raw[:3])
+        return (self.convert_to_strings(ids, lens),
+                self.convert_tensor(torch.from_numpy(offs), lens))
+
+    def feed_raw(self, probs, sizes=None, partial=True):
+        """``feed`` in device tensors: (ids [N,P,F], offsets [N,P,F], lens [N,P], scores [N,P],
+        frames [N]) with P = top_paths and F = the frames fed so far; the first four are None
+        with partial=False.  No synchronisation."""
+        if probs.dim() != 3 or probs.shape[2] != len(self.labels):
+            raise ValueError(f"probs must be [N, k, {len(self.labels)}], got {tuple(probs.shape)}")
+        n, k = int(probs.shape[0]), int(probs.shape[1])
+        if self._n is not None and n != self._n:
+            raise ValueError(f"StreamingBeamCTCDecoder: {self._n} streams since the first feed, "
+                             f"got {n}")
+        if self.frames_fed + k > self.max_frames:
+            raise ValueError(f"StreamingBeamCTCDecoder: {self.frames_fed} + {k} frames exceed "
+                             f"max_frames={self.max_frames}")
+        if not probs.is_cuda:
+            raise RuntimeError("ds2amd StreamingBeamCTCDecoder.feed runs on the GPU (HIP kernel)")
+        if n < 1:
+            raise ValueError("StreamingBeamCTCDecoder: at least one stream")
+        if self._state is None:
+            self._n, self._dev = n, probs.device
+            self._state = ops.ctc_beam_stream_state(n, self.max_frames, self.beam_width,
+                                                    probs.device)
+        out = self._feed_raw(probs.detach(), sizes, self.top_paths, partial)
+        self.frames_fed += k
+        return out
+
+    def feed(self, probs, sizes=None, partial=True):
+        raw = self.feed_raw(probs, sizes, partial)
+        return self._strings(raw) if partial else None
+
+    def _read(self, top_paths):
+        if self._state is None:
+            raise RuntimeError("StreamingBeamCTCDecoder: nothing fed yet (the first feed fixes "
+                               "the stream count and the device)")
+        empty = torch.empty(self._n, 0, len(self.labels), device=self._dev, dtype=torch.float32)
+        return self._strings(self._feed_raw(empty, None, top_paths, True))
+
+    def finish(self):
+        """(strings, offsets) of every beam, best first: what ``BeamCTCDecoder.decode`` returns
+        for the frames fed.  The state is left as it is (more frames may follow)."""
+        return self._read(self.beam_width)
+
+    def text(self):
+        """Per stream, the best string so far."""
+        return [s[0] for s in self._read(1)[0]]
+
+    def reset(self):
+        """Every stream back at the start of an utterance, in the same buffers."""
+        self.frames_fed = 0
+        if self._state is not None:
+            ops.ctc_beam_stream_state(self._n, self.max_frames, self.beam_width, self._dev,
+                                      out=self._state)
+
+
 class GreedyDecoder(Decoder):
     def __init__(self, labels, blank_index=0):
         super().__init__(labels, blank_index)

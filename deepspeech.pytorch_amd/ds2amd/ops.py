@@ -824,6 +824,96 @@ def ctc_beam_decode_lm_raw(probs: torch.Tensor, sizes: Optional[torch.Tensor], b
     return ids, offs, lens, scores
 
 
+def ctc_beam_stream_state(n: int, max_frames: int, beam_width: int, device,
+                          out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The carried state of a beam search over n streams of up to max_frames output frames
+    (ds2_ctc_beam_stream_init): an opaque uint8 device buffer, every stream at the start of an
+    utterance.  ``out``: a buffer this function returned for the same arguments, reset in
+    place."""
+    nbytes = _lib.size("ds2_ctc_beam_stream_state_size", int(n), int(max_frames), int(beam_width))
+    if nbytes == 0:
+        raise _lib.Ds2Error("ctc_beam_stream_state: n >= 1, max_frames >= 1 and "
+                            f"1 <= beam_width <= 128 (got {n}, {max_frames}, {beam_width})")
+    state = torch.empty(nbytes, dtype=torch.uint8, device=device) if out is None else out
+    if not state.is_cuda or state.dtype != torch.uint8 or state.numel() < nbytes:
+        raise _lib.Ds2Error("ctc_beam_stream_state: out is not a state buffer of this size")
+    _lib.call("ds2_ctc_beam_stream_init", state.data_ptr(), state.numel(), int(n),
+              int(max_frames), int(beam_width), _stream())
+    return state
+
+
+def _beam_stream_outputs(n, top_paths, out_cap, dev, readout):
+    frames = torch.empty(n, device=dev, dtype=_I32)
+    if not readout:
+        return None, None, None, None, frames
+    return (torch.empty(n, top_paths, out_cap, device=dev, dtype=_I32),
+            torch.empty(n, top_paths, out_cap, device=dev, dtype=_I32),
+            torch.empty(n, top_paths, device=dev, dtype=_I32),
+            torch.empty(n, top_paths, device=dev, dtype=_F32), frames)
+
+
+def ctc_beam_stream_feed_raw(state: torch.Tensor, probs: torch.Tensor,
+                             sizes: Optional[torch.Tensor], beam_width: int, top_paths: int,
+                             max_frames: int, t_done: int, readout: bool = True, blank: int = 0,
+                             cutoff_top_n: int = 40, cutoff_prob: float = 1.0):
+    """One chunk of a beam search over a stream (no LM).  probs [N,k,C] fp32 (any strides,
+    k >= 0): the next k frames of the N streams of ``state`` (ctc_beam_stream_state); sizes
+    (int32 [N] or None) the valid ones per stream; t_done the frames fed by earlier calls.
+
+    Returns (ids [N,P,max(t_done+k,1)] int32, offsets, lens [N,P] int32, scores [N,P] fp32, frames
+    [N] int32): the current paths in full, best first, as ctc_beam_decode_raw returns them
+    for the frames fed so far, and the frames each stream has consumed; with readout=False
+    the first four are None and nothing is ranked.  Nothing synchronises."""
+    if not probs.is_cuda or probs.dtype != _F32:
+        raise _lib.Ds2Error("ctc_beam_stream_feed: expected a float32 device tensor")
+    n, k, c = probs.shape
+    if probs.stride(2) != 1:
+        probs = probs.contiguous()
+    dev = probs.device
+    cap = max(int(t_done) + k, 1)   # a row stride; an empty tensor has no pointer to pass
+    ids, offs, lens, scores, frames = _beam_stream_outputs(n, top_paths, cap, dev, readout)
+    if sizes is not None:
+        sizes = sizes.to(device=dev, dtype=_I32).contiguous()
+    _lib.call("ds2_ctc_beam_stream_feed", probs.data_ptr(), n, k, c, probs.stride(0),
+              probs.stride(1), _p(sizes), int(blank), int(beam_width), int(cutoff_top_n),
+              float(cutoff_prob), int(top_paths), int(max_frames), int(t_done), cap, _p(ids),
+              _p(offs), _p(lens), _p(scores), frames.data_ptr(), state.data_ptr(), state.numel(),
+              _stream())
+    return ids, offs, lens, scores, frames
+
+
+def ctc_beam_stream_feed_lm_raw(state: torch.Tensor, probs: torch.Tensor,
+                                sizes: Optional[torch.Tensor], beam_width: int, top_paths: int,
+                                scorer, max_frames: int, t_done: int, readout: bool = True,
+                                blank: int = 0, cutoff_top_n: int = 40, cutoff_prob: float = 1.0):
+    """ctc_beam_stream_feed_raw with a word n-gram LM (scorer: ds2amd.lm.ArpaScorer, the same
+    one for every chunk of an utterance).  The scores read out include the last partial word;
+    the carried state does not."""
+    if not probs.is_cuda or probs.dtype != _F32:
+        raise _lib.Ds2Error("ctc_beam_stream_feed_lm: expected a float32 device tensor")
+    n, k, c = probs.shape
+    if probs.stride(2) != 1:
+        probs = probs.contiguous()
+    dev = probs.device
+    if scorer.table.device != dev:
+        raise _lib.Ds2Error("ctc_beam_stream_feed_lm: the LM tables live on another device")
+    if scorer.dict_next.shape[1] != c:
+        raise _lib.Ds2Error("ctc_beam_stream_feed_lm: the LM was built for another label set")
+    cap = max(int(t_done) + k, 1)   # a row stride; an empty tensor has no pointer to pass
+    ids, offs, lens, scores, frames = _beam_stream_outputs(n, top_paths, cap, dev, readout)
+    if sizes is not None:
+        sizes = sizes.to(device=dev, dtype=_I32).contiguous()
+    _lib.call("ds2_ctc_beam_stream_feed_lm", probs.data_ptr(), n, k, c, probs.stride(0),
+              probs.stride(1), _p(sizes), int(blank), int(beam_width), int(cutoff_top_n),
+              float(cutoff_prob), int(top_paths), scorer.space, scorer.order, scorer.start_id,
+              len(scorer.vocab), scorer.alpha, scorer.beta, scorer.dict_next.data_ptr(),
+              scorer.dict_mask.data_ptr(), scorer.dict_word.data_ptr(), scorer.n_states,
+              int(scorer.dict_next.shape[1]), scorer.table.data_ptr(), scorer.table_mask + 1,
+              int(max_frames), int(t_done), cap, _p(ids), _p(offs), _p(lens), _p(scores),
+              frames.data_ptr(), state.data_ptr(), state.numel(), _stream())
+    return ids, offs, lens, scores, frames
+
+
 def wave_aug(pcm: torch.Tensor, in_lens: torch.Tensor, op_i: torch.Tensor, op_f: torch.Tensor,
              noise: Optional[torch.Tensor], out_lens, out_stride: int, cap: int,
              check: bool = True) -> torch.Tensor:

@@ -24,8 +24,11 @@ sizes on the host, so ``feed`` never synchronises):
 Hence output frame j is final once input frame 2 (j + context) + 15 has arrived: 55 input
 frames (0.55 s at the 10 ms stride) of algorithmic latency at the default context of 20.
 
+The probabilities go to ds2amd.decoder.StreamingGreedyDecoder or, for the prefix beam search
+with the n-gram LM, to ds2amd.decoder.StreamingBeamCTCDecoder, chunk by chunk.
+
 Out of scope: a streaming STFT (the session takes normalised frames; per-utterance mean / std
-normalisation needs the whole utterance) and beam search over a stream.
+normalisation needs the whole utterance).
 """
 from __future__ import annotations
 

@@ -672,6 +672,59 @@ ds2_status_t ds2_ctc_beam_decode_lm(const float* probs, int n, int t_max, int c,
                                     float* out_scores, void* ws, size_t ws_bytes,
                                     ds2_stream_t stream);
 
+/* The same two searches over a stream: probabilities arrive in chunks and the beam is
+ * carried between calls, so a feed costs its own frames only and the result after the last
+ * chunk is the whole-utterance search's, whatever the partition (same kernel, one more
+ * template parameter).
+ * State: one opaque device buffer of ds2_ctc_beam_stream_state_size(n, max_frames,
+ * beam_width) bytes, 256-byte aligned, owned by the caller: per stream the beam (entries,
+ * scores, LM dictionary state and history) and its prefix trie, sized once for max_frames
+ * frames (36 bytes per node, max_frames * beam_width + 1 nodes per stream).  The size is 0
+ * for arguments no state exists for (n, max_frames or beam_width < 1, beam_width > 128).
+ * ds2_ctc_beam_stream_init resets all n streams to the empty prefix (start of an utterance).
+ * ds2_ctc_beam_stream_feed[_lm]: the arguments of ds2_ctc_beam_decode[_lm] with t_chunk =
+ * this chunk's frame count (>= 0), then
+ *   sizes       device int32 [n]: this chunk's valid frames per stream (clamped to
+ *               [0, t_chunk]; NULL = all); a stream with 0 valid frames keeps its state as
+ *               it is, bit for bit
+ *   max_frames, beam_width: as given to the size query and to init (a record initialised
+ *               for other values is not advanced and reports -1 in out_frames)
+ *   t_done      frames fed by earlier calls since init (the caller's count: no call
+ *               synchronises); t_done + t_chunk > max_frames is DS2_INVALID_VALUE, and no
+ *               stream consumes a frame past max_frames whatever t_done says
+ *   out_ids / out_offsets [n][top_paths][out_cap], out_lens / out_scores [n][top_paths]:
+ *               the current top_paths prefixes of every stream in full, offsets counted
+ *               from the stream's first frame; with the LM the scores include the last
+ *               partial word, which the carried state does not.  All four NULL: no read-out
+ *               (any other mix is DS2_INVALID_VALUE); out_cap >= t_done + t_chunk
+ *   out_frames  device int32 [n] or NULL: frames each stream has consumed so far
+ * beam_width, c limits and DS2_UNSUPPORTED_SHAPE as for ds2_ctc_beam_decode.
+ * DS2_INVALID_VALUE, before anything is launched, also for a NULL or misaligned state and a
+ * state_bytes below the size query.  n == 0, or t_chunk == 0 without read-out, is DS2_OK and
+ * launches nothing.  A stream whose beam emptied stays empty.  Feeds of one state must be
+ * ordered (one stream, or events); the LM and cutoffs must not change within an utterance. */
+size_t ds2_ctc_beam_stream_state_size(int n, int max_frames, int beam_width);
+ds2_status_t ds2_ctc_beam_stream_init(void* state, size_t state_bytes, int n, int max_frames,
+                                      int beam_width, ds2_stream_t stream);
+ds2_status_t ds2_ctc_beam_stream_feed(const float* probs, int n, int t_chunk, int c,
+                                      int64_t stride_n, int64_t stride_t, const int* sizes,
+                                      int blank, int beam_width, int cutoff_top_n,
+                                      double cutoff_prob, int top_paths, int max_frames,
+                                      int t_done, int out_cap, int* out_ids, int* out_offsets,
+                                      int* out_lens, float* out_scores, int* out_frames,
+                                      void* state, size_t state_bytes, ds2_stream_t stream);
+ds2_status_t ds2_ctc_beam_stream_feed_lm(const float* probs, int n, int t_chunk, int c,
+                                         int64_t stride_n, int64_t stride_t, const int* sizes,
+                                         int blank, int beam_width, int cutoff_top_n,
+                                         double cutoff_prob, int top_paths, int space_id,
+                                         int lm_order, int start_id, int lm_vocab, double alpha,
+                                         double beta, const int* dict_next, const void* dict_mask,
+                                         const int* dict_word, int dict_states, int dict_cols,
+                                         const int* lm_table, int64_t lm_slots, int max_frames,
+                                         int t_done, int out_cap, int* out_ids, int* out_offsets,
+                                         int* out_lens, float* out_scores, int* out_frames,
+                                         void* state, size_t state_bytes, ds2_stream_t stream);
+
 /* bf16 GEMM on bf16 operands (BASELINE cfg4's bf16 MFMA RNN GEMMs; csrc/bgemm.hip):
  * C[m x n] (fp32, ldc) = alpha * A . B^T + beta * C + bias, A [m][lda] and B [n][ldb] bf16
  * (raw 16-bit words, k-contiguous), fp32 accumulation.  A and B 16-B aligned, k, lda, ldb

@@ -26,7 +26,8 @@ constexpr int kRows = 161;     // rows of the returned spectrogram (data_loader_
 constexpr int kMaskInts = 9;   // per utterance: f_lo0 f_hi0 f_lo1 f_hi1 t_lo0 t_hi0 t_lo1 t_hi1 f_cut
 
 __device__ __forceinline__ int reflect_idx(int i, int n) {
-  // numpy 'reflect' (edge sample not repeated); assumes n > 1
+  // numpy 'reflect' (edge sample not repeated); one sample is repeated everywhere
+  if (n <= 1) return 0;
   const int period = 2 * (n - 1);
   i = i % period;
   if (i < 0) i += period;
@@ -39,6 +40,13 @@ __device__ __forceinline__ int scipy_reflect(int i, int n) {
   i = i % period;
   if (i < 0) i += period;
   return i < n ? i : period - 1 - i;
+}
+
+// librosa's frame count with center=True: the signal padded by n_fft/2 on both sides holds
+// 1 + (n + 2 (n_fft/2) - n_fft) / hop frames -- for odd n_fft that is 1 + (n - 1) / hop.  A row
+// without samples has no frames (np.pad cannot reflect an empty axis; the host refuses it).
+__device__ __forceinline__ int frame_count(int n, int n_fft, int hop) {
+  return n >= 1 ? 1 + (n + 2 * (n_fft / 2) - n_fft) / hop : 0;
 }
 
 // grid (ceil(max_frames / SF), batch); block 256 (thread = frequency bin)
@@ -57,7 +65,7 @@ __global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ pcm
   const int b = blockIdx.y;
   const int t0 = blockIdx.x * SF;
   const int nb = n_samples[b];
-  const int T = 1 + nb / hop;
+  const int T = frame_count(nb, n_fft, hop);
   const int F = n_fft / 2 + 1;
   // bins computed: the 161 returned rows when F >= 161 (spect[:161], :249); all F bins in
   // the raw mode (F < 161: the mirror-fill layout is built from them by remap_kernel)
@@ -179,8 +187,8 @@ __global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ pcm
 // (161 t + r) / F), rows 81..160 mirror rows 80..1.  Then the spectrogram masks, the 8 kHz
 // cut, log1p and the per-column mean, as in the fused kernel.  One wave per column.
 __global__ __launch_bounds__(256) void remap_kernel(const float* __restrict__ raw,
-                                                    const int* __restrict__ n_samples, int hop,
-                                                    int F, int normalize, int max_frames,
+                                                    const int* __restrict__ n_samples, int n_fft,
+                                                    int hop, int normalize, int max_frames,
                                                     const int* __restrict__ masks,
                                                     float* __restrict__ out,
                                                     float* __restrict__ frame_mean,
@@ -189,7 +197,8 @@ __global__ __launch_bounds__(256) void remap_kernel(const float* __restrict__ ra
   const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (t >= max_frames) return;
-  const int T = 1 + n_samples[b] / hop;
+  const int F = n_fft / 2 + 1;
+  const int T = frame_count(n_samples[b], n_fft, hop);
   int fm[4] = {0, 0, 0, 0}, tm[4] = {0, 0, 0, 0}, fcut = kRows;
   if (masks != nullptr) {
     const int* mk = masks + b * kMaskInts;
@@ -233,13 +242,13 @@ __global__ __launch_bounds__(256) void remap_kernel(const float* __restrict__ ra
 // One block per utterance.  taps != nullptr ('max_frame', 'frame'): offset =
 // mean_t(gaussian_filter1d(frame_mean, sigma)); else ('mean', 'norm') offset = the mean over
 // all 161 x T values = mean_t(frame_mean), and with frame_std ('norm') scale = mean_t(std).
-__global__ void maxframe_offset_kernel(const int* __restrict__ n_samples, int hop,
+__global__ void maxframe_offset_kernel(const int* __restrict__ n_samples, int n_fft, int hop,
                                        int max_frames, const float* __restrict__ frame_mean,
                                        const float* __restrict__ frame_std,
                                        const float* __restrict__ taps, int radius,
                                        float* __restrict__ offset, float* __restrict__ scale) {
   const int b = blockIdx.x;
-  int T = 1 + n_samples[b] / hop;
+  int T = frame_count(n_samples[b], n_fft, hop);
   if (T > max_frames) T = max_frames;
   const float* m = frame_mean + (int64_t)b * max_frames;
   double acc = 0.0, acc2 = 0.0;
@@ -262,17 +271,19 @@ __global__ void maxframe_offset_kernel(const int* __restrict__ n_samples, int ho
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    offset[b] = static_cast<float>((red[0] + red[1] + red[2] + red[3]) / T);
-    if (scale != nullptr) scale[b] = static_cast<float>((red2[0] + red2[1] + red2[2] + red2[3]) / T);
+    // a row without frames has nothing to subtract from: no 0 / 0 left in the workspace
+    offset[b] = T > 0 ? static_cast<float>((red[0] + red[1] + red[2] + red[3]) / T) : 0.f;
+    if (scale != nullptr)
+      scale[b] = T > 0 ? static_cast<float>((red2[0] + red2[1] + red2[2] + red2[3]) / T) : 1.f;
   }
 }
 
-__global__ void subtract_offset_kernel(const int* __restrict__ n_samples, int hop, int F,
-                                       int max_frames, const float* __restrict__ offset,
+__global__ void subtract_offset_kernel(const int* __restrict__ n_samples, int n_fft, int hop,
+                                       int F, int max_frames, const float* __restrict__ offset,
                                        const float* __restrict__ scale,
                                        float* __restrict__ out) {
   const int b = blockIdx.y;
-  int T = 1 + n_samples[b] / hop;
+  int T = frame_count(n_samples[b], n_fft, hop);
   if (T > max_frames) T = max_frames;
   const float o = offset[b];
   const float sc = scale != nullptr ? scale[b] : 1.0f;
@@ -332,20 +343,20 @@ ds2_status_t ds2_stft_logmag_masked(const float* pcm, const int* n_samples, int 
                        n_samples, max_samples, n_fft, hop, window, normalize, out, max_frames,
                        frame_mean, nullptr, masks, raw);
     hipLaunchKernelGGL(remap_kernel, dim3(cdiv(max_frames, 4), batch), dim3(256), 0, st, raw,
-                       n_samples, hop, F, normalize, max_frames, masks, out, frame_mean, fstd);
+                       n_samples, n_fft, hop, normalize, max_frames, masks, out, frame_mean, fstd);
   } else {
     hipLaunchKernelGGL(stft_kernel, dim3(cdiv(max_frames, SF), batch), dim3(256), 0, st, pcm,
                        n_samples, max_samples, n_fft, hop, window, normalize, out, max_frames,
                        frame_mean, fstd, masks, nullptr);
   }
   if (normalize != 0) {
-    hipLaunchKernelGGL(maxframe_offset_kernel, dim3(batch), dim3(256), 0, st, n_samples, hop,
+    hipLaunchKernelGGL(maxframe_offset_kernel, dim3(batch), dim3(256), 0, st, n_samples, n_fft, hop,
                        max_frames, frame_mean, fstd, smooth ? gauss_taps : nullptr, gauss_radius,
                        offset, normalize == 3 ? scale : nullptr);
     int g = cdiv((int64_t)kRows * max_frames, 256);
     if (g > 512) g = 512;
-    hipLaunchKernelGGL(subtract_offset_kernel, dim3(g, batch), dim3(256), 0, st, n_samples, hop,
-                       kRows, max_frames, offset, normalize == 3 ? scale : nullptr, out);
+    hipLaunchKernelGGL(subtract_offset_kernel, dim3(g, batch), dim3(256), 0, st, n_samples, n_fft,
+                       hop, kRows, max_frames, offset, normalize == 3 ? scale : nullptr, out);
   }
   return launch_status("ds2_stft_logmag");
 }

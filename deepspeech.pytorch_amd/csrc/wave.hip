@@ -28,6 +28,14 @@ __global__ __launch_bounds__(WAV_T) void wave_aug_kernel(
   const int n = blockIdx.x;
   const int tid = threadIdx.x;
   int64_t len = in_lens[n];
+  // Consistency word: 1 = a length past cap (the input's, or a SHIFT's result) or a shift
+  // outside [0, limit]; 2 = a record that cannot be replayed (unknown kind, NOISE without a
+  // noise table); 4 = the final length is not out_lens[n].  A row that sets it writes nothing
+  // from that record on, and nothing to out.
+  if (len > cap) {
+    if (tid == 0) atomicOr(err, 1);
+    return;
+  }
   const float* src = in + (int64_t)n * in_stride;
   float* pp[2] = {buf + (int64_t)(2 * n) * cap, buf + (int64_t)(2 * n + 1) * cap};
   int which = 0;
@@ -58,6 +66,10 @@ __global__ __launch_bounds__(WAV_T) void wave_aug_kernel(
       // np.clip(v, 0, m) = minimum(maximum(v, 0), m)
       for (int64_t i = tid; i < len; i += WAV_T) dst[i] = fminf(fmaxf(alpha * src[i], 0.f), m);
     } else if (kind == WAV_NOISE) {
+      if (noise == nullptr) {
+        if (tid == 0) atomicOr(err, 2);
+        return;
+      }
       const double alpha = op_f[(int64_t)n * max_ops + o];
       const double* nz = noise + (int64_t)rec[1] * noise_stride;
       for (int64_t i = tid; i < len; i += WAV_T)

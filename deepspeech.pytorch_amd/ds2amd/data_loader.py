@@ -175,6 +175,11 @@ class SpectrogramParser(object):
         has sorted by length); None = row by row."""
         sr = sample_rate or self.sample_rate
         n_fft, hop, win, taps = self._consts(sr)
+        # a zero-length utterance has no spectrogram (np.pad cannot reflect an empty axis in
+        # the reference): refused here, before anything is uploaded or launched
+        for i, s in enumerate(signals):
+            if (s.length if isinstance(s, Wave) else len(s)) < 1:
+                raise ValueError(f"parse_batch: utterance {i} has no samples")
         if any(isinstance(s, Wave) and s.records for s in signals):
             pcm_d, lens = apply_waves(signals, self.device)
         else:
@@ -190,7 +195,7 @@ class SpectrogramParser(object):
                     pcm[i, :len(s)] = s
                 pcm_d = torch.from_numpy(pcm).to(self.device)
         ns_d = torch.tensor(lens, dtype=torch.int32).to(self.device)
-        frames = [1 + n // hop for n in lens]
+        frames = [ops.stft_frames(n, n_fft, hop) for n in lens]
         # the per-utterance draws (mask bands, offset) go row by row, or through the rows in
         # draw_order: draw k belongs to row draw_order[k]
         pos = None
@@ -558,8 +563,10 @@ class DeviceBatchLoader(object):
         if len(rates) != 1:
             raise ValueError(f"DeviceBatchLoader: one sample rate per batch, got {sorted(rates)}")
         sr = rates.pop()
+        n_fft = int(sr * (ds.window_size + 1e-8))
         hop = int(sr * (ds.window_stride + 1e-8))
-        rows = sorted(range(len(items)), key=lambda p: 1 + items[p][0].length // hop,
+        rows = sorted(range(len(items)),
+                      key=lambda p: ops.stft_frames(items[p][0].length, n_fft, hop),
                       reverse=True)                     # row x holds the sampler's item rows[x]
         draw_order = [rows.index(p) for p in range(len(items))]
         items = [items[p] for p in rows]

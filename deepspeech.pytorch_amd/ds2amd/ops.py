@@ -1032,7 +1032,13 @@ def stretch_plan(in_len: int, rate: float) -> tuple:
 
 def time_stretch(pcm: torch.Tensor, lens, rates) -> tuple:
     """Per-utterance librosa.effects.time_stretch on the device (ds2_time_stretch).
-    pcm [N, S] fp32 device, lens / rates host sequences -> (out [N, max out_len], out_lens)."""
+    pcm [N, S] fp32 device, lens / rates host sequences -> (out [N, max out_len], out_lens).
+    ValueError for a row librosa has no answer for: no samples (nothing to reflect), or a rate
+    that is not positive."""
+    for i, (l, r) in enumerate(zip(lens, rates)):
+        if int(l) < 1 or not float(r) > 0:
+            raise ValueError(f"time_stretch: row {i} has len {int(l)}, rate {float(r)}; "
+                             "need len >= 1 and rate > 0")
     pcm = _need(pcm, "time_stretch.pcm")
     n = pcm.shape[0]
     dev = pcm.device
@@ -1057,7 +1063,13 @@ def time_stretch(pcm: torch.Tensor, lens, rates) -> tuple:
 def resample(pcm: torch.Tensor, lens, ratios, out_lens=None) -> tuple:
     """Per-utterance resampy 'kaiser_best' resampling on the device (ds2_resample).
     ratios = sr_new / sr_orig (float64 as numpy forms it); each utterance yields
-    int(len * ratio) samples, zero-padded to out_lens (default: that count)."""
+    int(len * ratio) samples, zero-padded to out_lens (default: that count).  ValueError for a
+    ratio that is not positive, or so small that resampy's filter-table step
+    int(min(1, ratio) * 512), which it divides by, is 0."""
+    for i, r in enumerate(ratios):
+        if not float(r) > 0 or int(min(1.0, float(r)) * 512) < 1:
+            raise ValueError(f"resample: row {i} has ratio {float(r)}; need a table step "
+                             "int(min(1, ratio) * 512) >= 1")
     pcm = _need(pcm, "resample.pcm")
     n = pcm.shape[0]
     dev = pcm.device
@@ -1078,6 +1090,17 @@ def resample(pcm: torch.Tensor, lens, ratios, out_lens=None) -> tuple:
 
 
 SPECT_ROWS = 161   # rows of every spectrogram the reference returns (data_loader_aug.py:234-249)
+
+
+def stft_frames(n: int, n_fft: int, hop: int) -> int:
+    """Frames of librosa.stft(center=True) over n >= 1 samples, the count every kernel of
+    csrc/stft.hip uses: the signal padded by n_fft // 2 on both sides holds
+    1 + (n + 2 * (n_fft // 2) - n_fft) // hop windows (1 + (n - 1) // hop for odd n_fft).
+    A zero-length utterance has no spectrogram: np.pad cannot reflect an empty axis."""
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"stft: an utterance of {n} samples has no frames")
+    return 1 + (n + 2 * (n_fft // 2) - n_fft) // hop
 
 
 def stft_logmag(pcm: torch.Tensor, n_samples: torch.Tensor, n_fft: int, hop: int,

@@ -45,7 +45,9 @@ const char* ds2_version(void);
 /* Features: SpectrogramParser.audio_to_stft + normalize_audio('max_frame') */
 /* ref data/data_loader.py:201-220,276-284; data/data_loader_aug.py:220-249,297-307 */
 /* pcm:  [batch][max_samples] float32, utterance b has n_samples[b] valid samples   */
-/* out:  [batch][161][max_frames], frames t >= 1 + n_samples[b]/hop are zero: the     */
+/* out:  [batch][161][max_frames], frames t >= 1 + (n_samples[b] + 2*(n_fft/2) - n_fft)/hop */
+/*       (librosa's count with center=True; one fewer than 1 + n/hop when n_fft is odd and */
+/*       hop divides n) are zero, and so is the whole row when n_samples[b] <= 0: the     */
 /*       reference always returns 161 rows (data_loader_aug.py:234-249): the first   */
 /*       161 bins when n_fft/2+1 >= 161, else its mirror-fill of ndarray.resize on    */
 /*       librosa's (Fortran-ordered) stft matrix -- see stft.hip remap_kernel.         */
@@ -80,7 +82,10 @@ ds2_status_t ds2_stft_logmag_masked(const float* pcm, const int* n_samples, int 
  * (kind 0 end, 1 shift (a = shift, b = limit), 2 distort, 3 noise (a = noise row)),
  * op_f [n][max_ops] = alpha; noise [rows][noise_stride] float64 slices; out:
  * [n][out_stride] zero padded, out_lens = the lengths the host expects (mismatch, a bad
- * record or cap too small sets *err).  cap = the longest intermediate length.  Replaces
+ * record or cap too small sets *err).  cap = the longest intermediate length.  *err is OR-ed
+ * with 1 for a length past cap (in_lens itself, or a shift's result) or a shift outside
+ * [0, limit], 2 for a record that cannot be replayed (an unknown kind, noise with noise ==
+ * NULL), 4 for a final length other than out_lens; such a row leaves out untouched.  Replaces
  * the numpy arithmetic of load_randomly_augmented_audio (data_loader_aug.py:660-699). */
 size_t ds2_wave_aug_workspace_size(int n, int64_t cap);
 ds2_status_t ds2_wave_aug(const float* in, int64_t in_stride, const int* in_lens, int n,

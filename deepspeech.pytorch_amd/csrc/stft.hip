@@ -16,23 +16,15 @@
 // a 32 x 10 s batch, far below the fp64 roof, and bit-for-bit free of the
 // float32 round-off a fp32 DFT would add to near-silent bins after the x2^20
 // gain of 'max_frame'.
+// The arithmetic of one frame (taps, DFT chain, magnitude, log, row mean) lives in
+// stft_frame.h, which the streaming front-end (stft_stream.hip) runs too.
 #include "common.h"
+#include "stft_frame.h"
 
 namespace ds2 {
 
 constexpr int SF = 8;          // frames per workgroup
-constexpr int SMAXN = 1024;    // max n_fft
-constexpr int kRows = 161;     // rows of the returned spectrogram (data_loader_aug.py:234-249)
 constexpr int kMaskInts = 9;   // per utterance: f_lo0 f_hi0 f_lo1 f_hi1 t_lo0 t_hi0 t_lo1 t_hi1 f_cut
-
-__device__ __forceinline__ int reflect_idx(int i, int n) {
-  // numpy 'reflect' (edge sample not repeated); one sample is repeated everywhere
-  if (n <= 1) return 0;
-  const int period = 2 * (n - 1);
-  i = i % period;
-  if (i < 0) i += period;
-  return i < n ? i : period - i;
-}
 
 __device__ __forceinline__ int scipy_reflect(int i, int n) {
   // scipy.ndimage mode='reflect' (half-sample symmetric): d c b a | a b c d
@@ -40,13 +32,6 @@ __device__ __forceinline__ int scipy_reflect(int i, int n) {
   i = i % period;
   if (i < 0) i += period;
   return i < n ? i : period - 1 - i;
-}
-
-// librosa's frame count with center=True: the signal padded by n_fft/2 on both sides holds
-// 1 + (n + 2 (n_fft/2) - n_fft) / hop frames -- for odd n_fft that is 1 + (n - 1) / hop.  A row
-// without samples has no frames (np.pad cannot reflect an empty axis; the host refuses it).
-__device__ __forceinline__ int frame_count(int n, int n_fft, int hop) {
-  return n >= 1 ? 1 + (n + 2 * (n_fft / 2) - n_fft) / hop : 0;
 }
 
 // grid (ceil(max_frames / SF), batch); block 256 (thread = frequency bin)
@@ -72,18 +57,13 @@ __global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ pcm
   const int R = raw != nullptr ? F : (F < kRows ? F : kRows);
   const int pad = n_fft / 2;
   const float* y = pcm + (int64_t)b * max_samples;
-  for (int m = threadIdx.x; m < n_fft; m += blockDim.x) {
-    double s, c;
-    sincospi(2.0 * m / n_fft, &s, &c);
-    cs[m] = c;
-    sn[m] = s;
-  }
+  stft_twiddles(cs, sn, n_fft);
   for (int i = threadIdx.x; i < SF * n_fft; i += blockDim.x) {
     const int f = i / n_fft;
     const int m = i - f * n_fft;
     const int t = t0 + f;
     double v = 0.0;
-    if (t < T) v = window[m] * (double)y[reflect_idx(t * hop + m - pad, nb)];
+    if (t < T) v = stft_tap(window, m, y[reflect_idx(t * hop + m - pad, nb)]);
     fr[f][m] = v;
   }
   __syncthreads();
@@ -108,27 +88,13 @@ __global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ pcm
   const float gain = normalize == 1 ? 1048576.0f : 1.0f;
   if (k < R) {
     double re[SF], im[SF];
-#pragma unroll
-    for (int f = 0; f < SF; ++f) { re[f] = 0.0; im[f] = 0.0; }
-    int idx = 0;   // (k * m) mod n_fft
-    for (int m = 0; m < n_fft; ++m) {
-      const double c = cs[idx], s = sn[idx];
-#pragma unroll
-      for (int f = 0; f < SF; ++f) {
-        const double v = fr[f][m];
-        re[f] = fma(v, c, re[f]);
-        im[f] = fma(-v, s, im[f]);
-      }
-      idx += k;
-      if (idx >= n_fft) idx -= n_fft;
-    }
+    stft_dft<SF>(cs, sn, fr, n_fft, k, re, im);
     if (raw != nullptr) {     // |D| frame-major, the memory order of librosa's stft matrix
 #pragma unroll
       for (int f = 0; f < SF; ++f) {
         const int t = t0 + f;
         if (t < T && t < max_frames)
-          raw[((int64_t)b * max_frames + t) * F + k] =
-              hypotf(static_cast<float>(re[f]), static_cast<float>(im[f]));
+          raw[((int64_t)b * max_frames + t) * F + k] = stft_mag(re[f], im[f]);
       }
       return;
     }
@@ -140,9 +106,8 @@ __global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ pcm
       if (t < T) {
         const bool masked =
             fmasked || (t >= tm[0] && t < tm[1]) || (t >= tm[2] && t < tm[3]);
-        const float mag =
-            masked ? 0.f : hypotf(static_cast<float>(re[f]), static_cast<float>(im[f]));
-        val = log1pf(mag * gain);
+        const float mag = masked ? 0.f : stft_mag(re[f], im[f]);
+        val = stft_logmag(mag, gain);
         lsum[f] = val;
       }
       out[((int64_t)b * R + k) * max_frames + t] = val;
@@ -151,11 +116,7 @@ __global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ pcm
   if (raw != nullptr) return;
   // mean over the F bins of every frame (torch spect.mean(dim=0)); 'norm' also the sum of
   // squares for the frame's unbiased std (spect.std(dim=0))
-#pragma unroll
-  for (int f = 0; f < SF; ++f) {
-    double v = wave_sum_d(lsum[f]);
-    if ((threadIdx.x & 63) == 0) red[f][threadIdx.x >> 6] = v;
-  }
+  stft_frame_sums<SF>(lsum, red);
   if (frame_std != nullptr) {
 #pragma unroll
     for (int f = 0; f < SF; ++f) {
@@ -168,7 +129,7 @@ __global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ pcm
     const int f = threadIdx.x;
     const int t = t0 + f;
     if (t < T && t < max_frames) {
-      const double s = red[f][0] + red[f][1] + red[f][2] + red[f][3];
+      const double s = stft_frame_sum(red[f]);
       frame_mean[(int64_t)b * max_frames + t] = static_cast<float>(s / R);
       if (frame_std != nullptr) {
         const double q = red2[f][0] + red2[f][1] + red2[f][2] + red2[f][3];

@@ -31,6 +31,13 @@ _PROTOS = {
                                  _c_int, _vp, _c_int, _vp, _sz, _vp]),
     "ds2_stft_logmag_masked": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _c_int,
                                         _vp, _c_int, _vp, _vp, _c_int, _vp, _sz, _vp]),
+    "ds2_stft_stream_state_size": (_sz, [_c_int, _c_int, _c_int]),
+    "ds2_stft_stream_workspace_size": (_sz, [_c_int, _c_int]),
+    "ds2_stft_stream_init": (_c_int, [_vp, _sz, _c_int, _c_int, _c_int, _vp, ctypes.c_double,
+                                      _vp]),
+    "ds2_stft_stream_feed": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_i64, _c_f, _c_i64, _c_int,
+                                      _c_int, _c_int, _vp, _c_int, _vp, _vp, _c_int, _vp, _vp,
+                                      _vp, _sz, _vp, _sz, _vp]),
     "ds2_wave_aug_workspace_size": (_sz, [_c_int, _c_i64]),
     "ds2_wave_aug": (_c_int, [_vp, _c_i64, _vp, _c_int, _vp, _vp, _c_int, _vp, _c_i64, _vp,
                               _c_i64, _vp, _c_i64, _vp, _vp, _sz, _vp]),

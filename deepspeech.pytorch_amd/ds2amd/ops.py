@@ -1126,6 +1126,96 @@ def stft_logmag(pcm: torch.Tensor, n_samples: torch.Tensor, n_fft: int, hop: int
     return out
 
 
+def _stft_stream_final(a: int, last: bool, n_fft: int, hop: int) -> int:
+    pad = n_fft // 2
+    if last:
+        return 1 + (a + 2 * pad - n_fft) // hop if a >= 1 else 0
+    return 1 + (a + pad - n_fft) // hop if a >= pad + 1 else 0
+
+
+def stft_stream_frames(a_before: int, a_after: int, last: bool, n_fft: int, hop: int) -> int:
+    """Frames a feed makes final when it takes a stream from a_before to a_after samples
+    (last: the utterance ends there).  With a samples arrived and the utterance open, frame t
+    is final iff max(t hop - pad + n_fft - 1, pad - t hop) <= a - 1 (pad = n_fft // 2): its
+    right edge and, for the first frames, the sample its left reflection reads.  That bound is
+    pad for t = 0, the right edge from t = 1 on and grows with t, so the final frames are the
+    first 1 + (a + pad - n_fft) // hop once a >= pad + 1; at the end all stft_frames(a) are."""
+    a_before, a_after = int(a_before), int(a_after)
+    if not 0 <= a_before <= a_after:
+        raise ValueError(f"stft_stream_frames: 0 <= a_before <= a_after, got {a_before}, {a_after}")
+    return (_stft_stream_final(a_after, bool(last), n_fft, hop)
+            - _stft_stream_final(a_before, False, n_fft, hop))
+
+
+def stft_stream_state(n: int, n_fft: int, hop: int, device,
+                      prior: Optional[Tuple[torch.Tensor, float]] = None,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The carried state of a streaming STFT over n streams (ds2_stft_stream_init): an opaque
+    uint8 device buffer, every stream at the start of an utterance.  prior: None or (o0, w),
+    o0 a float64 [n] device tensor and w >= 0 its weight in frames, for the causal offset.
+    ``out``: a buffer this function returned for the same arguments, reset in place."""
+    nbytes = _lib.size("ds2_stft_stream_state_size", int(n), int(n_fft), int(hop))
+    if nbytes == 0:
+        raise _lib.Ds2Error("stft_stream_state: n >= 1, hop >= 1 and 161 <= n_fft // 2 + 1 <= 256 "
+                            f"(got {n}, {n_fft}, {hop})")
+    state = torch.empty(nbytes, dtype=torch.uint8, device=device) if out is None else out
+    if not state.is_cuda or state.dtype != torch.uint8 or state.numel() < nbytes:
+        raise _lib.Ds2Error("stft_stream_state: out is not a state buffer of this size")
+    o0, w = (None, 0.0) if prior is None else prior
+    if o0 is not None:
+        o0 = _need(o0, "stft_stream_state.prior", torch.float64)
+        if o0.numel() != n or o0.device != state.device:
+            raise _lib.Ds2Error("stft_stream_state: the prior offset is [n] on the state's device")
+    _lib.call("ds2_stft_stream_init", state.data_ptr(), state.numel(), int(n), int(n_fft),
+              int(hop), _p(o0), float(w), _stream())
+    return state
+
+
+def stft_stream_feed(state: torch.Tensor, pcm: torch.Tensor, samples_done: int, last: bool,
+                     n_fft: int, hop: int, window: torch.Tensor, normalize: int,
+                     fixed_offset: Optional[torch.Tensor] = None,
+                     scale: float = 2.0 ** -15,
+                     cur_offset: Optional[torch.Tensor] = None):
+    """One chunk of a streaming STFT.  pcm [N, S] (S >= 0) float32 in [-1, 1] or int16 (read as
+    s * scale), the next S samples of the N streams of ``state`` (stft_stream_state);
+    samples_done the samples fed by earlier calls; last: the utterance ends with this chunk.
+    normalize 0: log1p(|X|); 1: log1p(|X| 2^20) minus fixed_offset (float32 [N]) or, without
+    one, the causal running offset (ds2hip.h).  cur_offset: None or a float64 [N] device
+    tensor that receives the running mean of the frame means.
+
+    Returns (out [N, 161, k] fp32, frames [N] int32): the k = stft_stream_frames(...) frames
+    this chunk made final, and the frames emitted so far per stream (-1: the state was not
+    initialised for this geometry and count; nothing was written for that stream).  Nothing
+    synchronises."""
+    if not pcm.is_cuda or pcm.dtype not in (_F32, torch.int16) or pcm.dim() != 2:
+        raise _lib.Ds2Error("stft_stream_feed: expected a [N, S] float32 or int16 device tensor")
+    n, s = pcm.shape
+    if s > 0 and (pcm.stride(1) != 1 or (n > 1 and pcm.stride(0) < s)):
+        pcm = pcm.contiguous()
+    dev = pcm.device
+    window = _need(window, "stft_stream.window", torch.float64)
+    if window.numel() != n_fft:
+        raise _lib.Ds2Error(f"stft_stream_feed: the window has {window.numel()} taps, n_fft {n_fft}")
+    if fixed_offset is not None:
+        fixed_offset = _need(fixed_offset, "stft_stream.fixed_offset")
+        if fixed_offset.numel() != n:
+            raise _lib.Ds2Error("stft_stream_feed: fixed_offset is [N]")
+    if cur_offset is not None and (not cur_offset.is_cuda or cur_offset.dtype != torch.float64
+                                   or cur_offset.numel() != n or not cur_offset.is_contiguous()):
+        raise _lib.Ds2Error("stft_stream_feed: cur_offset is a contiguous float64 [N] device tensor")
+    k = stft_stream_frames(samples_done, int(samples_done) + s, last, n_fft, hop)
+    out = torch.empty(n, SPECT_ROWS, k, device=dev, dtype=_F32)
+    frames = torch.empty(n, device=dev, dtype=_I32)
+    ws = _ws(_lib.size("ds2_stft_stream_workspace_size", n, k), dev)
+    _lib.call("ds2_stft_stream_feed", pcm.data_ptr() if s > 0 else None,
+              1 if pcm.dtype == torch.int16 else 0, n, s, pcm.stride(0) if s > 0 else 0,
+              float(scale), int(samples_done), int(bool(last)), int(n_fft), int(hop),
+              window.data_ptr(), int(normalize), _p(fixed_offset),
+              out.data_ptr() if k > 0 else None, k, _p(cur_offset), frames.data_ptr(),
+              state.data_ptr(), state.numel(), ws.data_ptr(), ws.numel(), _stream())
+    return out, frames
+
+
 # ----------------------------------------------------------------------------
 # autograd functions
 class ConvBlockFn(torch.autograd.Function):

@@ -75,6 +75,61 @@ ds2_status_t ds2_stft_logmag_masked(const float* pcm, const int* n_samples, int 
                                     const int* masks, float* out, int max_frames, void* ws,
                                     size_t ws_bytes, ds2_stream_t stream);
 
+/* The same frames over a stream (csrc/stft_stream.hip): PCM arrives in chunks, all n streams
+ * in lock-step, and a feed returns the frames that have become final -- with a samples
+ * arrived and the utterance open, frame t is final iff max(t hop - pad + n_fft - 1,
+ * pad - t hop) <= a - 1 (pad = n_fft / 2: its right edge and the sample its left reflection
+ * reads), which holds for the first (a >= pad + 1 ? 1 + (a + pad - n_fft) / hop : 0) frames;
+ * the last feed emits the rest, up to the count above, reflecting at the true end.  A frame
+ * is computed by the code ds2_stft_logmag runs, from the same samples: normalize 0 gives
+ * log1p(|X|) bit for bit the rows of ds2_stft_logmag(normalize = 0) on the whole utterance,
+ * over any partition.  normalize 1 gives val = log1p(|X| 2^20) minus an offset that can be
+ * had on a stream (the reference's mean_t(gauss20(mean_f)) reads the whole utterance):
+ *   fixed_offset != NULL   out = val - fixed_offset[b]
+ *   fixed_offset == NULL   out = val - (float)off_t, off_t = (w o0 + S_t) / (w + t + 1) in
+ *               fp64, S_t = S_{t-1} + (double)m_t summed in frame order, m_t the frame's
+ *               float32 mean over its 161 values as ds2_stft_logmag computes it, (o0, w) the
+ *               prior given to init: a pure function of the prefix, so bit for bit the same
+ *               over any partition
+ * Only n_fft with 161 <= n_fft / 2 + 1 <= 256 can stream (DS2_UNSUPPORTED_SHAPE otherwise:
+ * the mirror-fill for fewer bins reads frames ahead of the column it fills).  No masks.
+ * State: one opaque device buffer of ds2_stft_stream_state_size(n, n_fft, hop) bytes (0 for
+ * arguments no state exists for), 256-byte aligned, owned by the caller: per stream the
+ * last min(a, n_fft - 1) samples and samples 0 .. pad as float32, the fp64 sum S_t, the
+ * prior and a tag (geometry and samples taken).  ds2_stft_stream_init starts an utterance on
+ * all n streams; prior_offset NULL (no prior, w = 0) or n device doubles o0 with weight
+ * prior_frames >= 0.
+ * ds2_stft_stream_feed:
+ *   chunk       [n][chunk_samples] with row stride chunk_stride (elements): dtype 0 float32
+ *               in [-1, 1], dtype 1 int16 read as (float)s * scale (2^-15 is exact); may be
+ *               NULL when chunk_samples == 0
+ *   samples_done  samples fed by earlier calls since init (the caller's count: no call
+ *               synchronises); last 0 / 1: the utterance ends with this chunk
+ *   window      n_fft doubles; normalize 0 / 1; fixed_offset NULL or [n] floats (normalize 1)
+ *   out         [n][161][k], k = the frames this feed makes final; a k other than what
+ *               samples_done, chunk_samples and last yield is DS2_INVALID_VALUE
+ *   cur_offset  NULL or [n] doubles: S_t / (t + 1) after this feed (o0 before any frame)
+ *   out_frames  NULL or [n] int32: frames emitted so far, -1 for a record whose tag does not
+ *               match (n_fft, hop, samples_done): such a stream is not advanced and its rows
+ *               of out are not written (the tag is on the device, so the host cannot refuse)
+ *   ws          ds2_stft_stream_workspace_size(n, k) bytes (normalize 1, k > 0: the frame means)
+ * Two launches (one when k == 0), no allocation, no synchronisation.  n == 0, or
+ * chunk_samples == 0 without last, is DS2_OK and launches nothing.  DS2_INVALID_VALUE,
+ * before anything is launched, also for a NULL or misaligned state and a state_bytes below
+ * the size query.  Feeds of one state must be ordered (one stream, or events). */
+size_t ds2_stft_stream_state_size(int n, int n_fft, int hop);
+size_t ds2_stft_stream_workspace_size(int n, int k);
+ds2_status_t ds2_stft_stream_init(void* state, size_t state_bytes, int n, int n_fft, int hop,
+                                  const double* prior_offset, double prior_frames,
+                                  ds2_stream_t stream);
+ds2_status_t ds2_stft_stream_feed(const void* chunk, int dtype, int n, int chunk_samples,
+                                  int64_t chunk_stride, float scale, int64_t samples_done,
+                                  int last, int n_fft, int hop, const double* window,
+                                  int normalize, const float* fixed_offset, float* out, int k,
+                                  double* cur_offset, int* out_frames, void* state,
+                                  size_t state_bytes, void* ws, size_t ws_bytes,
+                                  ds2_stream_t stream);
+
 /* Waveform augmentations before the STFT: replays per-utterance op records drawn on the
  * host by ds2amd/audio_aug.py in the reference's `random` / `np.random` order —
  * Shift (data/audio_aug.py:26-44), AudioDistort (:47-60,177-178), AddNoise (:78-107).

@@ -25,17 +25,13 @@
 // retired by lgkmcnt(0) BEFORE the barrier that ends that load segment (WAR).  All LDS traffic
 // of the loop is LDS-DMA + ds_read; no ordinary global load is pending in the loop (hipcc would
 // drain the DMA queue at it).
-#include "common.h"
+#include "split_mma.h"
 #include "gemm_host.h"
 
 #include <algorithm>
 
 namespace ds2 {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BG_M = 256, BG_N = 256, BG_K = 64, BG_T = 512;
 constexpr int BG_IMG = (BG_M + BG_N) * BG_K;   // bf16 per LDS buffer (A rows, then B rows)
@@ -269,7 +265,7 @@ __global__ __launch_bounds__(256) void cvt_bf16_kernel(const float* __restrict__
     u32x4 o;
 #pragma unroll
     for (int e = 0; e < 4; ++e)
-      o[e] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2v{v[2 * e], v[2 * e + 1]}, bf16x2v));
+      o[e] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{v[2 * e], v[2 * e + 1]}, bf16x2));
     return o;
   };
   if (!transpose) {

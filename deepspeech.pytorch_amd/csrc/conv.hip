@@ -528,7 +528,7 @@ __global__ __launch_bounds__(256) void conv_patch_kernel(const float* __restrict
 
   // channel-invariant part of this thread's patch offsets: (row, col) of idx = tid + 256 r
   float rp[PT_PREG];
-  cu32x4 rw[PT_WREG4];
+  u32x4 rw[PT_WREG4];
   auto load = [&](int c) {
     const __amdgpu_buffer_rsrc_t rs = conv_rsrc(inn + (int64_t)c * plane, plane);
     int row = tid / p.pcols, col = tid - (tid / p.pcols) * p.pcols;
@@ -566,7 +566,7 @@ __global__ __launch_bounds__(256) void conv_patch_kernel(const float* __restrict
 #pragma unroll
     for (int r = 0; r < PT_WREG4; ++r) {
       const int i = tid + 256 * r;
-      if (i < wq) *reinterpret_cast<cu32x4*>(wl + 4 * i) = rw[r];
+      if (i < wq) *reinterpret_cast<u32x4*>(wl + 4 * i) = rw[r];
     }
   };
 

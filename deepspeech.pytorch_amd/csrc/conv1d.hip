@@ -5,7 +5,7 @@
 //
 // Fast path: an implicit GEMM on v_mfma_f32_16x16x32_f16 at fp32-class accuracy (fp16x3, the
 // two-term fp16 split under power-of-two row scales of gemm.hip's fp16x3 kernel; h3_exp /
-// h3_scale in common.h).  Output row (t, n) reads the window of k input rows t s - p ..
+// h3_scale in split_mma.h).  Output row (t, n) reads the window of k input rows t s - p ..
 // t s - p + k - 1 of sample n, each a contiguous Cin run, so K = k Cin walks (tap, channel
 // chunk of 32) stages; a tap outside [0, T) and the channels past Cin are predicated to zero
 // in the loader (no padded copy of the activations).  The weights are re-laid once per call
@@ -22,15 +22,10 @@
 #include <stdlib.h>
 
 #include "amax_rc.h"
-#include "common.h"
+#include "split_mma.h"
 
 namespace ds2 {
 namespace {
-
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 
 struct C1Dims {
   int t_in, n, ci, co, k, s, p, t_out;
@@ -100,22 +95,6 @@ constexpr int CT = 128;           // tile edge (rows of A and of B)
 constexpr int CP = CT * CK;       // fp16 per plane
 __device__ __forceinline__ int cslot(int row, int s) { return row * CK + 8 * (s ^ ((row >> 1) & 3)); }
 
-// 8 floats x sc -> hi = f16(x sc), lo = f16(x sc - hi): two 16-B stores
-__device__ __forceinline__ void c1_split_store(unsigned short* __restrict__ s, int at,
-                                               const float* v, float sc) {
-  u32x4v h, l;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const f32x2 x = f32x2{v[2 * j], v[2 * j + 1]} * sc;
-    const f16x2 hh = __builtin_convertvector(x, f16x2);
-    const f32x2 r = x - __builtin_convertvector(hh, f32x2);
-    h[j] = __builtin_bit_cast(unsigned, hh);
-    l[j] = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2));
-  }
-  *reinterpret_cast<u32x4v*>(s + at) = h;
-  *reinterpret_cast<u32x4v*>(s + CP + at) = l;
-}
-
 // one stage of MFMAs: wave tile 64 x 64 = 4 x 4 tiles of 16 x 16, three products per pair
 // (lo.hi + hi.lo + hi.hi; lo.lo, below 2^-22 |a b|, dropped)
 __device__ __forceinline__ void c1_mma_stage(const unsigned short* __restrict__ as,
@@ -137,11 +116,7 @@ __device__ __forceinline__ void c1_mma_stage(const unsigned short* __restrict__ 
     for (int p = 0; p < 2; ++p) bq[p] = *reinterpret_cast<const f16x8*>(bs + p * CP + bt);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      f32x4 c = acc[i][j];
-      c = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i][1], bq[0], c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i][0], bq[1], c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i][0], bq[0], c, 0, 0, 0);
-      acc[i][j] = c;
+      acc[i][j] = mma3h(af[i][0], af[i][1], bq[0], bq[1], acc[i][j]);
     }
   }
 }
@@ -264,8 +239,8 @@ __global__ __launch_bounds__(256, 2) void c1_igemm_kernel(
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int at = cslot((t >> 2) + 64 * u, slot);
-      c1_split_store(As[cur], at, ra[u], a_sc[u]);
-      c1_split_store(Bs[cur], at, rb[u], b_sc[u]);
+      split_store8<2>(As[cur], CP, at, ra[u], a_sc[u]);
+      split_store8<2>(Bs[cur], CP, at, rb[u], b_sc[u]);
     }
     // stage kt visible; the other buffer (stage kt - 1) is free once every wave is here
     __syncthreads();
@@ -360,8 +335,8 @@ __global__ __launch_bounds__(256, 2) void c1_wgrad_kernel(
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int at = cslot(row, 2 * kh + h);
-      c1_split_store(As[cur], at, ra + 8 * h, a_sc);
-      c1_split_store(Bs[cur], at, rb + 8 * h, b_sc);
+      split_store8<2>(As[cur], CP, at, ra + 8 * h, a_sc);
+      split_store8<2>(Bs[cur], CP, at, rb + 8 * h, b_sc);
     }
     __syncthreads();
     if (kt + 1 < stages) load(kt + 1);

@@ -6,7 +6,7 @@
 // DESIGN.md "Conv2d dispatch" has the ladder per direction; INTEGRATION.md the switches.
 #pragma once
 
-#include "common.h"
+#include "split_mma.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -152,8 +152,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t conv_rsrc(const float* p, int6
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p), (short)0,
                                            static_cast<int>(elems * 4), 0x00020000);
 }
-
-typedef unsigned int cu32x4 __attribute__((ext_vector_type(4)));
 
 // --- environment switches: read once per call, never cached (the tests flip them) -----------
 struct ConvSwitches {

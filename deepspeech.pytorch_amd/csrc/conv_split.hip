@@ -2,8 +2,8 @@
 // (bf16x6: three bf16 terms per operand, six products; fp16x3: two scaled fp16 terms, three
 // products) and the launchers of their rungs (launch_conv_split*, at the end), which conv.hip's
 // entry points call with the plan conv_host.h made.  In file order:
-//   * the operand splits and MFMA groups (cx_*), the fp16x3 scale kernels (conv_h3_wexp_kernel,
-//     conv_h3_samax_kernel, conv_h3_chamax_kernel);
+//   * the MFMA groups on its fragments (cx_mma*: split_mma.h's), the fp16x3 scale kernels
+//     (conv_h3_wexp_kernel, conv_h3_samax_kernel, conv_h3_chamax_kernel);
 //   * forward and 8-row-fragment dgrad, one output row per workgroup (conv_x6_wimg_kernel,
 //     conv_x6_kernel), and conv2's two-row fp16x3 forward (conv_h3_fwd2r_kernel);
 //   * the weight gradients for 11 kernel columns: per-row re-staging (conv_x6_wgrad_kernel),
@@ -37,121 +37,22 @@ namespace ds2 {
 // columns) is split and stored column-major (pitch P = 8 x odd bf16: conflict-free
 // fragment reads) and the channel's pre-split weight image [3][32][COP] is copied in; the
 // next channel's global loads fly during the MFMAs.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef cu32x4 u32x4;
-typedef __bf16 cbf16x2 __attribute__((ext_vector_type(2)));
-typedef float cf32x2 __attribute__((ext_vector_type(2)));
 
-// two fp32 -> (hi, mid, lo) bf16 pairs: one v_cvt_pk_bf16_f32 (RNE) per term pair, the
-// residuals exact in fp32 (bit-identical to per-element casts, half the instructions)
-__device__ __forceinline__ void cx_split2(float x0, float x1, unsigned& h, unsigned& m,
-                                          unsigned& l) {
-  h = __builtin_bit_cast(unsigned, __builtin_convertvector(cf32x2{x0, x1}, cbf16x2));
-  const float r0 = x0 - __builtin_bit_cast(float, h << 16);
-  const float r1 = x1 - __builtin_bit_cast(float, h & 0xffff0000u);
-  m = __builtin_bit_cast(unsigned, __builtin_convertvector(cf32x2{r0, r1}, cbf16x2));
-  const float q0 = r0 - __builtin_bit_cast(float, m << 16);
-  const float q1 = r1 - __builtin_bit_cast(float, m & 0xffff0000u);
-  l = __builtin_bit_cast(unsigned, __builtin_convertvector(cf32x2{q0, q1}, cbf16x2));
-}
+// The planes of either format are read as bf16x8 fragments; fp16x3's are bit-cast for the MFMA.
+__device__ __forceinline__ f16x8 as_h(bf16x8 v) { return __builtin_bit_cast(f16x8, v); }
 
-// 8 fp32 -> hi / mid / lo rows of 16 B at s + at, + plane, + 2 plane
-__device__ __forceinline__ void cx_split_store8(unsigned short* __restrict__ s, int plane, int at,
-                                                const float* v) {
-  u32x4 h, m, l;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    unsigned a, b, c;
-    cx_split2(v[2 * e], v[2 * e + 1], a, b, c);
-    h[e] = a;
-    m[e] = b;
-    l[e] = c;
-  }
-  *reinterpret_cast<u32x4*>(s + at) = h;
-  *reinterpret_cast<u32x4*>(s + plane + at) = m;
-  *reinterpret_cast<u32x4*>(s + 2 * plane + at) = l;
-}
-
-// fp16x3: 8 fp32 values times the power of two sc -> fp16 hi / lo rows of 16 B
-// at s + at, + plane (RNE casts; the residual is exact in fp32)
-typedef _Float16 cf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 cf16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void cx_split_store8h(unsigned short* __restrict__ s, int plane, int at,
-                                                 const float* v, float sc) {
-  u32x4 h, l;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const cf32x2 x = cf32x2{v[2 * e], v[2 * e + 1]} * sc;
-    const cf16x2 hh = __builtin_convertvector(x, cf16x2);
-    const cf16x2 ll = __builtin_convertvector(x - __builtin_convertvector(hh, cf32x2), cf16x2);
-    h[e] = __builtin_bit_cast(unsigned, hh);
-    l[e] = __builtin_bit_cast(unsigned, ll);
-  }
-  *reinterpret_cast<u32x4*>(s + at) = h;
-  *reinterpret_cast<u32x4*>(s + plane + at) = l;
-}
-
-// NPL 3: bf16 hi / mid / lo planes; NPL 2: fp16 hi / lo planes of v sc
-template <int NPL>
-__device__ __forceinline__ void cx_store8(unsigned short* __restrict__ s, int plane, int at,
-                                          const float* v, float sc) {
-  if constexpr (NPL == 2) cx_split_store8h(s, plane, at, v, sc);
-  else cx_split_store8(s, plane, at, v);
-}
-
-// acc += a.b over one 32 x 32 x 16 fragment pair: bf16x6 (6 products, small terms first) or
-// fp16x3 (lo.hi + hi.lo + hi.hi)
+// acc += a.b over one 32 x 32 x 16 fragment pair: bf16x6 or fp16x3 in one chain
 template <int NPL>
 __device__ __forceinline__ f32x16 cx_mma(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x16 c) {
-  if constexpr (NPL == 2) {
-    typedef cf16x8 H;
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(H, a[1]), __builtin_bit_cast(H, b[0]), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(H, a[0]), __builtin_bit_cast(H, b[1]), c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(H, a[0]), __builtin_bit_cast(H, b[0]), c, 0, 0, 0);
-  } else {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
-  }
+  if constexpr (NPL == 2) return mma3h(as_h(a[0]), as_h(a[1]), as_h(b[0]), as_h(b[1]), c);
+  else return mma6(a, b, c);
 }
 
-// acc += a.b, fp16x3 with the small products in their own chain: big += hi.hi, small +=
-// lo.hi + hi.lo.  The matrix cores floor (truncate toward -inf) each addend's bits below
-// ~2^-31 of the largest operand of the instruction, C included (scripts/mfma_rounding.hip,
-// profiles/r5n_mfma_rounding.txt).  Chained with hi.hi and a large C, every lo.hi product
-// lost its low bits to that floor: a small NEGATIVE bias per product that sums of the outputs
-// (the conv block's BatchNorm parameter gradients: 1.3 M nearly cancelling terms) amplify.  In
-// their own chain the small products keep every bit (their C stays ~2^-11 of the big one's);
-// the two sums meet by a VALU add (RNE).
+// fp16x3 with the small products in their own chain (split_mma.h, the product order): the sums
+// of the outputs that the conv block's BatchNorm parameter gradients take amplify their bias
 __device__ __forceinline__ void cx_mma_h3s(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x16& big,
                                            f32x16& small) {
-  typedef cf16x8 H;
-  small = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(H, a[1]), __builtin_bit_cast(H, b[0]), small, 0, 0, 0);
-  small = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(H, a[0]), __builtin_bit_cast(H, b[1]), small, 0, 0, 0);
-  big = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(H, a[0]), __builtin_bit_cast(H, b[0]), big, 0, 0, 0);
-}
-
-// a weight-image value's fp16x3 / bf16x6 terms (NPL planes, `per` apart from img[base])
-template <int NPL>
-__device__ __forceinline__ void cx_wimg_put(unsigned short* __restrict__ img, int64_t base,
-                                            int64_t per, float v, float sc) {
-  if constexpr (NPL == 2) {
-    const float x = v * sc;
-    const _Float16 hb = (_Float16)x;
-    img[base] = __builtin_bit_cast(unsigned short, hb);
-    img[base + per] = __builtin_bit_cast(unsigned short, (_Float16)(x - (float)hb));
-  } else {
-    const __bf16 hb = (__bf16)v;
-    const float r1 = v - (float)hb;
-    const __bf16 mbf = (__bf16)r1;
-    const __bf16 lb = (__bf16)(r1 - (float)mbf);
-    img[base] = __builtin_bit_cast(unsigned short, hb);
-    img[base + per] = __builtin_bit_cast(unsigned short, mbf);
-    img[base + 2 * per] = __builtin_bit_cast(unsigned short, lb);
-  }
+  mma3h2(as_h(a[0]), as_h(a[1]), as_h(b[0]), as_h(b[1]), big, small);
 }
 
 // fp16x3 scales of an implicit-GEMM convolution: m_exp[m] = h3_exp(max |w| over the taps and
@@ -281,7 +182,7 @@ __global__ void conv_x6_wimg_kernel(const float* __restrict__ w, ConvDims g, CxG
       if (flip_odd == 0 ? st >= (nks + 1) / 2 : (flip_odd == 1 && (l & 1) != 0)) v = -v;
     }
     const float sc = NPL == 2 && m < M ? h3_scale(m_exp[m]) : 1.f;
-    cx_wimg_put<NPL>(img, ((((int64_t)q * mbn + mb) * L + l) * NPL) * per + e, per, v, sc);
+    split_put<NPL>(img, ((((int64_t)q * mbn + mb) * L + l) * NPL) * per + e, per, v, sc);
   }
 }
 
@@ -404,7 +305,7 @@ __global__ __launch_bounds__(CX_T, 1) void conv_x6_kernel(const float* __restric
       const int unit = tid + CX_T * u;
       if (unit < units) {
         const int j = unit / ngr, rg = unit - (unit / ngr) * ngr;
-        cx_store8<NPL>(dst, PPL, j * cP + 8 * rg, rp[u], nsc);
+        split_store8<NPL>(dst, PPL, j * cP + 8 * rg, rp[u], nsc);
       }
     }
   };
@@ -634,7 +535,7 @@ __global__ __launch_bounds__(CX_T, 1) void conv_h3_fwd2r_kernel(
 #pragma unroll
     for (int u = 0; u < C2_PU; ++u) {
       const int unit = tid + CX_T * u;
-      if (unit < units) cx_store8<2>(dst, C2_PPL, (unit >> 2) * C2_P + 8 * (unit & 3), rp[u], nsc);
+      if (unit < units) split_store8<2>(dst, C2_PPL, (unit >> 2) * C2_P + 8 * (unit & 3), rp[u], nsc);
     }
   };
   auto store_w = [&]() __attribute__((always_inline)) {
@@ -760,10 +661,6 @@ constexpr int CW_XPL = 4 * 32 * CW_XP;     // bf16 per x plane
 constexpr int CW_DPL = 32 * CW_DP;         // bf16 per dy plane
 
 // 8 fp32 -> hi / mid / lo bf16 rows of 16 B (RNE casts, exact residuals)
-__device__ __forceinline__ void cw_split_store(unsigned short* __restrict__ s, int plane, int at,
-                                               const float (&v)[8]) {
-  cx_split_store8(s, plane, at, v);
-}
 
 // Partial sums of the bf16x6 weight-gradient kernels: one contiguous block per workgroup,
 // partial[s][gi][co 32][w 4][b KW][ci 32] (tap row a = 4 gi + w) -- lane fr = ci, so every
@@ -885,12 +782,12 @@ __global__ __launch_bounds__(CW_T, 2) void conv_x6_wgrad_kernel(const float* __r
         }
       }
       __syncthreads();   // every wave is done with the previous stage's fragments
-      cw_split_store(ds, CW_DPL, dco * CW_DP + 8 * dseg, dv);
+      split_store8<3>(ds, CW_DPL, dco * CW_DP + 8 * dseg, dv);
 #pragma unroll
       for (int u = 0; u < 5; ++u) {
         const int id = tid + CW_T * u;
         const int j = id % 10, ci = (id / 10) & 31, w = id / 320;
-        cw_split_store(xs, CW_XPL, (w * 32 + ci) * CW_XP + 8 * j, xv[u]);
+        split_store8<3>(xs, CW_XPL, (w * 32 + ci) * CW_XP + 8 * j, xv[u]);
       }
       __syncthreads();
       if (active) {
@@ -1081,11 +978,11 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_x6_wgrad_sw_ker
     };
     auto store = [&](int xr0, int nr, int db) {
       if (a_is_x && xr_a < nr)
-        cx_store8<NPL>(xs, XPL, slot_of(xr0 + xr_a) * XSL + xc_a * XP + 8 * xj_a, va, sc_a);
+        split_store8<NPL>(xs, XPL, slot_of(xr0 + xr_a) * XSL + xc_a * XP + 8 * xj_a, va, sc_a);
       if (b_is_x) {
-        if (nr > 1) cx_store8<NPL>(xs, XPL, slot_of(xr0 + 1) * XSL + xc_b * XP + 8 * xj_b, vb, sc_b);
+        if (nr > 1) split_store8<NPL>(xs, XPL, slot_of(xr0 + 1) * XSL + xc_b * XP + 8 * xj_b, vb, sc_b);
       } else if (b_is_dy && db >= 0) {
-        cx_store8<NPL>(ds[db], DPL, dc_b * DP + 8 * dj_b, DY_IN_A ? va : vb, DY_IN_A ? sc_a : sc_b);
+        split_store8<NPL>(ds[db], DPL, dc_b * DP + 8 * dj_b, DY_IN_A ? va : vb, DY_IN_A ? sc_a : sc_b);
       }
     };
     // segment start: every slot and dy buffer is free once all waves pass this barrier; the
@@ -1137,8 +1034,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_x6_wgrad_sw_ker
 #pragma unroll
               for (int i = NPL - 1 - pl; i >= 0; --i) {
                 if constexpr (NPL == 2)
-                  acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(cf16x8, af[i]),
-                                                                  __builtin_bit_cast(cf16x8, bx),
+                  acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h(af[i]),
+                                                                  as_h(bx),
                                                                   acc[b], 0, 0, 0);
                 else
                   acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bx, acc[b], 0, 0, 0);
@@ -1208,7 +1105,7 @@ __global__ void conv_x6q_wimg_kernel(const float* __restrict__ w, ConvDims g,
     // dgrad kernel's epilogue (flip_odd: the odd loop channels instead, conv_h3_dgrad2r_kernel)
     if (flip_odd ? (l & 1) != 0 : slot >= ((CQ_NK + 1) / 2) * 16) v = -v;
     const float sc = NPL == 2 && m < M ? h3_scale(m_exp[m]) : 1.f;
-    cx_wimg_put<NPL>(img, ((((int64_t)q * mbn + mb) * L + l) * NPL) * per + e, per, v, sc);
+    split_put<NPL>(img, ((((int64_t)q * mbn + mb) * L + l) * NPL) * per + e, per, v, sc);
   }
 }
 
@@ -1307,7 +1204,7 @@ __global__ __launch_bounds__(CX_T, 1) void conv_x6q_dgrad_kernel(const float* __
     unsigned short* wb = ws + b * wstride;
 #pragma unroll
     for (int u = 0; u < 2; ++u)
-      if (soff[u] >= 0) cx_store8<NPL>(pb, CQ_PPL, soff[u], rp[u], nsc);
+      if (soff[u] >= 0) split_store8<NPL>(pb, CQ_PPL, soff[u], rp[u], nsc);
 #pragma unroll
     for (int r = 0; r < WR; ++r) {
       const int i = tid + CX_T * r;
@@ -1521,7 +1418,7 @@ __global__ __launch_bounds__(CX_T, 1) void conv_h3_dgrad2r_kernel(
     unsigned short* wb = ws + b * wstride;
 #pragma unroll
     for (int u = 0; u < C2Q_PU; ++u)
-      if (soff[u] >= 0) cx_store8<2>(pb, C2Q_PPL, soff[u], rp[u], nsc);
+      if (soff[u] >= 0) split_store8<2>(pb, C2Q_PPL, soff[u], rp[u], nsc);
 #pragma unroll
     for (int r = 0; r < WR; ++r) {
       const int i = tid + CX_T * r;

@@ -9,7 +9,7 @@
 // tile k+1 are issued before the MFMAs of tile k (register double buffering).
 // Operands that are k-contiguous are transposed on the LDS write; the row pad
 // (+2 floats) makes those 8 ds_write_b32 per thread conflict-free.
-#include "common.h"
+#include "split_mma.h"
 #include "amax_rc.h"
 #include "gemm_host.h"
 
@@ -442,7 +442,6 @@ __global__ __launch_bounds__(256, 2) void sgemm64_kernel(
 //   k-contiguous source: a thread unit = (row, slot): 2 float4 loads -> 1 ds_write_b128;
 //   row-contiguous source: a unit = (4 rows, slot): 8 float4 loads (one per k) -> 4 writes.
 constexpr int KB16 = 64;   // k per stage
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ int bslot(int row, int s) { return row * KB16 + 8 * (s ^ ((row >> 1) & 7)); }
 
@@ -634,9 +633,6 @@ __device__ __forceinline__ int xslot_t(int row, int s) {
 constexpr int X2M = 256;                 // tile rows
 constexpr int X2T = 512;                 // threads
 constexpr int X2_AP = X2M * XS;          // bf16 per A plane
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 
 template <bool KC, int ROWS>
 struct X2Op {
@@ -690,67 +686,6 @@ __device__ __forceinline__ void x2_load(__amdgpu_buffer_rsrc_t rs, int ld, const
   }
 }
 
-// two fp32 -> (hi, mid, lo) bf16 pairs: v_cvt_pk_bf16_f32 (RNE), exact residuals
-__device__ __forceinline__ void x2_split2(float x0, float x1, unsigned& h, unsigned& m,
-                                          unsigned& l) {
-  h = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{x0, x1}, bf16x2));
-  const float r0 = x0 - __builtin_bit_cast(float, h << 16);
-  const float r1 = x1 - __builtin_bit_cast(float, h & 0xffff0000u);
-  m = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{r0, r1}, bf16x2));
-  const float l0 = r0 - __builtin_bit_cast(float, m << 16);
-  const float l1 = r1 - __builtin_bit_cast(float, m & 0xffff0000u);
-  l = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{l0, l1}, bf16x2));
-}
-
-// NPL 3: the hi / mid / lo planes; NPL 1: the bf16 (RNE) rounding alone (the bf16-operand GEMM);
-// NPL 2: the fp16 two-term split of the scaled value x sc (sc = 2^e, the operand row's scale:
-// hi = f16(x sc), lo = f16(x sc - hi), RNE, the residual exact in fp32), two planes
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-template <int NPL = 3>
-__device__ __forceinline__ void x2_split_store(unsigned short* __restrict__ s, int plane, int at,
-                                               const float* v, float sc = 1.f) {
-  if constexpr (NPL == 2) {
-    u32x4v h, l;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const f32x2 x = f32x2{v[2 * j], v[2 * j + 1]} * sc;
-      const f16x2 hh = __builtin_convertvector(x, f16x2);
-      const f32x2 r = x - __builtin_convertvector(hh, f32x2);
-      h[j] = __builtin_bit_cast(unsigned, hh);
-      l[j] = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2));
-    }
-    *reinterpret_cast<u32x4v*>(s + at) = h;
-    *reinterpret_cast<u32x4v*>(s + plane + at) = l;
-  } else if constexpr (NPL == 1) {
-    u32x4v h;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      h[j] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{v[2 * j], v[2 * j + 1]}, bf16x2));
-    *reinterpret_cast<u32x4v*>(s + at) = h;
-  } else {
-    u32x4v h, m, l;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      unsigned a, b, c;
-#if defined(DS2_X6_ABL) && DS2_X6_ABL == 3
-      // ablation build: the hi term only (no residual splits)
-      a = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{v[2 * j], v[2 * j + 1]}, bf16x2));
-      b = a;
-      c = a;
-#else
-      x2_split2(v[2 * j], v[2 * j + 1], a, b, c);
-#endif
-      h[j] = a;
-      m[j] = b;
-      l[j] = c;
-    }
-    *reinterpret_cast<u32x4v*>(s + at) = h;
-    *reinterpret_cast<u32x4v*>(s + plane + at) = m;
-    *reinterpret_cast<u32x4v*>(s + 2 * plane + at) = l;
-  }
-}
-
 // sc: the scales of the thread's staging rows (NPL 2): k-contiguous unit u -> sc[u]; a
 // row-contiguous operand's thread row -> sc[0]
 template <bool KC, int ROWS, int NPL = 3, bool M16 = false>
@@ -763,34 +698,14 @@ __device__ __forceinline__ void x2_store(unsigned short* __restrict__ s,
 #pragma unroll
     for (int u = 0; u < O::SL; ++u) {
       const int unit = t + X2T * u;
-      x2_split_store<NPL>(s, O::P, xslot_t<M16>(unit >> 2, unit & 3), v + 8 * u, sc[u]);
+      split_store8<NPL>(s, O::P, xslot_t<M16>(unit >> 2, unit & 3), v + 8 * u, sc[u]);
     }
   } else {
     const int r = t % ROWS;
 #pragma unroll
     for (int u = 0; u < O::SL; ++u)
-      x2_split_store<NPL>(s, O::P, xslot_t<M16>(r, O::SL * (t / ROWS) + u), v + 8 * u, sc[0]);
+      split_store8<NPL>(s, O::P, xslot_t<M16>(r, O::SL * (t / ROWS) + u), v + 8 * u, sc[0]);
   }
-}
-
-// c += a.b to fp32 accuracy on the 32x32x16 form (small terms first)
-__device__ __forceinline__ void x2_mma6(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x16& c) {
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
-}
-
-// the same on the 16x16x32 form
-__device__ __forceinline__ void x2_mma6_16(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x4& c) {
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[1], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2], b[0], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[2], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[0], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[1], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[0], c, 0, 0, 0);
 }
 
 // B stages of 160 rows (N = 800 / 2400 without a partial tile column): 640 (row, 8-k slot)
@@ -844,11 +759,11 @@ __device__ __forceinline__ void x2_store160(unsigned short* __restrict__ s, cons
   constexpr int P = 160 * XS;
   const int t = threadIdx.x;
   if (KC) {
-    x2_split_store<NPL>(s, P, xslot_t<M16>(t >> 2, t & 3), v, sc[0]);
-    if (t < 128) x2_split_store<NPL>(s, P, xslot_t<M16>((t + X2T) >> 2, (t + X2T) & 3), v + 8, sc[1]);
+    split_store8<NPL>(s, P, xslot_t<M16>(t >> 2, t & 3), v, sc[0]);
+    if (t < 128) split_store8<NPL>(s, P, xslot_t<M16>((t + X2T) >> 2, (t + X2T) & 3), v + 8, sc[1]);
   } else {
-    x2_split_store<NPL>(s, P, xslot_t<M16>(t & 127, t >> 7), v, sc[0]);
-    if (t < 128) x2_split_store<NPL>(s, P, xslot_t<M16>(128 + (t & 31), (t >> 5) & 3), v + 8, sc[1]);
+    split_store8<NPL>(s, P, xslot_t<M16>(t & 127, t >> 7), v, sc[0]);
+    if (t < 128) split_store8<NPL>(s, P, xslot_t<M16>(128 + (t & 31), (t >> 5) & 3), v + 8, sc[1]);
   }
 }
 
@@ -1021,11 +936,7 @@ __global__ __launch_bounds__(X2T, 1) void sxgemm2_kernel(
         for (int p = 0; p < 2; ++p) bq[p] = *reinterpret_cast<const f16x8*>(bs + p * BP + bt);
 #pragma unroll
         for (int i = 0; i < WMT; ++i) {
-          AccT c = acc[i][j];
-          c = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i][1], bq[0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i][0], bq[1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i][0], bq[0], c, 0, 0, 0);
-          acc[i][j] = c;
+          acc[i][j] = mma3h(af[i][0], af[i][1], bq[0], bq[1], acc[i][j]);
         }
       }
       x2_store<AK, X2M, NPL, true>(As[cur ^ 1], sa, a_sc);
@@ -1069,7 +980,7 @@ __global__ __launch_bounds__(X2T, 1) void sxgemm2_kernel(
           // ablation build: no MFMA, the fragments kept live
           asm volatile("" ::"v"(af[i][0]), "v"(af[i][1]), "v"(af[i][2]), "v"(bq[0]), "v"(bq[1]), "v"(bq[2]));
 #else
-          x2_mma6_16(af[i], bq, acc[i][j]);
+          acc[i][j] = mma6(af[i], bq, acc[i][j]);
 #endif
         }
       }
@@ -1115,7 +1026,7 @@ __global__ __launch_bounds__(X2T, 1) void sxgemm2_kernel(
         for (int j = 0; j < WNT; ++j) {
           if constexpr (M16) {
           } else if constexpr (NPL == 3)
-            x2_mma6(af[i], bfr[j], acc[i][j]);
+            acc[i][j] = mma6(af[i], bfr[j], acc[i][j]);
           else
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][0], bfr[j][0], acc[i][j], 0, 0, 0);
         }
@@ -1554,7 +1465,7 @@ extern "C" size_t ds2_sgemm_workspace_size(int m, int n, int k, int batch) {
 // One launch per rung of gemm_select (DESIGN.md "GEMM dispatch").  fp16x3 (default since round
 // 5; DS2_GEMM_H3=0 selects the bf16x6 kernel): the x6 kernel's plan and tiles with the operands
 // split into two fp16 terms of row-scaled values and three products per pair (see
-// x2_split_store); the row maxima come from the caller (ds2_sgemm_amax_ws) or from a pre-pass
+// split_store8); the row maxima come from the caller (ds2_sgemm_amax_ws) or from a pre-pass
 // over each operand into the workspace after the split-K slabs.  On the step's shapes 1.4-1.7x
 // the bf16x6 kernel's rate at equal or lower error against fp64 (scripts/bench_gemm_h3.py,
 // profiles/r5b_gemm_h3_vs_x6.txt).

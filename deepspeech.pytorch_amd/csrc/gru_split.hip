@@ -24,75 +24,12 @@
 
 namespace ds2 {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int XW = 4;            // waves per workgroup, one per SIMD
 constexpr int kXTraceS0 = 100, kXTraceSteps = 16;   // = gru.hip's DS2_GRU_STAMPS=2 window
 constexpr int XT = XW * 64;      // 256 threads = 16 samples x 16 units
 
-struct Tri {
-  bf16x8 hi, mid, lo;
-};
-
-// 8 fp32 values (k slots 0..3 from a, 4..7 from b) -> three bf16 terms (RNE splits; each
-// residual is exact in fp32)
-__device__ __forceinline__ Tri split3(const f32x4 a, const f32x4 b) {
-  Tri t;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float v = j < 4 ? a[j] : b[j - 4];
-    const __bf16 h = (__bf16)v;
-    const float r1 = v - (float)h;
-    const __bf16 m = (__bf16)r1;
-    const float r2 = r1 - (float)m;
-    t.hi[j] = h;
-    t.mid[j] = m;
-    t.lo[j] = (__bf16)r2;
-  }
-  return t;
-}
-
-// c += a.b to fp32 accuracy (small terms first)
-__device__ __forceinline__ f32x4 mma6(const Tri& a, const Tri& b, f32x4 c) {
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.mid, b.mid, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.lo, b.hi, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.hi, b.lo, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.mid, b.hi, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.hi, b.mid, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.hi, b.hi, c, 0, 0, 0);
-  return c;
-}
-
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
-
-// 4 fp32 -> their (hi, mid) bf16 terms packed as one 16-B run {hi01, hi23, mid01, mid23} and
-// their lo terms as one 8-B run (v_cvt_pk_bf16_f32, RNE: the terms split3 forms)
-__device__ __forceinline__ void split_pk4(const f32x4 v, u32x4& hm, u32x2& lo) {
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    const float x0 = v[2 * q], x1 = v[2 * q + 1];
-    const unsigned h = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{x0, x1}, bf16x2v));
-    const float r0 = x0 - __builtin_bit_cast(float, h << 16);
-    const float r1 = x1 - __builtin_bit_cast(float, h & 0xffff0000u);
-    const unsigned m = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{r0, r1}, bf16x2v));
-    const float l0 = r0 - __builtin_bit_cast(float, m << 16);
-    const float l1 = r1 - __builtin_bit_cast(float, m & 0xffff0000u);
-    hm[q] = h;
-    hm[2 + q] = m;
-    lo[q] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{l0, l1}, bf16x2v));
-  }
-}
-
-// the Tri of a 32-k pair from two pre-split tiles' runs (slots 0..3 tile a, 4..7 tile b)
-__device__ __forceinline__ Tri tri_of(const u32x4 ha, const u32x2 la, const u32x4 hb, const u32x2 lb) {
-  Tri t;
-  t.hi = __builtin_bit_cast(bf16x8, u32x4{ha[0], ha[1], hb[0], hb[1]});
-  t.mid = __builtin_bit_cast(bf16x8, u32x4{ha[2], ha[3], hb[2], hb[3]});
-  t.lo = __builtin_bit_cast(bf16x8, u32x4{la[0], la[1], lb[0], lb[1]});
-  return t;
-}
+// The splits and product groups (Tri / split3 / split_pk4 / tri_of / mma6, Duo / split2h /
+// mma3h) are split_mma.h's.
 
 // wave's contiguous share [p0, p0 + np) of `pairs` 32-k pairs
 __device__ __forceinline__ void pair_split(int pairs, int wave, int& p0, int& np) {
@@ -929,9 +866,11 @@ __global__ __launch_bounds__(BW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
         if (p + LWP < NPW) load_rec(p + LWP);
         if (p < np) {
           // big (hi.hi) and small (lo.hi + hi.lo) products in separate zero-C chains, and the
-          // 16x16x16 n-gate products apart from the 16x16x32 ones (see mma3h; a 16x16x16 MFMA
+          // 16x16x16 n-gate products apart from the 16x16x32 ones (split_mma.h; a 16x16x16 MFMA
           // taking a 16x16x32 result as srcC back to back also got rows 0-1 of every 4 wrong
-          // on gfx950: hipcc 7.2 inserts no wait states between the two opcodes)
+          // on gfx950: hipcc 7.2 inserts no wait states between the two opcodes).  mma3h2's
+          // products written out: a call of it moves the schedule of the <8, 3> instance
+          // (228 -> 227 VGPRs, one SGPR spill more), which nobody has timed
           const f32x4 z4 = f32x4{0.f, 0.f, 0.f, 0.f};
           f32x4 tb = z4, ts = z4;
           if constexpr (NG >= 3) {

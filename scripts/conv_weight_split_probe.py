@@ -20,7 +20,7 @@ P = ['w1', 'b1', 'g1', 'be1', 'w2', 'b2', 'g2', 'be2']
 
 
 def h3_image(w):
-    """hi + lo of the per-output-channel scaled fp16 split (csrc/rnn_common.h split2h)."""
+    """hi + lo of the per-output-channel scaled fp16 split (csrc/split_mma.h split2h)."""
     w = w.float()
     amax = w.abs().flatten(1).amax(1).clamp_min(1e-30)
     e = 14 - torch.floor(torch.log2(amax))

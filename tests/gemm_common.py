@@ -169,10 +169,10 @@ def run_gemm(kind, dev, *, m, n, k, ta, tb, alpha, beta, A, B, C, bias, batch=1,
 
 
 # ---------------------------------------------------------------------------------------------
-# The fp16x3 error model (csrc/gemm.hip x2_split_store, csrc/common.h h3_exp), in NumPy.
+# The fp16x3 error model (csrc/split_mma.h split_store8<2> and h3_exp), in NumPy.
 
 def h3_exp(amax_bits):
-    """The row-scale exponent of a claimed row maximum (float bits), as common.h h3_exp."""
+    """The row-scale exponent of a claimed row maximum (float bits), as split_mma.h h3_exp."""
     bits = np.asarray(amax_bits, dtype=np.uint32)
     E = (bits >> 23).astype(np.int64)
     e = 14 - (np.where(E == 0, 1, E) - 127)

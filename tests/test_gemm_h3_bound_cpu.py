@@ -1,8 +1,8 @@
 """CPU: the fp16x3 GEMM's error model on the scale-edge inputs of test_gpu_gemm_contract.py,
 without the kernel.
 
-A NumPy emulation of the kernel's operand split (csrc/gemm.hip x2_split_store with the row
-scales of csrc/common.h h3_exp: fp16 hi and lo of the row-scaled value, the three products
+A NumPy emulation of the kernel's operand split (csrc/split_mma.h split_store8<2> with the
+row scales of its h3_exp: fp16 hi and lo of the row-scaled value, the three products
 hi*hi + hi*lo + lo*hi exact, scaled back) is compared with the float64 product under the bound
 the GPU test asserts,
 
@@ -22,7 +22,7 @@ from gemm_common import (H3_CASES, bits_of, h3_bound, h3_case, h3_emulate, h3_ex
 
 
 def test_h3_exp_matches_the_header():
-    """common.h h3_exp: the row's largest element lands in [2^14, 2^15); a zero, inf or NaN
+    """split_mma.h h3_exp: the row's largest element lands in [2^14, 2^15); a zero, inf or NaN
     maximum keeps e = 0; the exponent clamps at 127 (2^e stays a normal float)."""
     x = np.array([1.0, 1.5, 2.0 ** -20, 65504.0, 2.0 ** 100, 0.0, np.inf, np.nan, 2.0 ** -120,
                   2.0 ** -149], dtype=np.float32)
